@@ -13,10 +13,13 @@ Panoptic CMU0 geometry, 5 views, 1024 queries x 15 joints, 4 layers, feature map
 (geometry fp32/fp64).  With N > 1 the person-queries are sharded over the ranks
 (BASELINE.json configs[2]) and the pose set is assembled with one RCCL all-gather per forward.
 
-Rank 0 prints ONE JSON line (contract in the task statement) with two extra objects:
+Rank 0 prints ONE JSON line (contract in the task statement).  A plain run does only what the headline
+figure needs: set up, warm up, time the K steps, print the line.  With --full it also fills
   roofline     : the sampling kernel (msda_gsamp / msda_fused), HIP-event timed per launch on its stream
   cpu_baseline : the CPU oracle (oracle/decoder_ref.py, "port") timed on <= 32 host threads on a
                  bounded sample (as many of the 4 layers as fit in ~30 s), scaled to samples/s
+and the other objects of the line (roofline_mfma, kernels, rank_time_split, secondary), which stay null / empty
+in a plain run.  --dump-outputs DIR writes what the timed forward returned in its last step (dump_outputs).
 """
 import argparse
 import json
@@ -332,6 +335,33 @@ def measure_secondary(config, dtype_name, inside, batch, dev, steps=20, warmup=3
     return rec
 
 
+DUMP_LIMIT = 64 << 20       # bytes a --dump-outputs directory may take in all
+DUMP_SAMPLED = 32 << 20     # what a dump over DUMP_LIMIT is cut down to
+
+
+def dump_outputs(out, path):
+    """--dump-outputs: what a caller of the timed forward receives from its last step, as <path>/<name>.npy -- hs, refs, refs2d,
+    projs2d (DQDecoder.forward's per-layer stacks; hs is absent where the query-sharded path does not gather it) and class_prob (its
+    per-layer class probabilities, stacked) -- in float32 (float64 stays float64).  If the arrays take more than DUMP_LIMIT bytes,
+    every one keeps the same fixed, seeded sample of its query axis (axis -2), about DUMP_SAMPLED bytes in all; the sample depends
+    only on the shapes, so two runs with the same arguments compare row for row.  Returns {name: shape written}."""
+    import numpy as np
+    named = list(zip(("hs", "refs", "refs2d", "projs2d"), out[:4])) + [("class_prob", torch.stack(list(out[4])))]
+    host = {name: t.detach().to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy()
+            for name, t in named if t is not None}
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT:
+        frac = DUMP_SAMPLED / total
+        for name, a in host.items():
+            n = a.shape[-2]
+            rows = np.sort(np.random.RandomState(0).choice(n, max(1, int(n * frac)), replace=False))
+            host[name] = np.ascontiguousarray(np.take(a, rows, axis=-2))
+    os.makedirs(path, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in host.items()}
+
+
 def rccl_preflight(rank, world, dev):
     """First contact with the collectives BEFORE anything is timed: one all_gather_into_tensor and one MAX all_reduce on tiny
     tensors, the library version and every rank's device.  A failure prints a line that says where it happened instead of
@@ -467,11 +497,20 @@ def main():
                     help="query-sharded runs: 1 = the whole forward as one graph, assuming every layer has a valid query "
                          "somewhere, verified after the forward and redone exactly on a miss (dist.SpeculativeShardedDecoder); "
                          "0 = graph segments with a MAX all-reduce of the flag between the layers")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what goes beyond the headline figure: the eager per-kernel profile pass (roofline, "
+                         "roofline_mfma, kernels, rank_time_split), the rocprofv3 child passes of roofline.traffic, the secondary "
+                         "workloads and the CPU oracle baseline; --profile-steps / --traffic / --secondary / --cpu-baseline "
+                         "still select among them.  Off (default): set up, warm up, time the steps, print the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the timed forward returned in its last step as DIR/<name>.npy "
+                         "(float32, at most 64 MB in all: a fixed, seeded sample of the query axis when larger)")
     ap.add_argument("--traffic", default="auto", choices=["auto", "live", "cached", "off"],
                     help="roofline.traffic (HBM bytes per launch of the sampling kernel from the PMC counters): live = two "
                          "rocprofv3 --pmc child passes of this command now (~20 s); cached = the committed "
                          "profiles/*_pmc_msda.json, only if it was measured on these kernel sources (hash) and this "
-                         "configuration; auto (default) = live when rocprofv3 is on PATH, else cached; off = null")
+                         "configuration; auto (default) = with --full live when rocprofv3 is on PATH, else cached, "
+                         "without --full off; off = null")
     ap.add_argument("--inside", default="grid", choices=["grid", "all"],
                     help="where the initial query poses sit: grid = the model's 'sample_space' grid over the whole space "
                          "(SURVEY 8(d); ~1/3 of the (view, query) pairs project outside their image and are skipped); all = the "
@@ -482,16 +521,22 @@ def main():
                          "products per 16 k, fp32 accumulation (error against fp64 not above the exact form's, "
                          "profiles/r03_f32_split_gemm.txt); exact = v_mfma_f32_32x32x2_f32, bitwise an fp32 fmaf chain")
     ap.add_argument("--pmc-child", type=int, default=0, help=argparse.SUPPRESS)
-    ap.add_argument("--cpu-baseline", type=int, default=1)
+    ap.add_argument("--cpu-baseline", type=int, default=-1, help="-1 = auto: on with --full")
     ap.add_argument("--secondary", type=int, default=-1,
                     help="1 GPU: after the headline's timed region also measure cfg-2 fp32, cfg-4 fp32, cfg-2 --inside all, cfg-5 bf16 "
                          "and cfg-2 bf16 with 2 / 4 samples per forward (>= 10 graph replays each, ~20 s) and attach them as "
                          "`secondary`; N GPUs, query-sharded: also time one-sample-per-rank replicas (`shard_samples`).  -1 = auto: "
-                         "on for the default headline command, off when a diagnostic override is given")
+                         "on for the default headline command with --full, off without it or when a diagnostic override is given")
     ap.add_argument("--batch", type=int, default=1,
                     help="samples per forward (the decoder batches natively); the headline is quoted at 1")
-    ap.add_argument("--profile-steps", type=int, default=5)
+    ap.add_argument("--profile-steps", type=int, default=-1, help="eager forwards of the per-kernel profile pass; -1 = auto: 5 with --full, else 0")
     args = ap.parse_args()
+    if args.profile_steps < 0:
+        args.profile_steps = 5 if args.full else 0
+    if args.cpu_baseline < 0:
+        args.cpu_baseline = int(args.full)
+    if args.traffic == "auto" and not args.full:
+        args.traffic = "off"
 
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: start the N ranks ourselves (one process per GPU, rendezvous on 127.0.0.1),
@@ -674,6 +719,7 @@ def main():
             def step():
                 res = inner()
                 exchange_poses(out if graph is not None else res)
+                return res
 
         for _ in range(args.warmup):
             step()
@@ -686,8 +732,9 @@ def main():
         t0 = time.perf_counter()
         if evs:
             evs[0].record()
+        last = None
         for i in range(args.steps):
-            step()
+            last = step()
             if evs:
                 evs[i + 1].record()
         torch.cuda.synchronize()
@@ -699,6 +746,9 @@ def main():
             tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev)
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
             elapsed = float(tmax.item())
+        if last is not None:        # eager steps return their outputs; a replayed graph refreshes `out` in place
+            out = last
+        dumped = dump_outputs(out, args.dump_outputs) if (args.dump_outputs and rank == 0) else None
 
         # ---- per-kernel timing (HIP events on the launch stream), eager, outside the timed region
         prof = {}
@@ -766,7 +816,7 @@ def main():
     default_headline = (args.config == "cfg2" and args.dtype == "bf16" and args.queries is None and args.valid_fraction is None
                         and args.inside == "grid" and args.inflight == 1 and args.batch == 1 and args.producer == "nchw"
                         and args.emulate_rank is None)
-    want_secondary = default_headline if args.secondary < 0 else bool(args.secondary)
+    want_secondary = (default_headline and args.full) if args.secondary < 0 else bool(args.secondary)
     secondary = {}
     if want_secondary and sharded:
         # the weak-scaling number next to the strong-scaling one, in the same job (collective: every rank takes part)
@@ -1047,7 +1097,8 @@ def main():
                       if args.dtype == "fp32" else {}),
                    "hip_graph": graph is not None, "device": arch, "cus": cus},
         "roofline": roof, "roofline_mfma": roof_mfma, "cpu_baseline": cpu, "rank_time_split": split, "kernels": kern,
-        "secondary": secondary or None, "rccl": rccl,
+        "secondary": secondary or None, "rccl": rccl, "full": args.full,
+        **({"dumped_outputs": {"dir": args.dump_outputs, "shapes": dumped}} if dumped is not None else {}),
     }
     print(json.dumps(line))
     if world > 1:

@@ -1,6 +1,7 @@
-"""bench.py's output contract (the driver parses this line): one JSON line on stdout with the metric of BASELINE.json,
-the `roofline` of the dominant kernel and the `cpu_baseline` timed beside it.  Runs the real script on the GPU with few
-steps; the CPU part only checks that the script refuses to run without a GPU instead of falling back."""
+"""bench.py's output contract (the driver parses this line): one JSON line on stdout with the metric of BASELINE.json; with
+--full also the `roofline` of the dominant kernel and the `cpu_baseline` timed beside it, in a plain run only the headline.
+Runs the real script on the GPU with few steps; the CPU part checks that the script refuses to run without a GPU instead of
+falling back, and what --dump-outputs writes."""
 import json
 import os
 import subprocess
@@ -27,7 +28,7 @@ def test_bench_refuses_to_run_without_a_gpu():
 
 @pytest.mark.gpu
 def test_bench_line_has_the_contract_fields():
-    p = _run(["--steps", "5", "--warmup", "2", "--cpu-baseline", "0"])
+    p = _run(["--steps", "5", "--warmup", "2", "--full", "--cpu-baseline", "0"])
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, "exactly one line on stdout"
@@ -99,6 +100,60 @@ def test_bench_line_has_the_contract_fields():
         assert lo <= rec["ms_per_step"] <= hi and rec["ms_per_step"] == rec["ms_per_step_median"], name
 
 
+@pytest.mark.gpu
+def test_plain_bench_run_times_the_headline_only_and_dumps_its_outputs(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W`: the headline fields, K timed steps, nothing of what --full adds; --dump-outputs writes
+    the last timed step's outputs (float32, at most 64 MB) and the line names what it wrote."""
+    dump = tmp_path / "out"
+    p = _run(["--gpus", "1", "--steps", "7", "--warmup", "2", "--dump-outputs", str(dump)])
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [l for l in p.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, "exactly one line on stdout"
+    d = json.loads(lines[0])
+    with open(os.path.join(ROOT, "BASELINE.json")) as f:
+        assert d["metric"] in json.load(f)["metric"]
+    assert d["steps"] == 7 and d["warmup"] == 2 and d["unit"] == "samples/s" and d["dtype"] == "bf16" and d["higher_is_better"] is True
+    lo, hi = d["ms_per_step_min_max"]
+    assert 0 < lo <= d["ms_per_step"] <= hi and abs(d["value"] - 1e3 / d["ms_per_step_mean"]) < 1e-2 * d["value"]
+    assert d["full"] is False and d["config"]["hip_graph"] is True
+    assert d["roofline"] is None and d["roofline_mfma"] is None and d["cpu_baseline"] is None and d["secondary"] is None
+    assert d["kernels"] == {} and d["rank_time_split"] is None
+    import numpy as np
+    shapes = d["dumped_outputs"]["shapes"]
+    assert set(shapes) == {"hs", "refs", "refs2d", "projs2d", "class_prob"}
+    total = 0
+    for name, shape in shapes.items():
+        a = np.load(str(dump / (name + ".npy")))
+        assert a.dtype == np.float32 and list(a.shape) == shape and np.isfinite(a).all(), name
+        total += a.nbytes
+    assert total <= 64 << 20
+    assert shapes["refs"][:2] == [4, 1] and shapes["refs"][3] == 3 and shapes["class_prob"][-1] == 2
+
+
+def test_dump_outputs_is_float32_bounded_and_the_same_sample_every_time(tmp_path):
+    """bench.dump_outputs on the headline's output shapes (cfg-2: 4 layers, 15 360 query-joints, 5 views): over 64 MB in all, so
+    every array keeps the same seeded sample of its query axis; two dumps of the same outputs are identical."""
+    import numpy as np
+    import bench
+    g = torch.Generator().manual_seed(0)
+    L, Lq, V, NQ = 4, 15360, 5, 1024
+    out = (torch.randn(L, 1, Lq, 256, generator=g), torch.randn(L, 1, Lq, 3, generator=g), torch.randn(L, 1, V, Lq, 2, generator=g),
+           torch.randn(L, 1, V, Lq, 2, generator=g), [torch.rand(1, NQ, 2, generator=g).to(torch.bfloat16) for _ in range(L)])
+    a = bench.dump_outputs(out, str(tmp_path / "a"))
+    b = bench.dump_outputs(out, str(tmp_path / "b"))
+    assert a == b and set(a) == {"hs", "refs", "refs2d", "projs2d", "class_prob"}
+    assert a["hs"][2] == a["refs"][2] == a["refs2d"][3] < Lq
+    total = 0
+    for name in a:
+        x, y = np.load(str(tmp_path / "a" / (name + ".npy"))), np.load(str(tmp_path / "b" / (name + ".npy")))
+        assert x.dtype == np.float32 and (x == y).all()
+        total += x.nbytes
+    assert total <= 64 << 20
+    # the sample holds rows of the originals: hs row k of the dump is one of the 15 360 rows of the last layer
+    hs = np.load(str(tmp_path / "a" / "hs.npy"))
+    assert (out[0][-1, 0].numpy() == hs[-1, 0, 0]).all(axis=1).any()
+
+
 @pytest.mark.skipif(torch.cuda.is_available(), reason="checks the no-GPU behaviour")
 def test_plain_multi_gpu_command_launches_its_own_ranks():
     """`python bench.py --gpus 2` (no torch.distributed.run in front, the shape of the driver's 1-GPU command) starts two
@@ -127,7 +182,7 @@ def test_two_rank_query_sharded_bench_runs_end_to_end_on_one_gpu(speculative):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
-                        "--speculative", str(speculative), "--traffic", "off", "--profile-steps", "1"],
+                        "--speculative", str(speculative), "--full", "--traffic", "off", "--profile-steps", "1"],
                        cwd=ROOT, env=env, timeout=900, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.strip().startswith("{")]
@@ -153,7 +208,7 @@ def test_eight_rank_query_sharded_bench_on_one_gpu():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "3", "--warmup", "1",
-                        "--traffic", "off", "--profile-steps", "1", "--secondary", "0"],
+                        "--full", "--traffic", "off", "--profile-steps", "1", "--secondary", "0"],
                        cwd=ROOT, env=env, timeout=1500, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.strip().startswith("{")]

@@ -3,7 +3,7 @@
 cd ${GRAFT_REPO_ROOT:-/root/repo}
 O=gpurun_out/r05_base; mkdir -p $O
 timeout 900 python -m pytest tests -x -q -m gpu > $O/pytest.log 2>&1; tail -3 $O/pytest.log
-timeout 600 python bench.py > $O/bench.json 2> $O/bench.err; tail -2 $O/bench.err
+timeout 600 python bench.py --full > $O/bench.json 2> $O/bench.err; tail -2 $O/bench.err
 python - <<'PY'
 import json
 d=json.loads(open("gpurun_out/r05_base/bench.json").read().strip().splitlines()[-1])

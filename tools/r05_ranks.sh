@@ -4,11 +4,11 @@
 cd ${GRAFT_REPO_ROOT:-/root/repo}
 O=gpurun_out/r05_ranks; mkdir -p $O
 for r in 0 3 7; do
-  python bench.py --emulate-rank $r --of 8 --cpu-baseline 0 --traffic off --steps 100 > $O/bench_rank${r}of8.json 2> $O/err_$r.txt; tail -2 $O/err_$r.txt
+  python bench.py --full --emulate-rank $r --of 8 --cpu-baseline 0 --traffic off --steps 100 > $O/bench_rank${r}of8.json 2> $O/err_$r.txt; tail -2 $O/err_$r.txt
 done
-python bench.py --queries 128 --cpu-baseline 0 --traffic off --secondary 0 --steps 100 > $O/bench_q128.json 2> $O/err_q128.txt
-for r in 0 1; do python bench.py --emulate-rank $r --of 2 --cpu-baseline 0 --traffic off --steps 100 > $O/bench_rank${r}of2.json 2>> $O/err_2.txt; done
-for r in 0 3; do python bench.py --emulate-rank $r --of 4 --cpu-baseline 0 --traffic off --steps 100 > $O/bench_rank${r}of4.json 2>> $O/err_4.txt; done
+python bench.py --full --queries 128 --cpu-baseline 0 --traffic off --secondary 0 --steps 100 > $O/bench_q128.json 2> $O/err_q128.txt
+for r in 0 1; do python bench.py --full --emulate-rank $r --of 2 --cpu-baseline 0 --traffic off --steps 100 > $O/bench_rank${r}of2.json 2>> $O/err_2.txt; done
+for r in 0 3; do python bench.py --full --emulate-rank $r --of 4 --cpu-baseline 0 --traffic off --steps 100 > $O/bench_rank${r}of4.json 2>> $O/err_4.txt; done
 python - <<'PY'
 import json, glob
 for f in sorted(glob.glob("gpurun_out/r05_ranks/bench_*.json")):
