@@ -1530,7 +1530,7 @@ int mvg_gather_ref(const void* feat, int dtype, const float* ref_lvl, const floa
 }
 
 int mvg_mean_views(const void* attn, int dtype, void* out, int V, int rows, int C, void* stream) {
-  if (!attn || !out || V <= 0 || C % 4 != 0) return MVG_E_BADARG;
+  if (!attn || !out || V <= 0 || rows < 0 || C % 4 != 0) return MVG_E_BADARG;
   const long n4 = (long)rows * C / 4;
   if (n4 == 0) return 0;
   const int grid = mvg_ceil_div(n4, 256);
@@ -1546,7 +1546,7 @@ int mvg_mean_views(const void* attn, int dtype, void* out, int V, int rows, int 
 
 int mvg_add_layernorm(const float* res, const void* h, int h_dtype, const float* gamma, const float* beta, float* y,
                       int rows, int C, void* stream) {
-  if (!res || !h || !gamma || !beta || !y || C % 4 != 0 || C > 1024) return MVG_E_BADARG;
+  if (!res || !h || !gamma || !beta || !y || rows < 0 || C % 4 != 0 || C > 1024) return MVG_E_BADARG;
   if (rows == 0) return 0;
   const int grid = mvg_ceil_div(rows, 4);
   if (h_dtype == MVG_F32)
@@ -1562,6 +1562,7 @@ int mvg_add_layernorm(const float* res, const void* h, int h_dtype, const float*
 int mvg_class_head(const float* tgt, const float* Wc, const float* bc, float threshold, const uint8_t* forced_valid,
                    float* prob, uint8_t* valid, int* any_valid, int B, int NQ, int J, int C, void* stream) {
   if (!tgt || !Wc || !bc || !prob || !valid || !any_valid || C % 4 != 0) return MVG_E_BADARG;
+  if (B < 0 || NQ < 0 || J <= 0) return MVG_E_BADARG;      // J = 0: the per-query means would divide by zero
   const int nq_total = B * NQ;
   if (nq_total == 0) return 0;
   hipLaunchKernelGGL(class_head_kernel, dim3(mvg_ceil_div(nq_total, 4)), dim3(256), 0, (hipStream_t)stream, tgt, Wc, bc,
@@ -1571,7 +1572,7 @@ int mvg_class_head(const float* tgt, const float* Wc, const float* bc, float thr
 }
 
 int mvg_rowdot3(const void* h, int h_dtype, const float* W3, const float* b3, float* o, int rows, int C, void* stream) {
-  if (!h || !W3 || !b3 || !o || C % 4 != 0) return MVG_E_BADARG;
+  if (!h || !W3 || !b3 || !o || rows < 0 || C % 4 != 0) return MVG_E_BADARG;
   if (rows == 0) return 0;
   const int grid = mvg_ceil_div(rows, 4);
   if (h_dtype == MVG_F32)
