@@ -122,6 +122,14 @@ int mvg_msda_backward_det_f32(const float* value, const int64_t* shapes_host, co
                               float* grad_value, float* grad_sampling_loc, float* grad_attn_weight,
                               int N, int S, int M, int D, int L, int Lq, int P,
                               void* workspace, size_t workspace_bytes, void* stream);
+/* The same with a bf16 `value` (raw bf16 bits; mixed-precision training): each value is widened exactly to fp32 as it is loaded
+ * and every later instruction is mvg_msda_backward_det_f32's, so all three fp32 outputs equal that function's on the
+ * upcast value, bit for bit.  Same shape limits and workspace. */
+int mvg_msda_backward_det_bf16(const void* value, const int64_t* shapes_host, const int64_t* starts_host,
+                               const float* sampling_loc, const float* attn_weight, const float* grad_output,
+                               float* grad_value, float* grad_sampling_loc, float* grad_attn_weight,
+                               int N, int S, int M, int D, int L, int Lq, int P,
+                               void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- stage entry points of the decoder layer ------------------------------------------ */
 
@@ -170,6 +178,11 @@ int mvg_linear_ordered(const float* A, int lda, const float* W, const float* bia
  * (deterministic; dW equals mvg_linear_wgrad_f32's partials summed slice 0 first). */
 int mvg_linear_wgrad_bias_f32(const float* dY, int ldy, const float* X, int ldx, float* partial, float* partial_db, float* dW, float* db,
                               int rows, int N, int K, int splits, void* stream);
+/* The same for bf16 dY and X (raw bf16 bits; 8-byte aligned, N, K, ldy, ldx multiples of 4) with fp32 dW / db: one bf16 MFMA per
+ * 16 k on the same tiles, slices and k order; on the same values the result equals mvg_linear_wgrad_bias_f32's bit for bit (the
+ * split form's lower parts are zero).  rows may be 0 (dW and db are then zero). */
+int mvg_linear_wgrad_bias_bf16(const void* dY, int ldy, const void* X, int ldx, float* partial, float* partial_db, float* dW, float* db,
+                               int rows, int N, int K, int splits, void* stream);
 
 /* mvg_linear with the activation formed as A + A2 on load (A2: fp32, same shape and leading dimension as A, or NULL):
  * the query term of the first layer, Linear(tgt + query_pos) (dq_decoder.py:580 `with_pos_embed` + projattn.py:180-181),

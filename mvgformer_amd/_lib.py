@@ -28,6 +28,7 @@ SIGNATURES = {
     "mvg_msda_backward_f32": [_vp] * 9 + [_i] * 7 + [_vp],
     "mvg_msda_backward_det_workspace": [_i] * 7 + [_vp],
     "mvg_msda_backward_det_f32": [_vp] * 9 + [_i] * 7 + [_vp, C.c_size_t, _vp],
+    "mvg_msda_backward_det_bf16": [_vp] * 9 + [_i] * 7 + [_vp, C.c_size_t, _vp],
     "mvg_msda_forward_f64": [_vp] * 6 + [_i] * 7 + [_vp],
     "mvg_msda_backward_f64": [_vp] * 9 + [_i] * 7 + [_vp],
     "mvg_pack_pyramid": [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _vp],
@@ -37,6 +38,7 @@ SIGNATURES = {
     "mvg_dlt_forward": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "mvg_dlt_backward": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "mvg_linear_wgrad_bias_f32": [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
+    "mvg_linear_wgrad_bias_bf16": [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "mvg_linear_ordered": [_vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
     "mvg_linear_sum": [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _vp],
     "mvg_msda_fused": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],

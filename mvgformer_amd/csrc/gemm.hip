@@ -495,6 +495,111 @@ __global__ __launch_bounds__(256, 2) void wgrad_f32s_kernel(const float* __restr
   }
 }
 
+// bf16 weight gradient (mixed-precision training): dY and X bf16, dW / db fp32.  wgrad_f32s_kernel with the split planes reduced
+// to one: the same workgroup tiles, slices, 32-row slabs, loader patches (8 rows x 4 columns, transposed in registers: the 8 row
+// values of a column are ONE 16-byte LDS store) and k order, and one v_mfma_f32_32x32x16_bf16 per 16 k where the split form issues
+// six.  On inputs that are exactly bf16 the split form's m / l parts are zero, so its five other products add exact zeros; the
+// bias partials are the same fp32 sums of the same values.
+__global__ __launch_bounds__(256, 2) void wgrad_bf16_kernel(const bf16_t* __restrict__ dY, long ldy, const bf16_t* __restrict__ X, long ldx,
+                                                            float* __restrict__ partial, int rows, int N, int K, int rows_per_split,
+                                                            float* __restrict__ partial_db) {
+  constexpr int BM = 128, BN = 128, BP = 64;    // LDS row: 32 k x bf16, the split form's first plane (same slot permutation)
+  __shared__ __attribute__((aligned(16))) char lds[(BM + BN) * BP];
+  char* ldsA = lds;
+  char* ldsB = lds + BM * BP;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1, rl = lane & 31, h = lane >> 5;
+  const int m0 = blockIdx.y * BM, n0 = blockIdx.x * BN;
+  const long r_begin = (long)blockIdx.z * rows_per_split, r_end = min((long)rows, r_begin + rows_per_split);
+  const int opnd = tid >> 7, p = tid & 127, rgrp = p >> 5, cgrp = p & 31;
+  const bf16_t* src = opnd ? X : dY;
+  const long ld = opnd ? ldx : ldy;
+  const int width = opnd ? K : N, c0 = (opnd ? n0 : m0) + 4 * cgrp;
+  char* dst = opnd ? ldsB : ldsA;
+  u16x4 x[8];
+  auto gload = [&](long r0) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const long r = r0 + 8 * rgrp + i;
+      const u16x4 v = *reinterpret_cast<const u16x4*>(src + min(r, (long)rows - 1) * ld + min(c0, width - 4));
+      x[i] = (r < r_end && c0 < width) ? v : u16x4{0, 0, 0, 0};
+    }
+  };
+  float bsum[4] = {0.f, 0.f, 0.f, 0.f};
+  auto lstore = [&]() {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      uint4 pk;
+      pk.x = (unsigned)x[0][c] | ((unsigned)x[1][c] << 16);
+      pk.y = (unsigned)x[2][c] | ((unsigned)x[3][c] << 16);
+      pk.z = (unsigned)x[4][c] | ((unsigned)x[5][c] << 16);
+      pk.w = (unsigned)x[6][c] | ((unsigned)x[7][c] << 16);
+      const int row = 4 * cgrp + c;
+      *reinterpret_cast<uint4*>(dst + row * BP + split_slot(row, rgrp)) = pk;
+      if (opnd == 0) {
+        float v[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[i] = bf16_to_f32(x[i][c]);
+        bsum[c] += ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
+      }
+    }
+  };
+  f32x16 acc[2][2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+  const int nslab = (int)((r_end - r_begin + 31) / 32);
+  if (nslab > 0) {
+    gload(r_begin);
+    lstore();
+  }
+  __syncthreads();
+  for (int t = 0; t < nslab; ++t) {
+    if (t + 1 < nslab) gload(r_begin + (long)(t + 1) * 32);
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+      bf16x8 a[2], b[2];
+#pragma unroll
+      for (int i = 0; i < 2; ++i) a[i] = *reinterpret_cast<const bf16x8*>(ldsA + (wm * 64 + i * 32 + rl) * BP + split_slot(rl, 2 * g + h));
+#pragma unroll
+      for (int j = 0; j < 2; ++j) b[j] = *reinterpret_cast<const bf16x8*>(ldsB + (wn * 64 + j * 32 + rl) * BP + split_slot(rl, 2 * g + h));
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b[j], a[i], acc[i][j], 0, 0, 0);
+    }
+    __syncthreads();
+    if (t + 1 < nslab) {
+      lstore();
+      __syncthreads();
+    }
+  }
+  float* outz = partial + (long)blockIdx.z * N * K;
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int m = m0 + wm * 64 + i * 32 + rl;
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int n = n0 + wn * 64 + j * 32 + 8 * g + 4 * h;
+        if (m < N && n < K)
+          *reinterpret_cast<f32x4*>(outz + (long)m * K + n) = f32x4{acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]};
+      }
+  }
+  if (partial_db != nullptr && blockIdx.x == 0) {
+    float* red = reinterpret_cast<float*>(lds);       // 4 x 128 floats = 2 KB of the (dead) operand tiles
+    if (opnd == 0)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) red[rgrp * BM + 4 * cgrp + c] = bsum[c];
+    __syncthreads();
+    if (tid < BM && m0 + tid < N)
+      partial_db[(long)blockIdx.z * N + m0 + tid] = (red[tid] + red[BM + tid]) + (red[2 * BM + tid] + red[3 * BM + tid]);
+  }
+}
+
 // dW = sum over the slices of partial (Z, N*K) and db = sum of partial_db (Z, N), slice 0 first: one float4 (or one bias entry) per thread
 __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restrict__ partial, const float* __restrict__ partial_db,
                                                            float* __restrict__ dW, float* __restrict__ db, int Z, long nk4, int N) {
@@ -600,6 +705,27 @@ extern "C" int mvg_linear_wgrad_bias_f32(const float* dY, int ldy, const float* 
   dim3 grid((K + 127) / 128, (N + 127) / 128, splits);
   hipLaunchKernelGGL(wgrad_f32s_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, dY, (long)ldy, X, (long)ldx, partial, rows, N, K, rps,
                      db ? partial_db : (float*)nullptr);
+  MVG_LAUNCH_CHECK();
+  const long nk4 = (long)N * K / 4;
+  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((nk4 + (db ? N : 0) + 255) / 256)), dim3(256), 0, (hipStream_t)stream, partial,
+                     partial_db, dW, db, splits, nk4, N);
+  MVG_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int mvg_linear_wgrad_bias_bf16(const void* dY, int ldy, const void* X, int ldx, float* partial, float* partial_db, float* dW,
+                                          float* db, int rows, int N, int K, int splits, void* stream) {
+  if (!dY || !X || !partial || !dW || rows < 0 || N <= 0 || K <= 0 || splits <= 0) return MVG_E_BADARG;
+  if (db && !partial_db) return MVG_E_BADARG;
+  if (N % 4 != 0 || K % 4 != 0 || ldy % 4 != 0 || ldx % 4 != 0 || ldy < N || ldx < K) return MVG_E_BADARG;
+  if ((reinterpret_cast<uintptr_t>(dY) | reinterpret_cast<uintptr_t>(X)) % 8 != 0 ||
+      (reinterpret_cast<uintptr_t>(partial) | reinterpret_cast<uintptr_t>(dW)) % 16 != 0)
+    return MVG_E_BADARG;
+  // rows == 0: every slice is empty and writes zero partials (no operand is read)
+  const int rps = ((rows + splits - 1) / splits + 31) / 32 * 32;
+  dim3 grid((K + 127) / 128, (N + 127) / 128, splits);
+  hipLaunchKernelGGL(wgrad_bf16_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dY, (long)ldy, (const bf16_t*)X, (long)ldx,
+                     partial, rows, N, K, rps, db ? partial_db : (float*)nullptr);
   MVG_LAUNCH_CHECK();
   const long nk4 = (long)N * K / 4;
   hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((nk4 + (db ? N : 0) + 255) / 256)), dim3(256), 0, (hipStream_t)stream, partial,

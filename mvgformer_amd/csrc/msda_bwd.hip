@@ -240,8 +240,11 @@ __device__ __forceinline__ float sum8(float v) {
   return v;
 }
 
+// TV: storage type of `value` (float, or bf16_t for mixed-precision training).  Only the patch load differs: a bf16 value is
+// widened exactly to fp32 on its way into LDS, and everything after it is the fp32 kernel's.
+template <typename TV>
 __global__ __launch_bounds__(BW_NT) void bw_reduce_kernel(
-    const float* __restrict__ value, const float* __restrict__ loc, const float* __restrict__ wgt, const float* __restrict__ gout,
+    const TV* __restrict__ value, const float* __restrict__ loc, const float* __restrict__ wgt, const float* __restrict__ gout,
     BwLevels lv, const int* __restrict__ offset, const unsigned* __restrict__ list, const unsigned* __restrict__ gmax_bits,
     unsigned long long* __restrict__ accum, float* __restrict__ gvalue, float* __restrict__ gloc, float* __restrict__ gwgt, int N,
     int S, int Lq, int M, int P) {
@@ -281,11 +284,11 @@ __global__ __launch_bounds__(BW_NT) void bw_reduce_kernel(
     }
     return;
   }
-  const float* vbase = value + ((long)n * S + lv.start[l]) * row_stride + (long)m * BW_D;
+  const TV* vbase = value + ((long)n * S + lv.start[l]) * row_stride + (long)m * BW_D;
   for (int i = tid; i < BW_P * BW_P * BW_D; i += BW_NT) {
     const int px = i >> 5, ch = i & 31;
     const int y = y0 + px / BW_P, x = x0 + px % BW_P;
-    vpatch[px][ch] = (y < H && x < W) ? vbase[((long)y * W + x) * row_stride + ch] : 0.f;
+    vpatch[px][ch] = (y < H && x < W) ? load1<TV>(vbase + ((long)y * W + x) * row_stride + ch) : 0.f;
     apatch[px][ch] = 0ull;
   }
   __syncthreads();
@@ -485,10 +488,15 @@ size_t mvg_msda_backward_det_workspace(int N, int S, int M, int D, int L, int Lq
   return bw_layout(N, S, M, Lq, (long)L * P, bpi).bytes;
 }
 
-int mvg_msda_backward_det_f32(const float* value, const int64_t* shapes_host, const int64_t* starts_host,
-                              const float* sampling_loc, const float* attn_weight, const float* grad_output,
-                              float* grad_value, float* grad_sampling_loc, float* grad_attn_weight, int N, int S, int M,
-                              int D, int L, int Lq, int P, void* workspace, size_t workspace_bytes, void* stream) {
+}  // extern "C"
+
+namespace {
+
+template <typename TV>
+int backward_det(const TV* value, const int64_t* shapes_host, const int64_t* starts_host, const float* sampling_loc,
+                 const float* attn_weight, const float* grad_output, float* grad_value, float* grad_sampling_loc,
+                 float* grad_attn_weight, int N, int S, int M, int D, int L, int Lq, int P, void* workspace, size_t workspace_bytes,
+                 void* stream) {
   if (!value || !shapes_host || !starts_host || !sampling_loc || !attn_weight || !grad_output || !grad_value ||
       !grad_sampling_loc || !grad_attn_weight || !workspace)
     return MVG_E_BADARG;
@@ -540,12 +548,33 @@ int mvg_msda_backward_det_f32(const float* value, const int64_t* shapes_host, co
   hipLaunchKernelGGL(bw_scan_kernel, dim3(1), dim3(1024), 0, st, (const int*)total, offset, (int)nbins);
   hipLaunchKernelGGL((bw_part_kernel<1>), dim3(N * BW_PARTS), dim3(1024), lds, st, sampling_loc, lv, cnt, (const int*)offset,
                      list, Lq, M, P, (int)bpi, per_img, chunk, grad_sampling_loc, grad_attn_weight);
-  hipLaunchKernelGGL(bw_reduce_kernel, dim3((unsigned)(nbins * BW_SPLIT)), dim3(BW_NT), 0, st, value, sampling_loc, attn_weight,
+  hipLaunchKernelGGL(bw_reduce_kernel<TV>, dim3((unsigned)(nbins * BW_SPLIT)), dim3(BW_NT), 0, st, value, sampling_loc, attn_weight,
                      grad_output, lv, (const int*)offset, (const unsigned*)list, (const unsigned*)gmax, accum, grad_value,
                      grad_sampling_loc, grad_attn_weight, N, S, Lq, M, P);
   hipLaunchKernelGGL((bw_shared_kernel<1>), shared_grid, dim3(256), 0, st, accum, gmax, grad_value, lv, S, M, rows_per_img);
   MVG_LAUNCH_CHECK();
   return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mvg_msda_backward_det_f32(const float* value, const int64_t* shapes_host, const int64_t* starts_host,
+                              const float* sampling_loc, const float* attn_weight, const float* grad_output,
+                              float* grad_value, float* grad_sampling_loc, float* grad_attn_weight, int N, int S, int M,
+                              int D, int L, int Lq, int P, void* workspace, size_t workspace_bytes, void* stream) {
+  return backward_det<float>(value, shapes_host, starts_host, sampling_loc, attn_weight, grad_output, grad_value, grad_sampling_loc,
+                             grad_attn_weight, N, S, M, D, L, Lq, P, workspace, workspace_bytes, stream);
+}
+
+int mvg_msda_backward_det_bf16(const void* value, const int64_t* shapes_host, const int64_t* starts_host,
+                               const float* sampling_loc, const float* attn_weight, const float* grad_output,
+                               float* grad_value, float* grad_sampling_loc, float* grad_attn_weight, int N, int S, int M,
+                               int D, int L, int Lq, int P, void* workspace, size_t workspace_bytes, void* stream) {
+  return backward_det<bf16_t>(reinterpret_cast<const bf16_t*>(value), shapes_host, starts_host, sampling_loc, attn_weight, grad_output,
+                              grad_value, grad_sampling_loc, grad_attn_weight, N, S, M, D, L, Lq, P, workspace, workspace_bytes,
+                              stream);
 }
 
 }  // extern "C"

@@ -174,6 +174,7 @@ class DQDecoderLayer(MvPDecoderLayer):
         self.filter_query = filter_query
         self.d_model = d_model
         self.compute_dtype = torch.float32
+        self.training_dtype = torch.float32     # set_training_dtype
         self.use_fused_chains = True    # bf16 inference: LDS-resident Linear chains (csrc/chain.hip)
         # fp32 inference: the same two chains on pre-split operands (csrc/f32s.hip); MVG_F32_FUSED=0: one launch per GEMM / row op
         self.use_fused_chains_f32 = os.environ.get("MVG_F32_FUSED", "1") != "0"
@@ -201,6 +202,18 @@ class DQDecoderLayer(MvPDecoderLayer):
             raise ValueError("compute dtype must be float32 or bfloat16")
         self.compute_dtype = dtype
         self.proj_attn.compute_dtype = dtype
+        return self
+
+    def set_training_dtype(self, dtype):
+        """Precision of the autograd path (forward_autograd: grad enabled, or dropout active).  torch.float32 (default): fp32 storage,
+        fp32-accurate GEMMs.  torch.bfloat16: mixed precision -- bf16 GEMM operands with fp32 accumulation, fp32 master weights and
+        fp32 gradients, a bf16 value for the sampling op (rounding points: forward_autograd).  LayerNorm, softmax, dropout, sigmoid
+        and all geometry stay fp32 / fp64.  The native inference path, compute_dtype, GraphedDecoder and the query-sharded
+        runners do not read it.  torch.autocast is NOT consulted: this switch alone selects the bf16 path."""
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError("training dtype must be float32 or bfloat16")
+        self.training_dtype = dtype
+        self.proj_attn.training_dtype = dtype
         return self
 
     def _check_supported(self):
@@ -403,12 +416,34 @@ class DQDecoderLayer(MvPDecoderLayer):
             self._any_valid_hook(st["any_valid"])
         return self.forward_triangulate(st, ctx)
 
+    def _lin_bf16(self, x, weight, bias, relu=False):
+        from .functions import linear_bf16
+        return linear_bf16(x, weight, bias, self._wc, "train16/%x" % id(weight), relu=relu)
+
     def forward_autograd(self, tgt, query_pos, reference_points, src_views, src_spatial_shapes, level_start_index, meta,
                          indices=None, threshold=0.5):
         """Training path: the same layer as differentiable torch ops (fp32) with the HIP sampling op
         (DeformFunction forward + backward kernels) inside ProjAttn -- what run/train_3d.py needs
         (SURVEY.md section 8 f2).  Dense compute + masking instead of the reference's gather/pad/scatter
-        (every step is per-query, so values and gradients of the kept queries are the same)."""
+        (every step is per-query, so values and gradients of the kept queries are the same).
+
+        training_dtype bfloat16 (set_training_dtype; torch.autocast is not consulted) rounds to bf16 at exactly these points:
+          forward
+            * the input of every Linear with both widths multiples of 64 (LinearBF16): the ProjAttn value projection rayconv, its
+              [sampling_offsets; attention_weights] projection, output_proj, feature_update_mlp, linear1 / linear2 (FFN) and the
+              first two pose-MLP layers -- and their weights (cast once per optimizer step); products accumulate in fp32, bias
+              and ReLU are applied to the fp32 sum;
+            * the value projection's output (the sampling op's value is bf16), and so the sampling op's output (bf16, from fp32
+              arithmetic on the widened value);
+            * with a bf16 packed pyramid (a DecoderContext built for compute_dtype bf16): the pyramid itself, and the gathered
+              reference-point input bf16(bilinear + query);
+          backward
+            * dy of every LinearBF16 before its dgrad and wgrad (dW, db fp32 sums of bf16 products);
+            * the gradient of every bf16 tensor above (value, the sampling output, a bf16 gathered input): autograd hands it back
+              in that tensor's dtype;
+          everything else -- the 2- and 3-output heads (class_embed, the last pose layer: fp32-accurate split GEMMs), LayerNorm,
+          softmax, dropout, sigmoid, the sampling op's locations / weights / gradients (fp32), UncropUndistort (fp32),
+          DenseDLT (fp64) -- is the fp32 path's arithmetic."""
         from . import geometry_torch as G
         B, Lq, C = tgt.shape
         J = self.num_joints
@@ -454,6 +489,8 @@ class DQDecoderLayer(MvPDecoderLayer):
             self.proj_attn._packed_feat = None
         a_all = inside_all.unsqueeze(-1).to(a_all.dtype) * a_all                   # dq_decoder.py:585-586
         from .functions import linear as lin
+        if self.training_dtype == torch.bfloat16:
+            lin = self._lin_bf16
         mean = a_all.view(V, B, Lq, C).mean(0)
         tgt_update = self.norm2(tgt + self.dropout2(lin(mean, self.feature_update_mlp.weight, self.feature_update_mlp.bias)))
         if self.open_forward_ffn:           # forward_ffn (mvp_decoder.py:94-98) with the two GEMMs on mvg_linear
@@ -730,6 +767,15 @@ class DQDecoder(MvPDecoder):
     def set_compute_dtype(self, dtype):
         for layer in self.layers:
             layer.set_compute_dtype(dtype)
+        return self
+
+    def set_training_dtype(self, dtype):
+        """DQDecoderLayer.set_training_dtype on every layer (float32 default, or bfloat16 mixed precision for the autograd path;
+        torch.autocast is not consulted)"""
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError("training dtype must be float32 or bfloat16")
+        for layer in self.layers:
+            layer.set_training_dtype(dtype)
         return self
 
     def fork_side_stream(self, device, f32_shape=None):

@@ -32,6 +32,10 @@ class DeformFunction(Function):
     def backward(ctx, grad_output):
         value, shapes, starts, loc, attn = ctx.saved_tensors
         DF._check_step(value, ctx.im2col_step)
+        if value.dtype == torch.bfloat16:
+            # bf16 training: the op's output is bf16 (so is the gradient autograd hands back); the backward takes fp32 and
+            # returns an fp32 grad_value (autograd rounds it to the bf16 value's dtype)
+            grad_output = grad_output.float()
         with DF._device_of(value):
             gv, gl, ga = ops.msda_backward(value, shapes, starts, loc, attn, grad_output.contiguous(), host=ctx.host_levels)
         return gv, None, None, gl, ga, None
@@ -106,6 +110,71 @@ class LinearF32S(Function):
         elif want_b:
             db = dy.sum(0)[:N]
         return dx, dw, db, None
+
+
+class LinearBF16(Function):
+    """bf16 mixed-precision sibling of LinearF32S: y = act(x W^T + b) with bf16 operands, fp32 accumulation and fp32 master weights.
+         forward  y  = mvg_linear(x, W16): an fp32 x is rounded to bf16 as it is loaded, bias + ReLU in the fp32 epilogue, y fp32 (or
+                       bf16 when out_bf16: the value projection, whose consumer -- the sampling op -- reads bf16)
+         dgrad    dx = mvg_linear(bf16(dy), W16^T)                            fp32 dx
+         wgrad    dW, db = mvg_linear_wgrad_bias_bf16(bf16(dy), bf16(x))      fp32, slice-ordered (deterministic)
+       w16 / w16t: the bf16 weight and its transpose, cast once per optimizer step by the caller (bf16_weights); the gradient goes to
+       the fp32 `weight`.  Saves bf16(x) and, for the ReLU mask, the output.  Needs N % 64 == 0 (dgrad's K) and K % 64 == 0: the
+       2- and 3-output heads stay on LinearF32S."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, w16, w16t, relu, out_bf16):
+        x2 = x.reshape(-1, x.shape[-1])
+        if x2.stride(1) != 1 or x2.stride(0) != x2.shape[1]:
+            x2 = x2.contiguous()
+        N = w16.shape[0]
+        y = ops.linear(x2, w16, bias, out_dtype=torch.bfloat16 if out_bf16 else torch.float32, relu=bool(relu))
+        x16 = x2 if x2.dtype == torch.bfloat16 else x2.to(torch.bfloat16)
+        ctx.relu = bool(relu)
+        ctx.x_shape = x.shape
+        ctx.has_bias = bias is not None
+        ctx.save_for_backward(x16, w16t, y if relu else None)
+        return y.view(*x.shape[:-1], N)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_y):
+        x16, w16t, y = ctx.saved_tensors
+        N = w16t.shape[1]
+        dy = grad_y.reshape(-1, N)
+        if ctx.relu:
+            dy = torch.ops.aten.threshold_backward(dy, y.to(dy.dtype) if y.dtype != dy.dtype else y, 0.0)
+        dy16 = dy.to(torch.bfloat16).contiguous()
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            dx = ops.linear(dy16, w16t, None, out_dtype=torch.float32).view(ctx.x_shape)
+        want_b = ctx.has_bias and ctx.needs_input_grad[2]
+        if ctx.needs_input_grad[1]:
+            dw, db = ops.linear_wgrad_bias(dy16, x16, want_bias=want_b)
+        elif want_b:
+            db = dy16.float().sum(0)
+        return dx, dw, db, None, None, None, None
+
+
+def bf16_weights(cache, key, params, build=None):
+    """(W16, W16^T) of a Linear weight for LinearBF16, cast once per optimizer step: cached on the source parameters' versions in
+    `cache` (a projattn.WeightCache).  build(*params) forms the fp32 weight when it is not params[0] (ProjAttn's concatenated
+    [sampling_offsets; attention_weights])."""
+    w16 = cache.get(key, params, torch.bfloat16, build, sync=False)
+    w16t = cache.get(key + "^T", params, torch.bfloat16, lambda *p: (build(*p) if build else p[0]).t(), sync=False)
+    return w16, w16t
+
+
+def linear_bf16(x, weight, bias, cache, key, params=None, build=None, relu=False, out_bf16=False):
+    """the bf16 training path's Linear: LinearBF16 where its shape rules hold (both widths multiples of 64), LinearF32S otherwise
+    (the 2- and 3-output heads: fp32 operands).  `weight` is the differentiable fp32 weight; its bf16 copies come from `cache`
+    under `key`, stamped with `params` (default: (weight,))."""
+    N, K = weight.shape
+    if x.is_cuda and N % 64 == 0 and K % 64 == 0 and x.numel() > 0:
+        w16, w16t = bf16_weights(cache, key, params or (weight,), build)
+        return LinearBF16.apply(x, weight, bias, w16, w16t, relu, out_bf16)
+    y = linear(x.float(), weight, bias, relu)
+    return y.to(torch.bfloat16) if out_bf16 else y
 
 
 def linear(x, weight, bias=None, relu=False):

@@ -136,6 +136,8 @@ def msda_backward(value, spatial_shapes, level_start_index, sampling_loc, attn_w
     entries -- any weight magnitude and any gradient magnitude down to 2^-96 are exact int32 contributions; what is smaller than
     2^-31 of its image's largest possible contribution rounds to zero.  Non-finite grad_output entries do not enter grad_value."""
     L.require_cuda(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output)
+    if value.dtype == torch.bfloat16:
+        return _msda_backward_bf16(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output, host)
     if value.dtype not in (torch.float32, torch.float64):
         raise RuntimeError("deform_backward: float32 / float64 only")        # AT_DISPATCH_FLOATING_TYPES, deform_cuda.cu:145
     for t in (sampling_loc, attn_weight, grad_output):
@@ -165,6 +167,42 @@ def msda_backward(value, spatial_shapes, level_start_index, sampling_loc, attn_w
                                         L.ptr(sampling_loc), L.ptr(attn_weight), L.ptr(grad_output), L.ptr(gv), L.ptr(gl),
                                         L.ptr(ga), N, S, M, D, nl, Lq, P, L.stream_ptr())
     L.check(rc, "mvg_msda_backward")
+    return gv, gl, ga
+
+
+def _msda_backward_bf16(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output, host):
+    """bf16 value (mixed-precision training), fp32 sampling_loc / attn_weight / grad_output -> three fp32 gradients.  The
+    deterministic form reads the bf16 patch and widens it exactly (mvg_msda_backward_det_bf16): bit-identical to the fp32 call on
+    value.float().  Where that form does not take the shape (workspace 0) or MVG_BACKWARD=atomic, the fp32 atomic kernel runs on
+    value.float()."""
+    for name, t in (("sampling_loc", sampling_loc), ("attn_weight", attn_weight), ("grad_output", grad_output)):
+        if t.dtype != torch.float32:
+            raise RuntimeError("deform_backward: with a bfloat16 value, %s must be float32 (got %s)" % (name, t.dtype))
+    if not value.is_contiguous():
+        raise RuntimeError("value tensor has to be contiguous")
+    grad_output = grad_output.contiguous()
+    N, S, M, D = value.shape
+    _, Lq, _, nl, P, _ = sampling_loc.shape
+    lib = L.load()
+    if BACKWARD_MODE != "atomic":
+        shapes_c, starts_c = host if host is not None else host_levels(spatial_shapes, level_start_index)
+        ws_bytes = int(lib.mvg_msda_backward_det_workspace(N, S, M, D, nl, Lq, P, shapes_c))
+        if ws_bytes:
+            ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=value.device)
+            gv = torch.empty(value.shape, dtype=torch.float32, device=value.device)
+            gl, ga = torch.empty_like(sampling_loc), torch.empty_like(attn_weight)
+            with _timed("msda_backward_det_bf16"):
+              L.check(lib.mvg_msda_backward_det_bf16(L.ptr(value), shapes_c, starts_c, L.ptr(sampling_loc), L.ptr(attn_weight),
+                                                     L.ptr(grad_output), L.ptr(gv), L.ptr(gl), L.ptr(ga), N, S, M, D, nl, Lq, P,
+                                                     L.ptr(ws), ws_bytes, L.stream_ptr()), "mvg_msda_backward_det_bf16")
+            return gv, gl, ga
+    v32 = value.float()
+    gv = torch.zeros_like(v32)
+    gl = torch.empty_like(sampling_loc)
+    ga = torch.empty_like(attn_weight)
+    L.check(lib.mvg_msda_backward_f32(L.ptr(v32), L.ptr(spatial_shapes), L.ptr(level_start_index), L.ptr(sampling_loc),
+                                      L.ptr(attn_weight), L.ptr(grad_output), L.ptr(gv), L.ptr(gl), L.ptr(ga), N, S, M, D, nl, Lq, P,
+                                      L.stream_ptr()), "mvg_msda_backward")
     return gv, gl, ga
 
 
@@ -275,16 +313,17 @@ def linear_wgrad(dy, x, splits=None):
 
 def linear_wgrad_bias(dy, x, want_bias=True, splits=None):
     """(dW (N, K), db (N) | None) = (dy^T x, column sums of dy) (mvg_linear_wgrad_bias_f32): the weight-gradient launch also leaves the
-    bias gradient's per-slice partials, a second small launch adds both in slice order."""
+    bias gradient's per-slice partials, a second small launch adds both in slice order.  bf16 dy and x (both) run
+    mvg_linear_wgrad_bias_bf16: one bf16 MFMA per 16 k, fp32 accumulation, fp32 dW / db, the same slices and order."""
     rows, N = dy.shape
     K = x.shape[1]
+    if dy.dtype == torch.bfloat16 and x.dtype == torch.bfloat16:
+        return _linear_wgrad_bias_bf16(dy, x, want_bias, splits)
     if (dy.dtype != torch.float32 or x.dtype != torch.float32 or dy.stride(1) != 1 or x.stride(1) != 1 or x.shape[0] != rows
             or N % 4 or K % 4):
         raise RuntimeError("mvg_linear_wgrad_bias: fp32 row-major (rows, N) / (rows, K) operands with N, K multiples of 4 required")
     if splits is None:
-        tiles = ((N + 127) // 128) * ((K + 127) // 128)
-        # ~512 workgroups (two per CU), at most 128 slices, at least 256 rows per slice (tools/bench_wgrad.py)
-        splits = max(1, min((rows + 255) // 256, 128, (512 + tiles - 1) // tiles))
+        splits = _wgrad_splits(rows, N, K)
     partial = torch.empty((splits, N, K), dtype=torch.float32, device=dy.device)
     dw = torch.empty((N, K), dtype=torch.float32, device=dy.device)
     pdb = torch.empty((splits, N), dtype=torch.float32, device=dy.device) if want_bias else None
@@ -292,6 +331,34 @@ def linear_wgrad_bias(dy, x, want_bias=True, splits=None):
     with _timed("linear_wgrad_bias_%dx%dx%d" % (N, K, rows)):
       L.check(L.load().mvg_linear_wgrad_bias_f32(L.ptr(dy), dy.stride(0), L.ptr(x), x.stride(0), L.ptr(partial), L.ptr(pdb), L.ptr(dw),
                                                  L.ptr(db), rows, N, K, splits, L.stream_ptr()), "mvg_linear_wgrad_bias_f32")
+    return dw, db
+
+
+def _wgrad_splits(rows, N, K):
+    tiles = ((N + 127) // 128) * ((K + 127) // 128)
+    # ~512 workgroups (two per CU), at most 128 slices, at least 256 rows per slice (tools/bench_wgrad.py)
+    return max(1, min((rows + 255) // 256, 128, (512 + tiles - 1) // tiles))
+
+
+def _linear_wgrad_bias_bf16(dy, x, want_bias, splits):
+    rows, N = dy.shape
+    K = x.shape[1]
+    if (dy.stride(1) != 1 or x.stride(1) != 1 or x.shape[0] != rows or N % 4 or K % 4 or dy.stride(0) % 4 or x.stride(0) % 4
+            or dy.data_ptr() % 8 or x.data_ptr() % 8):
+        raise RuntimeError("mvg_linear_wgrad_bias: bf16 row-major (rows, N) / (rows, K) operands with N, K and the row strides "
+                           "multiples of 4 required")
+    if rows == 0:
+        return (torch.zeros((N, K), dtype=torch.float32, device=dy.device),
+                torch.zeros((N,), dtype=torch.float32, device=dy.device) if want_bias else None)
+    if splits is None:
+        splits = _wgrad_splits(rows, N, K)
+    partial = torch.empty((splits, N, K), dtype=torch.float32, device=dy.device)
+    dw = torch.empty((N, K), dtype=torch.float32, device=dy.device)
+    pdb = torch.empty((splits, N), dtype=torch.float32, device=dy.device) if want_bias else None
+    db = torch.empty((N,), dtype=torch.float32, device=dy.device) if want_bias else None
+    with _timed("linear_wgrad_bias_bf16_%dx%dx%d" % (N, K, rows)):
+      L.check(L.load().mvg_linear_wgrad_bias_bf16(L.ptr(dy), dy.stride(0), L.ptr(x), x.stride(0), L.ptr(partial), L.ptr(pdb), L.ptr(dw),
+                                                  L.ptr(db), rows, N, K, splits, L.stream_ptr()), "mvg_linear_wgrad_bias_bf16")
     return dw, db
 
 

@@ -44,7 +44,8 @@ class WeightCache:
     def __init__(self):
         self._store = {}
 
-    def get(self, key, params, dtype, build=None):
+    def get(self, key, params, dtype, build=None, sync=True):
+        """sync=False: the entry is only read on the stream that builds it (the training path), no wait for the build"""
         stamp = tuple((id(p), p._version, p.device) for p in params) + (dtype,)
         hit = self._store.get(key)
         if hit is not None and hit[0] == stamp:
@@ -65,7 +66,7 @@ class WeightCache:
         # An entry is built on whatever stream is current and then handed out to every stream (the decoder issues
         # query-independent work on a side stream): finish the build before anybody can see the entry.  Rare (first
         # use / parameters changed).
-        if t.is_cuda:
+        if t.is_cuda and sync:
             torch.cuda.current_stream(t.device).synchronize()
         out = (t,) + extra if extra else t
         self._store[key] = (stamp, out)
@@ -118,6 +119,8 @@ class ProjAttn(nn.Module):
         if self.sort_pairs in ("0", "off", "False"):
             self.sort_pairs = False
         self._wc = WeightCache()
+        # precision of the autograd path (the layer's set_training_dtype): float32, or bfloat16 operands with fp32 accumulation
+        self.training_dtype = torch.float32
         self._vp = None
         self._vp_event = None
         self._G = None
@@ -431,9 +434,12 @@ class ProjAttn(nn.Module):
                                       1, n_views)
             return out.view(n_views, Len_q, c).to(query.dtype)
         sample_grid = torch.clamp(reference_points * 2.0 - 1.0, -1.1, 1.1)
+        # bf16 mixed-precision training (DQDecoderLayer.set_training_dtype): the Linears on LinearBF16, a bf16 value for the
+        # sampling op, and a bf16 packed pyramid taken as it is (its consumers round to bf16 anyway)
+        bf = self.training_dtype == torch.bfloat16
         packed = getattr(self, "_packed_feat", None)
-        if (packed is not None and packed.dtype == torch.float32 and packed.shape[0] == n_views and packed.shape[2] == c
-                and not any(s.requires_grad for s in src_views)):
+        if (packed is not None and (packed.dtype == torch.float32 or (bf and packed.dtype == torch.bfloat16))
+                and packed.shape[0] == n_views and packed.shape[2] == c and not any(s.requires_grad for s in src_views)):
             # the channels-last pyramid the decoder packed once per forward IS cat + permute of the maps (projattn.py:160); only
             # when no gradient flows into the feature maps (the packing kernel is not differentiable)
             input_flatten = packed
@@ -441,7 +447,7 @@ class ProjAttn(nn.Module):
             input_flatten = torch.cat([s.flatten(2) for s in src_views], dim=-1).permute(0, 2, 1)
         assert int((input_spatial_shapes[:, 0] * input_spatial_shapes[:, 1]).sum()) == input_flatten.shape[1]
         xin = None
-        if (self.ref_gather_native and input_flatten.dtype == torch.float32 and not input_flatten.requires_grad
+        if (self.ref_gather_native and (input_flatten.dtype == torch.float32 or bf) and not input_flatten.requires_grad
                 and not reference_points.requires_grad and c % 4 == 0):
             # neither the maps nor the reference points carry a gradient (run/train_3d.py with a frozen backbone and
             # detach_refpoints_cameraprj, every shipped YAML): the inference path's gather kernel forms feats + query in one launch
@@ -461,15 +467,25 @@ class ProjAttn(nn.Module):
             feats = torch.stack([F.grid_sample(src_views[l], sample_grid[:, :, l:l + 1, :], align_corners=False).squeeze(-1)
                                  .permute(0, 2, 1) for l in range(feat_lvls)], dim=2)
         from .functions import linear as lin
-        value = lin(input_flatten, self.rayconv.weight, self.rayconv.bias)
+        if bf:
+            from .functions import linear_bf16
+            wc = self._wc
+            value = linear_bf16(input_flatten, self.rayconv.weight, self.rayconv.bias, wc, "train16/Wv", out_bf16=True)
+        else:
+            value = lin(input_flatten, self.rayconv.weight, self.rayconv.bias)
         if input_padding_mask is not None:
             value = value.masked_fill(input_padding_mask[..., None], float(0))
         value = value.view(n_views, -1, self.n_heads, self.d_model // self.n_heads)
         if xin is None:
             xin = feats + query.unsqueeze(2)
         n_off = self.sampling_offsets.out_features
-        oa = lin(xin, torch.cat([self.sampling_offsets.weight, self.attention_weights.weight], 0),      # one GEMM for both heads
-                 torch.cat([self.sampling_offsets.bias, self.attention_weights.bias], 0))
+        w_oa = torch.cat([self.sampling_offsets.weight, self.attention_weights.weight], 0)               # one GEMM for both heads
+        b_oa = torch.cat([self.sampling_offsets.bias, self.attention_weights.bias], 0)
+        if bf:
+            oa = linear_bf16(xin, w_oa, b_oa, wc, "train16/Woa", params=(self.sampling_offsets.weight, self.attention_weights.weight),
+                             build=lambda a, b: torch.cat([a, b], 0))
+        else:
+            oa = lin(xin, w_oa, b_oa)
         sampling_offsets = oa[..., :n_off].reshape(n_views, Len_q, self.n_heads, feat_lvls, self.n_points, 2)
         attention_weights = oa[..., n_off:].reshape(n_views, Len_q, self.n_heads, feat_lvls * self.n_points)
         attention_weights = F.softmax(attention_weights, -1).view(n_views, Len_q, self.n_heads, feat_lvls,
@@ -480,6 +496,8 @@ class ProjAttn(nn.Module):
         output = DeformFunction.apply(value.contiguous(), input_spatial_shapes.contiguous(),
                                       input_level_start_index.contiguous(), sampling_locations.contiguous(),
                                       attention_weights.contiguous(), self._step(n_views))
+        if bf:
+            return linear_bf16(output, self.output_proj.weight, self.output_proj.bias, wc, "train16/Wp")
         return lin(output, self.output_proj.weight, self.output_proj.bias)
 
 

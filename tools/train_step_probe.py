@@ -1,6 +1,6 @@
 """Time of one training step of the decoder at cfg-2 size: forward under autograd (torch geometry +
 ProjAttn with the HIP sampling forward / backward kernels) + backward to every parameter.  GPU only.
-python tools/train_step_probe.py [config] [steps]"""
+python tools/train_step_probe.py [config] [steps] [fp32|bf16]   (bf16: DQDecoder.set_training_dtype(torch.bfloat16))"""
 import os
 import sys
 import time
@@ -14,8 +14,13 @@ from mvgformer_amd.synthetic import build_case  # noqa: E402
 
 cfg = sys.argv[1] if len(sys.argv) > 1 else "cfg2"
 steps = int(sys.argv[2]) if len(sys.argv) > 2 else 5
+tdt = sys.argv[3] if len(sys.argv) > 3 else "fp32"
+if tdt not in ("fp32", "bf16"):
+    raise SystemExit("training dtype must be fp32 or bf16")
 case = build_case(cfg, seed=0)
 dec = build_decoder_for_case(case, "cuda", torch.float32)
+if tdt == "bf16":
+    dec.set_training_dtype(torch.bfloat16)
 g = case_to_device(case, "cuda")
 for p in dec.parameters():
     p.requires_grad_(True)
@@ -43,5 +48,5 @@ dt = (time.perf_counter() - t0) / steps
 # one multi-tensor launch instead of five per parameter: a profile of this script counts the steps' launches, not this check's
 grads = [p.grad for p in dec.parameters() if p.grad is not None]
 n_grad = int(torch.isfinite(torch.stack(torch._foreach_norm(grads))).sum())
-print("%s training step (fp32, forward + backward): %.1f ms; loss %.4f; %d / %d parameters with finite gradients; peak memory %.1f GB"
-      % (cfg, dt * 1e3, float(loss), n_grad, sum(1 for _ in dec.parameters()), torch.cuda.max_memory_allocated() / 2 ** 30))
+print("%s training step (%s, forward + backward): %.1f ms; loss %.4f; %d / %d parameters with finite gradients; peak memory %.1f GB"
+      % (cfg, tdt, dt * 1e3, float(loss), n_grad, sum(1 for _ in dec.parameters()), torch.cuda.max_memory_allocated() / 2 ** 30))
