@@ -375,6 +375,55 @@ int mvg_dlt_backward(const float* ud, const float* conf, const float* Pm, const 
  * eigenvector of A^T A in the forward, all pairs in the backward. */
 int mvg_sym4_eigh(const double* G, double* evals, double* evecs, long n, void* stream);
 
+/* ---- training criterion (csrc/criterion.hip) ------------------------------------------------------------------------------ */
+#define MVG_MATCH_KNN 0       /* the K nearest queries of every ground-truth person (matcher.py:232-262)          */
+#define MVG_MATCH_MULTIPLE 1  /* every query whose nearest person is closer than a threshold (matcher.py:201-230) */
+
+/* bytes of cost workspace mvg_knn_match needs (0 while the NQ x Gmax fp32 costs fit its 40 KB of LDS) */
+size_t mvg_knn_match_workspace(int B, int NQ, int Gmax);
+
+/* Ground-truth matcher of the training step (lib/models/matcher.py:80-262, match_coord_est 'abs', match_coord_gt 'norm') for the
+ * whole batch in ONE launch, one workgroup per batch element, nothing read back by the host.  poses (B, NQ*J, 3) fp32 absolute mm;
+ * joints_3d (B, Gmax, J, 3) fp32 absolute mm, taken through absolute -> norm -> absolute in fp32 as the reference does;
+ * num_person (B,) int32 (num_person_is64 = 0) or int64 (1), clamped to [0, Gmax]; space_size / space_center: 3 HOST floats.
+ * cost = 0.01 * L1 over the 3J coordinates.  method MVG_MATCH_KNN: the K smallest-cost queries of every person, pair slot g*K + k
+ * (person-major, ascending cost, ties to the lower query index), pair_count[b] = num_person[b] * K, Pmax >= Gmax*K;
+ * MVG_MATCH_MULTIPLE: every query whose nearest person (ties to the lower person) costs less than `value`, ascending query order
+ * (the reference's torch.where order), Pmax >= NQ.  Outputs: pair_query, pair_gt (B, Pmax) int32, -1 in unused slots; pair_count
+ * (B,) int32; matched (B, NQ) uint8 = the union of the matched queries (a query matched to two persons is in two pairs and once
+ * here), ready to be the decoder's triangulation filter.  MVG_E_BADARG for Gmax > 64, K > 16, K > NQ, J > 64, value <= 0, a
+ * too small Pmax or workspace. */
+int mvg_knn_match(const float* poses, const float* joints_3d, const void* num_person, int num_person_is64, const float* space_size,
+                  const float* space_center, int method, int K, float value, int B, int NQ, int Gmax, int J, int Pmax,
+                  void* workspace, size_t workspace_bytes, int* pair_query, int* pair_gt, int* pair_count, uint8_t* matched,
+                  void* stream);
+
+/* bytes of the (8-byte aligned) workspace of mvg_criterion: the projected ground truth and the per-(layer, batch) partial sums */
+size_t mvg_criterion_workspace(int L, int B, int Gmax, int V, int J);
+
+/* SetCriterion (lib/models/multi_view_pose_transformer.py:491-932 with losses labels / cardinality / joints,
+ * use_loss_pose_perprojection_2d, loss_joint_type l1, loss_pose_normalize false) for all L decoder layers of one step against
+ * ONE pair list (gt_match: every layer uses the match on the initial poses): value and gradients in three launches whatever L,
+ * B, Gmax are, fixed-order sums in fp64, no atomics, no host read-back.
+ *   logits (L,B,NQ,2), poses (L,B,NQ*J,3) mm, poses_2d (L,B,V,NQ*J,2) network-image px: fp32.
+ *   pair_query / pair_gt (B,Pmax), pair_count (B,): as written by mvg_knn_match (entries out of range are ignored).
+ *   joints_3d, joints_3d_vis (B,Gmax,J,3); joints_vis (V,B,Gmax,J,2); num_person (B,) int32 / int64.
+ *   num_samples: device fp32 scalar (the all-reduced clamp(sum(num_person) / world_size, 1)) or NULL = computed here from
+ *   num_person.  cams: packed records (V*B, MVG_CAM_STRIDE); the crop affine of record 0 (view 0, batch element 0) is applied to
+ *   every projected ground-truth point, without the clamp of mvg_project.  space_size / space_center: 3 HOST floats.
+ * table (L, 8) fp32: loss_ce, class_error, class_recall, class_precision, cardinality_error, loss_pose_perjoint,
+ * loss_pose_perprojection_2d (zero if it exceeded 1e5), keep_2d (0 in that case, else 1: the factor of its gradient).
+ * grad_logits / grad_poses / grad_poses_2d: d loss_ce / d logits, d loss_pose_perjoint / d poses and d (unguarded 2D loss) /
+ * d poses_2d, shaped like the inputs and written densely (zeros for unmatched queries; a query in several pairs gets the sum of
+ * their terms in pair order).  The 2D rows keep the reference's order: predictions pair-major, visibility weights view-major
+ * (loss.py:260-272).  Limits: NQ <= 4096, Pmax <= 4096, B <= 256, Gmax <= 64, J <= 64. */
+int mvg_criterion(const float* logits, const float* poses, const float* poses_2d, const int* pair_query, const int* pair_gt,
+                  const int* pair_count, const float* joints_3d, const float* joints_3d_vis, const float* joints_vis,
+                  const void* num_person, int num_person_is64, const float* num_samples, const float* cams, const float* space_size,
+                  const float* space_center, float pred_conf_threshold, float focal_alpha, float focal_gamma, int L, int B, int NQ,
+                  int J, int V, int Gmax, int Pmax, void* workspace, size_t workspace_bytes, float* table, float* grad_logits,
+                  float* grad_poses, float* grad_poses_2d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

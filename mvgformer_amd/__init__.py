@@ -6,10 +6,12 @@ Host-side mirror of the reference's operator interface (same names / signatures)
   ProjAttn        : mvgformer_amd.projattn.ProjAttn            (alias MSDeformAttn)
   DQDecoderLayer  : mvgformer_amd.decoder.DQDecoderLayer       (alias MultiViewDecoderLayer)
   DQDecoder       : mvgformer_amd.decoder.DQDecoder
+  Criterion       : mvgformer_amd.criterion.KNNMatcher / SetCriterion / criterion_all_layers / total_loss
 All compute goes through libmvgformer_hip.so (include/mvg_decoder.h); there is no CPU path.
 """
 from .decoder import MLP, DQDecoder, DQDecoderLayer, MultiViewDecoder, MultiViewDecoderLayer, offset_net  # noqa: F401
-from .functions import DeformFunction  # noqa: F401
+from .criterion import KNNMatcher, SetCriterion, criterion_all_layers, total_loss  # noqa: F401
+from .functions import CriterionFunction, DeformFunction  # noqa: F401
 from .projattn import MSDeformAttn, ProjAttn  # noqa: F401
 
 __version__ = "0.1.0"

@@ -61,6 +61,10 @@ SIGNATURES = {
     "mvg_triangulate_project": [_vp] * 8 + [_i] * 4 + [_vp, _i] + [_vp] * 4,
     "mvg_uncrop_undistort_jac": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp],
     "mvg_sym4_eigh": [_vp] * 3 + [C.c_long, _vp],
+    "mvg_knn_match_workspace": [_i] * 3,
+    "mvg_knn_match": [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _f] + [_i] * 5 + [_vp, C.c_size_t] + [_vp] * 5,
+    "mvg_criterion_workspace": [_i] * 5,
+    "mvg_criterion": [_vp] * 10 + [_i] + [_vp] * 4 + [_f] * 3 + [_i] * 7 + [_vp, C.c_size_t] + [_vp] * 5,
 }
 
 _lib = None
@@ -88,6 +92,8 @@ def load():
     lib.mvg_version.restype = C.c_char_p
     lib.mvg_bin_pairs_workspace.restype = C.c_size_t
     lib.mvg_msda_backward_det_workspace.restype = C.c_size_t
+    lib.mvg_knn_match_workspace.restype = C.c_size_t
+    lib.mvg_criterion_workspace.restype = C.c_size_t
     lib.mvg_version.argtypes = []
     # every knob change goes through this wrapper, so that host-side caches that depend on a knob (DQDecoderLayer's rows of
     # all-masked tiles: computed by the GEMM form that is active) can key on its value: TUNING[key] = last value set

@@ -7,7 +7,10 @@ without the reference's CUDA-only constructor (lib/models/dq_transformer.py:120-
   inverse_sigmoid               lib/models/util/misc.py:608-612
   decoder_outputs_to_dict       dq_transformer.py:569-603 (incl. the Shelf/Campus joint permutation)
   pack_predictions              lib/core/function.py:386-396 ([x, y, z, (score > thr) - 1, score])
-  DecoderHead                   embeddings + decoder behind one forward(src_views, meta, threshold)
+  DecoderHead                   embeddings + decoder behind one forward(src_views, meta, threshold); forward_train adds the
+                                ground-truth match in front of the decoder and the fused criterion behind it
+                                (dq_transformer.py:478-731 for gt_match: True)
+  total_loss                    lib/core/function.py:127-128
 """
 from __future__ import annotations
 
@@ -16,6 +19,7 @@ import math
 import torch
 from torch import nn
 
+from .criterion import criterion_all_layers, total_loss  # noqa: F401  (total_loss: part of this module's interface)
 from .synthetic import TPOSE_MM
 
 
@@ -77,7 +81,7 @@ def decoder_outputs_to_dict(hs, inter_references, inter_references_2d, inter_ref
         coords2d.append({"outputs_coord_2d": c2})
         coords2dp.append({"outputs_coord_2d_proj": cp})
     return {"pred_logits": logits[-1], "pred_poses": coords[-1], "pred_poses_2d": coords2d[-1],
-            "pred_poses_2d_proj": coords2dp[-1], "all_logits": logits, "all_poses": coords}
+            "pred_poses_2d_proj": coords2dp[-1], "all_logits": logits, "all_poses": coords, "all_poses_2d": coords2d}
 
 
 def pack_predictions(out, threshold):
@@ -107,6 +111,41 @@ class DecoderHead(nn.Module):
         self.instance_embedding = nn.Embedding(num_instance, d_model * 2)
         self.space_size, self.space_center = list(space_size), list(space_center)
         self.convert_joint_format_indices = convert_joint_format_indices
+        self.criterion, self.decay_method = None, "none"
+
+    def set_criterion(self, criterion, decay_method="none"):
+        """the criterion.SetCriterion (with its matcher) forward_train uses, and how the layers' losses are summed"""
+        self.criterion, self.decay_method = criterion, decay_method
+        return self
+
+    def forward_train(self, src_views, meta, spatial_shapes=None, level_start_index=None, threshold=0.1):
+        """One training forward for gt_match: True (dq_transformer.py:478-731): initial reference points, ground-truth match on
+        them (one launch), the decoder under autograd with the matched mask as its triangulation filter, the out dict, and the
+        losses of all layers from the fused criterion.  meta[0] holds joints_3d, joints_3d_vis, num_person and every meta[v]
+        its joints_vis, on the device.  Returns (out, loss_dict); total_loss(loss_dict, weight_dict).backward() is the step."""
+        from .decoder import DecoderContext
+        if self.criterion is None:
+            raise RuntimeError("DecoderHead.forward_train: no criterion (set_criterion / factory.build_training_head)")
+        if self.convert_joint_format_indices is not None:
+            raise NotImplementedError("forward_train with convert_joint_format_indices (Shelf / Campus joint format)")
+        dev = src_views[0].device
+        V = len(meta)
+        batch = src_views[0].shape[0] // V
+        if spatial_shapes is None:
+            spatial_shapes, level_start_index = level_tables(src_views)
+        query_pos, tgt = person_joint_queries(self.joint_embedding.weight, self.instance_embedding.weight, batch)
+        ref = sample_space_reference_points(self.num_instance, self.space_size, self.space_center, batch, dev,
+                                            t_pose=self.t_pose)
+        pairs = self.criterion.matcher.match(ref, meta)
+        layer0 = self.decoder.layers[0]
+        ctx = DecoderContext.prepare(spatial_shapes, level_start_index, meta, layer0.img_size, layer0.compute_dtype, batch, dev)
+        hs, refs, refs2d, projs2d, classes = self.decoder(
+            tgt.contiguous(), ref, src_views, meta, spatial_shapes, level_start_index, None,
+            query_pos=query_pos.contiguous(), indices=pairs[3], threshold=threshold, context=ctx)
+        out = decoder_outputs_to_dict(hs, refs, refs2d, projs2d, classes, self.num_instance, self.num_joints, None)
+        loss_dict, _ = criterion_all_layers(self.criterion, torch.stack(out["all_logits"]), refs, refs2d, meta, ref,
+                                            self.decay_method, cams=ctx.cams, pairs=pairs)
+        return out, loss_dict
 
     @torch.no_grad()
     def forward(self, src_views, meta, spatial_shapes=None, level_start_index=None, threshold=0.1):

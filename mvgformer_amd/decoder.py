@@ -68,6 +68,15 @@ def _get_activation_fn(activation):
     raise RuntimeError(F"activation should be relu/gelu, not {activation}.")
 
 
+def _mask_indices(indices, B, NQ, device):
+    """`indices` given as the matched-query mask (B, NQ) uint8 / bool on the device -> a fresh uint8 mask (the layer may force query
+    (0, 0) into it); a list of per-element index tensors stays the other accepted form."""
+    if indices.dtype not in (torch.uint8, torch.bool) or tuple(indices.shape) != (B, NQ) or indices.device != torch.device(device):
+        raise RuntimeError("indices as a tensor: (B, NQ) = (%d, %d) uint8 / bool mask on %s expected, got %s %s on %s"
+                           % (B, NQ, device, tuple(indices.shape), indices.dtype, indices.device))
+    return indices.to(torch.uint8).clone()
+
+
 class DecoderContext:
     """Per-forward, layer-independent state: level table + packed cameras (host side, built from
     ``meta``) and the packed channels-last pyramid (device side, built from ``src_views``).
@@ -501,6 +510,8 @@ class DQDecoderLayer(MvPDecoderLayer):
         prob = lin(tgt_update, self.class_embed.weight, self.class_embed.bias).view(B, NQ, J, 2).sigmoid().mean(2)
         if not self.filter_query or self.query_filter_method == "all":
             valid = torch.ones((B, NQ), dtype=torch.bool, device=dev)
+        elif torch.is_tensor(indices):      # the matcher's (B, NQ) mask (criterion.KNNMatcher.match): the filter as it is
+            valid = _mask_indices(indices, B, NQ, dev).bool()
         elif indices is not None:
             valid = torch.zeros((B, NQ), dtype=torch.bool, device=dev)
             for b, q in enumerate(indices):
@@ -604,6 +615,8 @@ class DQDecoderLayer(MvPDecoderLayer):
         forced = None
         if not self.filter_query or self.query_filter_method == "all":
             forced = torch.ones((B, NQ), dtype=torch.uint8, device=tgt.device)
+        elif torch.is_tensor(indices):
+            forced = _mask_indices(indices, B, NQ, tgt.device)
         elif indices is not None:
             forced = torch.zeros((B, NQ), dtype=torch.uint8, device=tgt.device)
             for b, q in enumerate(indices):

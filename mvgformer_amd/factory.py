@@ -18,6 +18,12 @@ _DECODER_DEFAULTS = dict(pose_embed_layer=3, d_model=256, dim_feedforward=1024, 
                          init_self_attention=False, open_forward_ffn=True, query_filter_method="threshold",
                          bayesian_update=False, triangulation_method="linalg", filter_query=True,
                          share_layer_weights=False, inference_conf_thr=[0.1])
+# defaults of lib/core/config.py:244-257, 306-318 for the keys the training criterion reads
+_CRITERION_DEFAULTS = dict(match_coord_est="abs", match_coord_gt="norm", match_method="KNN", match_method_value=5,
+                           loss_weight_loss_ce=2.0, loss_pose_perjoint=5.0, loss_pose_perprojection_2d=5.0, loss_weight_init=0.0,
+                           pred_conf_threshold=0.5, decay_method="none", loss_joint_type="l1", loss_pose_normalize=False,
+                           use_loss_pose_perbone=False, use_loss_pose_perprojection=False, use_loss_pose_perprojection_2d=True,
+                           use_ce_match=False)
 
 
 def load_yaml_config(path):
@@ -49,6 +55,39 @@ def build_decoder_from_cfg(cfg):
                            triangulation_method=d.triangulation_method, filter_query=d.filter_query,
                            num_joints=d.num_keypoints)
     return DQDecoder(cfg, layer, d.num_decoder_layers, d.return_intermediate_dec)
+
+
+def build_weight_dict(cfg):
+    """multi_view_pose_transformer.py:224-230"""
+    d = cfg.DECODER
+    return {"loss_ce": d.loss_weight_loss_ce, "loss_pose_perjoint": d.loss_pose_perjoint,
+            "loss_pose_perprojection_2d": d.loss_pose_perprojection_2d, "loss_init": d.loss_weight_init}
+
+
+def build_criterion_from_cfg(cfg):
+    """matcher + criterion + weight_dict from the DECODER keys, as multi_view_pose_transformer.py:217-247 builds them
+    (cost_class 2, cost_pose 5, focal alpha 0.25, losses joints / labels / cardinality).  Keys a hand-made cfg lacks take the
+    defaults of lib/core/config.py.  Returns (criterion, weight_dict, decay_method)."""
+    from .criterion import KNNMatcher, SetCriterion
+    d = SimpleNamespace(**{**_CRITERION_DEFAULTS, **vars(cfg.DECODER)})
+    full = SimpleNamespace(DECODER=d, NETWORK=cfg.NETWORK, MULTI_PERSON=cfg.MULTI_PERSON)
+    matcher = KNNMatcher(d.match_coord_est, d.match_coord_gt, cost_class=2., cost_pose=5., method=d.match_method,
+                         method_value=d.match_method_value)
+    weight_dict = build_weight_dict(full)
+    criterion = SetCriterion(2, matcher, weight_dict, ["joints", "labels", "cardinality"], full, focal_alpha=0.25)
+    return criterion, weight_dict, d.decay_method
+
+
+def build_training_head(cfg, decoder=None, t_pose=None):
+    """caller.DecoderHead around the cfg's decoder with the cfg's criterion set: forward_train is ready.  Returns (head, weight_dict)."""
+    from .caller import DecoderHead
+    d = cfg.DECODER
+    decoder = build_decoder_from_cfg(cfg) if decoder is None else decoder
+    head = DecoderHead(decoder, d.num_instance, d.num_keypoints, d.d_model, cfg.MULTI_PERSON.SPACE_SIZE, cfg.MULTI_PERSON.SPACE_CENTER,
+                       t_pose=t_pose)
+    criterion, weight_dict, decay = build_criterion_from_cfg(cfg)
+    head.set_criterion(criterion, decay)
+    return head, weight_dict
 
 
 def build_decoder_for_case(case, device="cuda", dtype=torch.float32):

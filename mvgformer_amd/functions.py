@@ -202,3 +202,31 @@ class RefGatherAdd(Function):
     @once_differentiable
     def backward(ctx, g):
         return g.reshape(ctx.shape).sum(2), None, None, None
+
+
+class CriterionFunction(Function):
+    """(L, 8) loss table of ops.criterion (columns ops.CRITERION_COLUMNS) for all decoder layers of one step.  The kernels
+    produce the gradients of loss_ce, loss_pose_perjoint and loss_pose_perprojection_2d in the forward pass; backward scales them
+    per layer by the table's grad_output (the 2D term also by keep_2d: a guarded layer gives a zero gradient).  The metric columns
+    carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, logits, poses, poses_2d, pair_query, pair_gt, pair_count, joints_3d, joints_3d_vis, joints_vis, num_person,
+                cams, space_size, space_center, pred_conf_threshold, num_samples, focal_alpha, focal_gamma):
+        table, gl, gp, gp2 = ops.criterion(logits, poses, poses_2d, pair_query, pair_gt, pair_count, joints_3d, joints_3d_vis,
+                                           joints_vis, num_person, cams, space_size, space_center, pred_conf_threshold,
+                                           num_samples, focal_alpha, focal_gamma)
+        ctx.save_for_backward(gl, gp, gp2, table)
+        return table
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_table):
+        gl, gp, gp2, table = ctx.saved_tensors
+        g = grad_table.to(torch.float32)
+        keep = table[:, 7] > 0
+        zero = torch.zeros_like(gp2)
+        g_logits = gl * g[:, 0].view(-1, 1, 1, 1)
+        g_poses = gp * g[:, 5].view(-1, 1, 1, 1)
+        g_2d = torch.where(keep.view(-1, 1, 1, 1, 1), gp2 * g[:, 6].view(-1, 1, 1, 1, 1), zero)
+        return (g_logits, g_poses, g_2d) + (None,) * 14

@@ -888,3 +888,99 @@ def sym4_eigh(G):
     L.check(L.load().mvg_sym4_eigh(L.ptr(Gc), L.ptr(w), L.ptr(V), n, L.stream_ptr()), "mvg_sym4_eigh")
     return w, V
 
+
+# ---- training criterion (csrc/criterion.hip) ---------------------------------------------------------------------------------
+MATCH_METHODS = {"KNN": 0, "multiple": 1}
+CRITERION_COLUMNS = ("loss_ce", "class_error", "class_recall", "class_precision", "cardinality_error", "loss_pose_perjoint",
+                     "loss_pose_perprojection_2d", "keep_2d")
+
+
+def _host3(x):
+    return (C.c_float * 3)(*(float(v) for v in x))
+
+
+def _count_tensor(num_person, B):
+    if num_person.dtype not in (torch.int32, torch.int64) or num_person.numel() != B:
+        raise RuntimeError("num_person: (B,) int32 / int64 tensor expected")
+    return num_person.contiguous(), int(num_person.dtype == torch.int64)
+
+
+def knn_match(poses, joints_3d, num_person, space_size, space_center, method="KNN", value=5):
+    """poses (B, NQ*J, 3) abs mm, joints_3d (B, Gmax, J, 3) abs mm, num_person (B,) -> pair_query, pair_gt (B, Pmax) int32 (-1 in
+    unused slots), pair_count (B,) int32, matched (B, NQ) uint8 (mvg_knn_match: one launch, nothing read back).  method 'KNN'
+    (value = K, Pmax = Gmax*K) or 'multiple' (value = cost threshold, Pmax = NQ)."""
+    if method in ("hungarian", "hungarian-dis"):
+        raise NotImplementedError("match method %r: the Hungarian assignment is not built (no shipped YAML uses it)" % method)
+    if method not in MATCH_METHODS:
+        raise ValueError("unknown match method %r" % (method,))
+    L.require_cuda(poses, joints_3d, num_person)
+    if poses.dtype != torch.float32 or joints_3d.dtype != torch.float32 or joints_3d.dim() != 4 or joints_3d.shape[-1] != 3 \
+            or poses.dim() != 3 or poses.shape[-1] != 3 or poses.shape[0] != joints_3d.shape[0]:
+        raise RuntimeError("mvg_knn_match: poses (B, NQ*J, 3) / joints_3d (B, Gmax, J, 3) float32 expected")
+    B, Gmax, J = joints_3d.shape[:3]
+    if poses.shape[1] % J:
+        raise RuntimeError("mvg_knn_match: poses rows (%d) are not a multiple of J = %d" % (poses.shape[1], J))
+    NQ = poses.shape[1] // J
+    num_person, is64 = _count_tensor(num_person, B)
+    poses, joints_3d = poses.detach().contiguous(), joints_3d.contiguous()
+    knn = method == "KNN"
+    K = int(value) if knn else 0
+    Pmax = Gmax * max(K, 1) if knn else NQ
+    lib = L.load()
+    dev = poses.device
+    pq = torch.empty((B, Pmax), dtype=torch.int32, device=dev)
+    pg = torch.empty((B, Pmax), dtype=torch.int32, device=dev)
+    pc = torch.empty((B,), dtype=torch.int32, device=dev)
+    matched = torch.empty((B, NQ), dtype=torch.uint8, device=dev)
+    nbytes = lib.mvg_knn_match_workspace(B, NQ, Gmax)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev) if nbytes else None
+    with _timed("knn_match"):
+        L.check(lib.mvg_knn_match(L.ptr(poses), L.ptr(joints_3d), L.ptr(num_person), is64, _host3(space_size), _host3(space_center),
+                                  MATCH_METHODS[method], K, float(value), B, NQ, Gmax, J, Pmax, L.ptr(ws), nbytes, L.ptr(pq),
+                                  L.ptr(pg), L.ptr(pc), L.ptr(matched), L.stream_ptr()), "mvg_knn_match")
+    return pq, pg, pc, matched
+
+
+def criterion(logits, poses, poses_2d, pair_query, pair_gt, pair_count, joints_3d, joints_3d_vis, joints_vis, num_person, cams,
+              space_size, space_center, pred_conf_threshold, num_samples=None, focal_alpha=0.25, focal_gamma=2.0):
+    """All layers' losses, metrics and gradients in three launches (mvg_criterion).  logits (L,B,NQ,2), poses (L,B,NQ*J,3),
+    poses_2d (L,B,V,NQ*J,2) fp32; the pair list of knn_match; joints_3d / joints_3d_vis (B,Gmax,J,3), joints_vis (V,B,Gmax,J,2)
+    fp32; cams = pack_cameras(...).  -> table (L, 8) fp32 in the order of CRITERION_COLUMNS, grad_logits, grad_poses,
+    grad_poses_2d (shaped like the inputs; the 2D gradient is the unguarded one, to be multiplied by keep_2d)."""
+    tensors = (logits, poses, poses_2d, pair_query, pair_gt, pair_count, joints_3d, joints_3d_vis, joints_vis, num_person, cams)
+    L.require_cuda(*tensors, num_samples)
+    if any(t.dtype != torch.float32 for t in (logits, poses, poses_2d, joints_3d, joints_3d_vis, joints_vis, cams)):
+        raise RuntimeError("mvg_criterion: float32 tensors expected")
+    if any(t.dtype != torch.int32 for t in (pair_query, pair_gt, pair_count)):
+        raise RuntimeError("mvg_criterion: int32 pair list expected")
+    if logits.dim() != 4 or logits.shape[-1] != 2 or poses.dim() != 4 or poses_2d.dim() != 5 or joints_3d.dim() != 4:
+        raise RuntimeError("mvg_criterion: logits (L,B,NQ,2) / poses (L,B,NQ*J,3) / poses_2d (L,B,V,NQ*J,2) expected")
+    Ln, B, NQ = logits.shape[:3]
+    Gmax, J = joints_3d.shape[1:3]
+    V = poses_2d.shape[2]
+    Pmax = pair_query.shape[-1]
+    if (tuple(poses.shape) != (Ln, B, NQ * J, 3) or tuple(poses_2d.shape) != (Ln, B, V, NQ * J, 2)
+            or tuple(joints_3d.shape) != (B, Gmax, J, 3) or tuple(joints_3d_vis.shape) != (B, Gmax, J, 3)
+            or tuple(joints_vis.shape) != (V, B, Gmax, J, 2) or tuple(pair_query.shape) != (B, Pmax)
+            or tuple(pair_gt.shape) != (B, Pmax) or pair_count.numel() != B or tuple(cams.shape) != (V * B, L.CAM_STRIDE)):
+        raise RuntimeError("mvg_criterion: inconsistent shapes")
+    if num_samples is not None and (num_samples.dtype != torch.float32 or num_samples.numel() != 1):
+        raise RuntimeError("mvg_criterion: num_samples must be a float32 device scalar")
+    num_person, is64 = _count_tensor(num_person, B)
+    logits, poses, poses_2d = logits.detach().contiguous(), poses.detach().contiguous(), poses_2d.detach().contiguous()
+    pair_query, pair_gt, pair_count = pair_query.contiguous(), pair_gt.contiguous(), pair_count.contiguous()
+    joints_3d, joints_3d_vis, joints_vis, cams = (t.contiguous() for t in (joints_3d, joints_3d_vis, joints_vis, cams))
+    lib = L.load()
+    dev = logits.device
+    nbytes = lib.mvg_criterion_workspace(Ln, B, Gmax, V, J)
+    ws = torch.empty(((nbytes + 7) // 8,), dtype=torch.float64, device=dev)
+    table = torch.empty((Ln, len(CRITERION_COLUMNS)), dtype=torch.float32, device=dev)
+    gl, gp, gp2 = torch.empty_like(logits), torch.empty_like(poses), torch.empty_like(poses_2d)
+    with _timed("criterion"):
+        L.check(lib.mvg_criterion(L.ptr(logits), L.ptr(poses), L.ptr(poses_2d), L.ptr(pair_query), L.ptr(pair_gt), L.ptr(pair_count),
+                                  L.ptr(joints_3d), L.ptr(joints_3d_vis), L.ptr(joints_vis), L.ptr(num_person), is64,
+                                  L.ptr(num_samples), L.ptr(cams), _host3(space_size), _host3(space_center),
+                                  float(pred_conf_threshold), float(focal_alpha), float(focal_gamma), Ln, B, NQ, J, V, Gmax, Pmax,
+                                  L.ptr(ws), nbytes, L.ptr(table), L.ptr(gl), L.ptr(gp), L.ptr(gp2), L.stream_ptr()),
+                "mvg_criterion")
+    return table, gl, gp, gp2

@@ -336,3 +336,27 @@ def build_case(name, B=1, seed=0, NQ=None, layers=None, V=None, feat_dtype=torch
                            reference_points=ref, src_views=src, spatial_shapes=spatial_shapes,
                            level_start_index=level_start, weights=weights,
                            space_size=c["space_size"], space_center=c["space_center"])
+
+
+def add_ground_truth(case, num_person, Gmax=10, seed=0):
+    """Synthetic training targets in the loader's schema (JointsDataset.py:197-220), added to ``case.meta`` in place: persons
+    inside the space, their centres on a ring 1.5 .. 3 m apart, T-pose joints with a little noise.  meta[0] gets joints_3d
+    (B, Gmax, J, 3) mm, joints_3d_vis (B, Gmax, J, 3) and num_person (B,) int64; every view its joints_vis (B, Gmax, J, 2)."""
+    rs = np.random.RandomState(seed + 4211)
+    B, J = case.B, TPOSE_MM.shape[0]
+    num_person = [num_person] * B if np.isscalar(num_person) else list(num_person)
+    size, cen = np.asarray(case.space_size, np.float64), np.asarray(case.space_center, np.float64)
+    gt = np.zeros((B, Gmax, J, 3), np.float32)
+    for b in range(B):
+        for g in range(Gmax):
+            ang = 2.0 * math.pi * (g + 0.3 * rs.rand()) / Gmax
+            rad = 0.3 * min(size[0], size[1]) * (0.6 + 0.4 * rs.rand())
+            ctr = np.array([cen[0] + rad * math.cos(ang), cen[1] + rad * math.sin(ang), cen[2]])
+            gt[b, g] = ctr + TPOSE_MM + rs.standard_normal((J, 3)) * 40.0
+    dev = case.meta[0]["center"].device
+    case.meta[0]["joints_3d"] = torch.from_numpy(gt).to(dev)
+    case.meta[0]["joints_3d_vis"] = torch.ones((B, Gmax, J, 3), dtype=torch.float32, device=dev)
+    case.meta[0]["num_person"] = torch.tensor(num_person, dtype=torch.int64, device=dev)
+    for m in case.meta:
+        m["joints_vis"] = torch.from_numpy(np.repeat((rs.rand(B, Gmax, J, 1) > 0.15).astype(np.float32), 2, -1)).to(dev)
+    return case

@@ -1,6 +1,8 @@
 """Time of one training step of the decoder at cfg-2 size: forward under autograd (torch geometry +
 ProjAttn with the HIP sampling forward / backward kernels) + backward to every parameter.  GPU only.
-python tools/train_step_probe.py [config] [steps] [fp32|bf16]   (bf16: DQDecoder.set_training_dtype(torch.bfloat16))"""
+python tools/train_step_probe.py [config] [steps] [fp32|bf16] [--criterion]   (bf16: DQDecoder.set_training_dtype(torch.bfloat16))
+--criterion: the real step -- DecoderHead.forward_train (ground-truth match, decoder with the matched mask, fused criterion) on
+synthetic ground truth (5 persons, K = 5) and total_loss(...).backward() -- instead of the made-up loss of the default run."""
 import os
 import sys
 import time
@@ -12,9 +14,11 @@ import torch  # noqa: E402
 from mvgformer_amd.factory import build_decoder_for_case, case_to_device  # noqa: E402
 from mvgformer_amd.synthetic import build_case  # noqa: E402
 
-cfg = sys.argv[1] if len(sys.argv) > 1 else "cfg2"
-steps = int(sys.argv[2]) if len(sys.argv) > 2 else 5
-tdt = sys.argv[3] if len(sys.argv) > 3 else "fp32"
+with_criterion = "--criterion" in sys.argv
+argv = [a for a in sys.argv if a != "--criterion"]
+cfg = argv[1] if len(argv) > 1 else "cfg2"
+steps = int(argv[2]) if len(argv) > 2 else 5
+tdt = argv[3] if len(argv) > 3 else "fp32"
 if tdt not in ("fp32", "bf16"):
     raise SystemExit("training dtype must be fp32 or bf16")
 case = build_case(cfg, seed=0)
@@ -25,11 +29,28 @@ g = case_to_device(case, "cuda")
 for p in dec.parameters():
     p.requires_grad_(True)
 dec.train()
+head = weight_dict = None
+if with_criterion:
+    from types import SimpleNamespace as NS
+    from mvgformer_amd.caller import DecoderHead, total_loss
+    from mvgformer_amd.factory import build_criterion_from_cfg
+    from mvgformer_amd.synthetic import add_ground_truth
+    add_ground_truth(g, 5, Gmax=10, seed=0)
+    ccfg = NS(DECODER=NS(match_method="KNN", match_method_value=5), NETWORK=NS(IMAGE_SIZE=list(case.img_size)),
+              MULTI_PERSON=NS(SPACE_SIZE=list(case.space_size), SPACE_CENTER=list(case.space_center)))
+    criterion, weight_dict, decay = build_criterion_from_cfg(ccfg)
+    head = DecoderHead(dec, case.NQ, 15, 256, case.space_size, case.space_center).to("cuda").set_criterion(criterion, decay)
+    head.train()
 
 
 def step():
     for p in dec.parameters():
         p.grad = None
+    if head is not None:
+        _, loss_dict = head.forward_train(g.src_views, g.meta, g.spatial_shapes, g.level_start_index, threshold=0.1)
+        loss = total_loss(loss_dict, weight_dict)
+        loss.backward()
+        return loss
     out = dec(g.tgt, g.reference_points, g.src_views, g.meta, g.spatial_shapes, g.level_start_index, None,
               query_pos=g.query_pos, threshold=0.1)
     loss = out[0].float().pow(2).mean() + 1e-6 * out[1].float().pow(2).mean() + sum(c.float().sum() for c in out[4]) * 1e-3
@@ -48,5 +69,5 @@ dt = (time.perf_counter() - t0) / steps
 # one multi-tensor launch instead of five per parameter: a profile of this script counts the steps' launches, not this check's
 grads = [p.grad for p in dec.parameters() if p.grad is not None]
 n_grad = int(torch.isfinite(torch.stack(torch._foreach_norm(grads))).sum())
-print("%s training step (%s, forward + backward): %.1f ms; loss %.4f; %d / %d parameters with finite gradients; peak memory %.1f GB"
-      % (cfg, tdt, dt * 1e3, float(loss), n_grad, sum(1 for _ in dec.parameters()), torch.cuda.max_memory_allocated() / 2 ** 30))
+print("%s training step (%s%s, forward + backward): %.1f ms; loss %.4f; %d / %d parameters with finite gradients; peak memory %.1f GB"
+      % (cfg, tdt, ", match + criterion" if with_criterion else "", dt * 1e3, float(loss), n_grad, sum(1 for _ in dec.parameters()), torch.cuda.max_memory_allocated() / 2 ** 30))
