@@ -424,6 +424,39 @@ int mvg_criterion(const float* logits, const float* poses, const float* poses_2d
                   int J, int V, int Gmax, int Pmax, void* workspace, size_t workspace_bytes, float* table, float* grad_logits,
                   float* grad_poses, float* grad_poses_2d, void* stream);
 
+/* ---- optimizer step (csrc/optim.hip) -------------------------------------------------------------------------------------- */
+#define MVG_OPTIM_CHUNK 4096          /* elements of one tensor that one workgroup handles                                  */
+#define MVG_OPTIM_MAX_GROUPS 64
+#define MVG_OPTIM_TENSOR_WORDS 6      /* 8-byte words per tensor record                                                      */
+#define MVG_OPTIM_GROUP_WORDS 6       /* doubles per group record                                                            */
+#define MVG_OPTIM_STATE_HEADER 64     /* bytes of the state block in front of the per-group results                          */
+#define MVG_OPTIM_STATE_PER_GROUP 16
+
+/* bytes of the (8-byte aligned) workspace of mvg_optim_step: one fp64 partial sum per chunk */
+size_t mvg_optim_workspace(int n_chunks);
+
+/* One optimizer step over every parameter tensor of a model: clip_grad_norm_(max_norm) followed by Adam / AdamW
+ * (lib/core/function.py:167-178), in at most three launches, without memset, copy or atomics, nothing read back.  Unlike the
+ * other entry points this one updates memory it is handed: p, exp_avg, exp_avg_sq, grad and the state block.  All tables are in
+ * DEVICE memory, 8-byte aligned:
+ *   tensor_table  n_tensors records of 6 x 8 bytes: pointers p, grad, exp_avg, exp_avg_sq (fp32, n elements each), int64 n,
+ *                 int64 group.  Pointers aligned to 16 bytes take the vector path, others the scalar one.
+ *   chunk_table   n_chunks records {int32 tensor, int32 index}: elements [index * MVG_OPTIM_CHUNK, min(n, (index + 1) *
+ *                 MVG_OPTIM_CHUNK)) of that tensor; every element of every tensor in exactly one chunk (an empty tensor in none).
+ *   group_table   n_groups (1 .. MVG_OPTIM_MAX_GROUPS) records of 6 doubles: lr, beta1, beta2, eps, weight_decay, decoupled
+ *                 (0: Adam, the decay is added to the gradient; 1: AdamW, p *= 1 - lr * weight_decay).
+ *   state         MVG_OPTIM_STATE_HEADER + n_groups * MVG_OPTIM_STATE_PER_GROUP bytes, zeroed once by the caller: int64 step
+ *                 count at byte 0 (the only field that persists), fp64 total norm at 8, fp32 clip coefficient at 16, int32 skip
+ *                 at 20, fp32 loss at 24, then per group fp32 {lr / (1 - beta1^t), sqrt(1 - beta2^t), 1 - lr * weight_decay, 0}.
+ * loss: device fp32 scalar or NULL; with it the step is skipped unless loss > 0 (a NaN skips): nothing is written to p, exp_avg,
+ * exp_avg_sq and the count stays.  max_norm <= 0: no clipping.  The gradient is left multiplied by the clip coefficient, or
+ * zeroed if zero_grad (also on a skipped step).  norm_out: device fp32 scalar or NULL, the total norm before clipping.  Sums are
+ * fp64 in a fixed order (a function of the tables alone); the update is fp32 in torch.optim.Adam's order of operations.
+ * MVG_E_BADARG for bad counts, unaligned tables, a short state block or workspace. */
+int mvg_optim_step(const void* tensor_table, int n_tensors, const void* chunk_table, int n_chunks, const void* group_table,
+                   int n_groups, void* state, size_t state_bytes, void* workspace, size_t workspace_bytes, const float* loss,
+                   float max_norm, int zero_grad, float* norm_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

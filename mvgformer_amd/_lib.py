@@ -65,6 +65,8 @@ SIGNATURES = {
     "mvg_knn_match": [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _f] + [_i] * 5 + [_vp, C.c_size_t] + [_vp] * 5,
     "mvg_criterion_workspace": [_i] * 5,
     "mvg_criterion": [_vp] * 10 + [_i] + [_vp] * 4 + [_f] * 3 + [_i] * 7 + [_vp, C.c_size_t] + [_vp] * 5,
+    "mvg_optim_workspace": [_i],
+    "mvg_optim_step": [_vp, _i, _vp, _i, _vp, _i, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _f, _i, _vp, _vp],
 }
 
 _lib = None
@@ -94,6 +96,7 @@ def load():
     lib.mvg_msda_backward_det_workspace.restype = C.c_size_t
     lib.mvg_knn_match_workspace.restype = C.c_size_t
     lib.mvg_criterion_workspace.restype = C.c_size_t
+    lib.mvg_optim_workspace.restype = C.c_size_t
     lib.mvg_version.argtypes = []
     # every knob change goes through this wrapper, so that host-side caches that depend on a knob (DQDecoderLayer's rows of
     # all-masked tiles: computed by the GEMM form that is active) can key on its value: TUNING[key] = last value set

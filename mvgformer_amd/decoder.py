@@ -773,7 +773,8 @@ class DQDecoder(MvPDecoder):
         new = cls.__new__(cls)
         memo[id(self)] = new
         for k, v in self.__dict__.items():
-            new.__dict__[k] = copy.deepcopy(v, memo)
+            # the side stream of an earlier GPU forward is run-time state (and not copyable): the copy forks its own
+            new.__dict__[k] = None if k == "_side_stream" else copy.deepcopy(v, memo)
         new._share_f32_pool()           # the copy's layers share ONE fresh pool again, not one each
         return new
 

@@ -24,6 +24,9 @@ _CRITERION_DEFAULTS = dict(match_coord_est="abs", match_coord_gt="norm", match_m
                            pred_conf_threshold=0.5, decay_method="none", loss_joint_type="l1", loss_pose_normalize=False,
                            use_loss_pose_perbone=False, use_loss_pose_perprojection=False, use_loss_pose_perprojection_2d=True,
                            use_ce_match=False)
+# defaults of lib/core/config.py:152,169 (TRAIN.LR, TRAIN.clip_max_norm) and :245 (DECODER.lr_linear_proj_mult)
+_TRAIN_DEFAULTS = dict(LR=0.001, clip_max_norm=0.1)
+_LR_LINEAR_PROJ_NAMES = ("reference_points", "sampling_offsets")
 
 
 def load_yaml_config(path):
@@ -33,6 +36,7 @@ def load_yaml_config(path):
         raw = yaml.safe_load(f)
     dec = dict(_DECODER_DEFAULTS)
     dec.update(raw.get("DECODER", {}))
+    train = {k: (raw.get("TRAIN") or {}).get(k, v) for k, v in _TRAIN_DEFAULTS.items()}
     return SimpleNamespace(
         DECODER=SimpleNamespace(**dec),
         NETWORK=SimpleNamespace(IMAGE_SIZE=list(raw["NETWORK"]["IMAGE_SIZE"])),
@@ -40,6 +44,7 @@ def load_yaml_config(path):
                                      SPACE_CENTER=list(raw["MULTI_PERSON"]["SPACE_CENTER"])),
         DATASET=SimpleNamespace(CAMERA_NUM=int(raw["DATASET"]["CAMERA_NUM"])),
         DEBUG=SimpleNamespace(VISUALIZATION_JUMP_NUM=-1),
+        TRAIN=SimpleNamespace(LR=float(train["LR"]), clip_max_norm=float(train["clip_max_norm"])),
     )
 
 
@@ -88,6 +93,29 @@ def build_training_head(cfg, decoder=None, t_pose=None):
     criterion, weight_dict, decay = build_criterion_from_cfg(cfg)
     head.set_criterion(criterion, decay)
     return head, weight_dict
+
+
+def build_optimizer_from_cfg(head, cfg, optim_type=None, weight_decay=1e-4, lr=None):
+    """optim.FusedAdam with the reference's two parameter groups (run/train_3d.py:116-146): every trainable parameter at TRAIN.LR,
+    except those whose name contains 'reference_points' or 'sampling_offsets' at TRAIN.LR * DECODER.lr_linear_proj_mult.
+    optim_type (default DECODER.optimizer): 'adam' -- no weight decay -- or 'adamw' -- decoupled `weight_decay` (the reference's
+    1e-4).  The gradient-norm clip is TRAIN.clip_max_norm (function.py:171-176), and the step leaves the gradients zeroed in
+    place.  A cfg without TRAIN / the DECODER keys takes the defaults of lib/core/config.py."""
+    from .optim import FusedAdam
+    train = getattr(cfg, "TRAIN", None)
+    lr = float(getattr(train, "LR", _TRAIN_DEFAULTS["LR"]) if lr is None else lr)
+    clip = float(getattr(train, "clip_max_norm", _TRAIN_DEFAULTS["clip_max_norm"]))
+    mult = float(getattr(cfg.DECODER, "lr_linear_proj_mult", 0.1))
+    optim_type = getattr(cfg.DECODER, "optimizer", "adam") if optim_type is None else optim_type
+    if optim_type not in ("adam", "adamw"):
+        raise ValueError("optimizer %r (adam | adamw)" % (optim_type,))
+    slow = lambda n: any(k in n for k in _LR_LINEAR_PROJ_NAMES)     # noqa: E731
+    named = [(n, p) for n, p in head.named_parameters() if p.requires_grad]
+    groups = [{"params": [p for n, p in named if not slow(n)], "lr": lr},
+              {"params": [p for n, p in named if slow(n)], "lr": lr * mult}]
+    adamw = optim_type == "adamw"
+    return FusedAdam(groups, lr=lr, weight_decay=float(weight_decay) if adamw else 0.0, decoupled_weight_decay=adamw,
+                     clip_max_norm=clip, zero_grad=True)
 
 
 def build_decoder_for_case(case, device="cuda", dtype=torch.float32):

@@ -984,3 +984,38 @@ def criterion(logits, poses, poses_2d, pair_query, pair_gt, pair_count, joints_3
                                   L.ptr(ws), nbytes, L.ptr(table), L.ptr(gl), L.ptr(gp), L.ptr(gp2), L.stream_ptr()),
                 "mvg_criterion")
     return table, gl, gp, gp2
+
+
+# ---- optimizer step (csrc/optim.hip) -----------------------------------------------------------------------------------------
+OPTIM_CHUNK = 4096                 # MVG_OPTIM_CHUNK
+OPTIM_TENSOR_WORDS, OPTIM_GROUP_WORDS = 6, 6
+OPTIM_STATE_HEADER, OPTIM_STATE_PER_GROUP = 64, 16
+
+
+def optim_state_words(n_groups):
+    """int64 words of the state block of optim_step for n_groups hyper-parameter groups"""
+    return (OPTIM_STATE_HEADER + n_groups * OPTIM_STATE_PER_GROUP) // 8
+
+
+def optim_step(tensor_table, chunk_table, group_table, state, workspace, loss=None, max_norm=0.0, zero_grad=False, norm_out=None):
+    """clip_grad_norm_ + Adam / AdamW over every tensor of the tables in at most three launches (mvg_optim_step; the table layouts
+    are in include/mvg_decoder.h).  tensor_table (n_tensors, 6) int64, chunk_table (n_chunks, 2) int32, group_table (n_groups, 6)
+    float64, state (>= optim_state_words(n_groups),) int64, workspace (>= max(n_chunks, 1),) float64; loss / norm_out: float32
+    device scalars or None.  Updates the tensors the tables point to in place; nothing is read back."""
+    L.require_cuda(tensor_table, chunk_table, group_table, state, workspace, loss, norm_out)
+    if (tensor_table.dtype != torch.int64 or tensor_table.dim() != 2 or tensor_table.shape[1] != OPTIM_TENSOR_WORDS
+            or chunk_table.dtype != torch.int32 or chunk_table.dim() != 2 or chunk_table.shape[1] != 2
+            or group_table.dtype != torch.float64 or group_table.dim() != 2 or group_table.shape[1] != OPTIM_GROUP_WORDS
+            or state.dtype != torch.int64 or workspace.dtype != torch.float64
+            or not all(t.is_contiguous() for t in (tensor_table, chunk_table, group_table, state, workspace))):
+        raise RuntimeError("mvg_optim_step: tables (n, 6) int64 / (n, 2) int32 / (n, 6) float64, state int64, workspace float64, "
+                           "all contiguous, expected")
+    for s in (loss, norm_out):
+        if s is not None and (s.dtype != torch.float32 or s.numel() != 1):
+            raise RuntimeError("mvg_optim_step: loss / norm_out must be float32 device scalars")
+    lib = L.load()
+    with _timed("optim_step"):
+        L.check(lib.mvg_optim_step(L.ptr(tensor_table), tensor_table.shape[0], L.ptr(chunk_table), chunk_table.shape[0],
+                                   L.ptr(group_table), group_table.shape[0], L.ptr(state), state.numel() * 8, L.ptr(workspace),
+                                   workspace.numel() * 8, L.ptr(loss), float(max_norm), int(bool(zero_grad)), L.ptr(norm_out),
+                                   L.stream_ptr()), "mvg_optim_step")

@@ -1,8 +1,12 @@
 """Time of one training step of the decoder at cfg-2 size: forward under autograd (torch geometry +
 ProjAttn with the HIP sampling forward / backward kernels) + backward to every parameter.  GPU only.
-python tools/train_step_probe.py [config] [steps] [fp32|bf16] [--criterion]   (bf16: DQDecoder.set_training_dtype(torch.bfloat16))
+python tools/train_step_probe.py [config] [steps] [fp32|bf16] [--criterion] [--optimizer fused|torch]
+(bf16: DQDecoder.set_training_dtype(torch.bfloat16))
 --criterion: the real step -- DecoderHead.forward_train (ground-truth match, decoder with the matched mask, fused criterion) on
-synthetic ground truth (5 persons, K = 5) and total_loss(...).backward() -- instead of the made-up loss of the default run."""
+synthetic ground truth (5 persons, K = 5) and total_loss(...).backward() -- instead of the made-up loss of the default run.
+--optimizer: the step includes the weight update (lr 4e-4, clip 0.1, the reference's two parameter groups).  torch: `if loss > 0`
+on the host, clip_grad_norm_ and torch.optim.Adam, gradients zeroed in place; fused: optim.FusedAdam.step(loss=loss), the guard
+on the device.  Without the option the step ends at backward() and drops the gradients, as before."""
 import os
 import sys
 import time
@@ -16,6 +20,13 @@ from mvgformer_amd.synthetic import build_case  # noqa: E402
 
 with_criterion = "--criterion" in sys.argv
 argv = [a for a in sys.argv if a != "--criterion"]
+optimizer = None
+if "--optimizer" in argv:
+    i = argv.index("--optimizer")
+    optimizer = argv[i + 1] if i + 1 < len(argv) else ""
+    if optimizer not in ("fused", "torch"):
+        raise SystemExit("--optimizer fused|torch")
+    del argv[i:i + 2]
 cfg = argv[1] if len(argv) > 1 else "cfg2"
 steps = int(argv[2]) if len(argv) > 2 else 5
 tdt = argv[3] if len(argv) > 3 else "fp32"
@@ -41,20 +52,44 @@ if with_criterion:
     criterion, weight_dict, decay = build_criterion_from_cfg(ccfg)
     head = DecoderHead(dec, case.NQ, 15, 256, case.space_size, case.space_center).to("cuda").set_criterion(criterion, decay)
     head.train()
+opt = None
+if optimizer is not None:
+    from types import SimpleNamespace as NS
+    from mvgformer_amd.factory import build_optimizer_from_cfg
+    model = head if head is not None else dec
+    ocfg = NS(DECODER=NS(optimizer="adam", lr_linear_proj_mult=0.1), TRAIN=NS(LR=0.0004, clip_max_norm=0.1))
+    opt = build_optimizer_from_cfg(model, ocfg)
+    if optimizer == "torch":
+        opt = torch.optim.Adam([{"params": gr["params"], "lr": gr["lr"]} for gr in opt.param_groups], lr=0.0004)
+        trained = [p for gr in opt.param_groups for p in gr["params"]]
+
+
+def update(loss):
+    if optimizer == "fused":
+        opt.step(loss=loss)                            # clip, Adam, the loss guard and the zeroing of the gradients: 3 launches
+    elif loss > 0:                                     # lib/core/function.py:167-178
+        torch.nn.utils.clip_grad_norm_(trained, 0.1)
+        opt.step()
+        opt.zero_grad(set_to_none=False)
 
 
 def step():
-    for p in dec.parameters():
-        p.grad = None
+    if opt is None:
+        for p in dec.parameters():
+            p.grad = None
     if head is not None:
         _, loss_dict = head.forward_train(g.src_views, g.meta, g.spatial_shapes, g.level_start_index, threshold=0.1)
         loss = total_loss(loss_dict, weight_dict)
         loss.backward()
+        if opt is not None:
+            update(loss.detach())
         return loss
     out = dec(g.tgt, g.reference_points, g.src_views, g.meta, g.spatial_shapes, g.level_start_index, None,
               query_pos=g.query_pos, threshold=0.1)
     loss = out[0].float().pow(2).mean() + 1e-6 * out[1].float().pow(2).mean() + sum(c.float().sum() for c in out[4]) * 1e-3
     loss.backward()
+    if opt is not None:
+        update(loss.detach())
     return loss
 
 
@@ -69,5 +104,5 @@ dt = (time.perf_counter() - t0) / steps
 # one multi-tensor launch instead of five per parameter: a profile of this script counts the steps' launches, not this check's
 grads = [p.grad for p in dec.parameters() if p.grad is not None]
 n_grad = int(torch.isfinite(torch.stack(torch._foreach_norm(grads))).sum())
-print("%s training step (%s%s, forward + backward): %.1f ms; loss %.4f; %d / %d parameters with finite gradients; peak memory %.1f GB"
-      % (cfg, tdt, ", match + criterion" if with_criterion else "", dt * 1e3, float(loss), n_grad, sum(1 for _ in dec.parameters()), torch.cuda.max_memory_allocated() / 2 ** 30))
+print("%s training step (%s%s, forward + backward%s): %.1f ms; loss %.4f; %d / %d parameters with finite gradients; peak memory %.1f GB"
+      % (cfg, tdt, ", match + criterion" if with_criterion else "", " + %s optimizer" % optimizer if optimizer else "", dt * 1e3, float(loss), n_grad, sum(1 for _ in dec.parameters()), torch.cuda.max_memory_allocated() / 2 ** 30))
