@@ -118,6 +118,43 @@ class DecoderContext:
                            src_views[0].device).pack(src_views)
 
 
+class DecoderRun:
+    """State of ONE forward over an ordered list of layers.  ``with run:`` attaches it to the layers (``_run``) and detaches it however
+    the block ends: a hand-off nobody consumed or a hook that never fired goes with it.  The runner sets ``i`` to the position of
+    the layer it calls next (a decoder with share_layer_weights holds ONE layer object at every position)."""
+
+    def __init__(self, layers, ctx, chained):
+        self.layers, self.ctx, self.chained, self.i = list(layers), ctx, chained, 0
+        self.hs_buf = self.flags = self.geo_buf = None      # (layers,B,Lq,C) f32; (layers,) int32 zeros; the stacked 3D / 2D outputs
+        # consumed once, by position: the query term (B*Lq,192) f32 from the previous layer's chain B, (new_ref, (r, ref_lvl, inside))
+        # from the previous layer's triangulation launch, the callable that issues the NEXT layer's pyramid products
+        self.xw_in, self.proj_in, self.after_chain_b = {}, {}, {}
+
+    def __enter__(self):
+        for layer in self.layers:
+            layer._run = self
+        return self
+
+    def __exit__(self, *exc):
+        for layer in self.layers:
+            layer._run = None
+
+    def __deepcopy__(self, memo):
+        return None         # a copy of a layer is outside every forward
+
+    def next_layer(self):
+        """the layer that consumes the current layer's output, when the layers are chained"""
+        return self.layers[self.i + 1] if (self.chained and self.i + 1 < len(self.layers)) else None
+
+    def outputs(self):
+        """the current layer's slices of the stacked buffers: (hidden state, any-valid flag int32[1], (3D, 2D, projected 2D)) or None"""
+        return (None if self.hs_buf is None else self.hs_buf[self.i], None if self.flags is None else self.flags[self.i:self.i + 1],
+                None if self.geo_buf is None else tuple(buf[self.i] for buf in self.geo_buf))
+
+
+_NO_RUN = DecoderRun((), None, False)       # what a layer called on its own sees: no context, no next layer, no preallocated outputs
+
+
 class MvPDecoderLayer(nn.Module):
     """helpers shared with the MvP base class (mvp_decoder.py:49-105)."""
 
@@ -191,14 +228,7 @@ class DQDecoderLayer(MvPDecoderLayer):
         # fp32 path: output projection + pose MLP skip the tiles whose pairs are all outside their image (round 3)
         self.skip_masked_f32 = True
         self._wc = WeightCache()
-        self._ctx = None   # set by DQDecoder.forward so the pyramid / cameras are packed once
-        self._tgt_out = None   # set by DQDecoder.forward: this layer's slice of the stacked hidden states
-        self._flag = None      # set by DQDecoder.forward: this layer's zeroed any-valid flag (int32[1])
-        self._geo_out = None   # set by DQDecoder.forward: this layer's slices of the stacked 3D / 2D outputs
-        self._next_layer = None   # set by DQDecoder.forward: the layer that consumes this layer's output
-        self._xw_in = None        # set by the previous layer: this layer's query term (B*Lq,192) f32
-        self._after_chain_b = None    # set by DQDecoder.launch_pyramid_projections (just-in-time schedule): issues the NEXT layer's pyramid products
-        self._proj_in = None      # set by the previous layer's triangulation launch: (new_ref, (r, ref_lvl, inside)) of this layer
+        self._run = None   # the DecoderRun of the forward this layer is part of; None outside one
         # query-sharded runs (mvgformer_amd.dist): callable(any_valid int32[1]) that makes the
         # "no query valid anywhere -> force query (0,0)" rule (dq_decoder.py:620-623) global
         self._any_valid_hook = None
@@ -354,6 +384,29 @@ class DQDecoderLayer(MvPDecoderLayer):
                   (not self.open_forward_ffn or self.linear1.out_features == 1024))
         return fuse_a, fuse_b
 
+    def _kernel_path(self, dt, C, J, Lq, levels):
+        """(chain A, chain B) of one forward_features call, each "bf16" (fused LDS-resident chains, csrc/chain.hip), "f32h" (fp32 on
+        pre-split two-part fp16 operands, csrc/f32s.hip) or None (one launch per GEMM / row op).  The two can differ."""
+        a16, b16 = self._fuses_chains(dt)
+        a32, b32 = self._fuses_chains_f32(dt, Lq, levels)
+        return ("bf16" if a16 else "f32h" if (a32 and C == 256) else None,
+                "bf16" if (b16 and C == 256 and J <= 64) else "f32h" if (b32 and C == 256) else None)
+
+    def _next_query_term(self, nxt, path_b, tgt, query_pos, levels):
+        """operands with which this layer's fused chain B also computes xw = (tgt' + query_pos) W^T + b, the query term of the next layer
+        `nxt` (its rows are in LDS): (qp, W, b, n) for the bf16 chain, (qp, W, scale, b, n) for the f32h one; None: not taken"""
+        dt = self.compute_dtype
+        if nxt is None or nxt.compute_dtype != dt or not (query_pos is None or query_pos.shape == tgt.shape):
+            return None
+        if not (nxt._fuses_chains_f32(dt, tgt.shape[1], levels)[0] if path_b == "f32h" else
+                nxt.use_fused_chains and nxt.proj_attn.uses_fast_path(dt)):
+            return None
+        qp = None if query_pos is None else query_pos.float().reshape(-1, tgt.shape[2]).contiguous()
+        if path_b == "f32h":
+            (Wn, sn), bn, n_next = nxt.proj_attn.query_term_weights_f32h()
+            return qp, Wn, sn, bn, n_next
+        return (qp,) + tuple(nxt.proj_attn.query_term_weights(dt))
+
     def prepare_caches(self, dtype=None):
         """Build every cached operand of the inference path on the CURRENT stream, outside any graph capture (one of
         them, o_masked, launches a kernel).  An entry created inside a capture would live in the graph's private pool
@@ -416,7 +469,7 @@ class DQDecoderLayer(MvPDecoderLayer):
         if dropping or (torch.is_grad_enabled() and (tgt.requires_grad or any(p.requires_grad for p in self.parameters()))):
             return self.forward_autograd(tgt, query_pos, reference_points, src_views, src_spatial_shapes,
                                          level_start_index, meta, indices, threshold)
-        ctx = self._ctx
+        ctx = (self._run or _NO_RUN).ctx
         if ctx is None:
             ctx = DecoderContext.build(src_views, src_spatial_shapes, level_start_index, meta, self.img_size,
                                        self.compute_dtype, tgt.shape[0])
@@ -467,7 +520,7 @@ class DQDecoderLayer(MvPDecoderLayer):
         x = self.with_pos_embed(tgt, query_pos)
         # Per-forward constants of the geometry (packed camera records, level table, projection matrices): built once and kept on the
         # DecoderContext when the layer runs inside DQDecoder.forward -- as torch ops per layer they were ~40 launches each.
-        ctx = self._ctx
+        ctx = (self._run or _NO_RUN).ctx
         tc = getattr(ctx, "_train_cache", None) if ctx is not None else None
         if tc is not None and tc["key"] != (ctx.cams.data_ptr(), ctx.cams._version):
             tc = None           # the context was given new camera records: projection matrices and records are rebuilt
@@ -551,10 +604,12 @@ class DQDecoderLayer(MvPDecoderLayer):
         NQ = Lq // J
         dt = self.compute_dtype
         V = ctx.V
+        run = self._run or _NO_RUN
+        path_a, path_b = self._kernel_path(dt, C, J, Lq, ctx.levels)
 
         # 1. projective attention features of every view (generate_features, dq_decoder.py:516-593)
         X = reference_points.detach().reshape(B, Lq, 3).float().contiguous()
-        proj_in, self._proj_in = self._proj_in, None
+        proj_in = run.proj_in.pop(run.i, None)
         if proj_in is not None and proj_in[0].data_ptr() == X.data_ptr() and tuple(proj_in[0].shape) == tuple(X.shape):
             r, ref_lvl, inside = proj_in[1]      # projected by the previous layer's triangulation launch (same arithmetic)
         else:
@@ -563,19 +618,18 @@ class DQDecoderLayer(MvPDecoderLayer):
         if (query_pos is not None and tgt.dtype == torch.float32 and query_pos.dtype == torch.float32 and tgt.is_contiguous()
                 and query_pos.is_contiguous() and query_pos.shape == tgt.shape):
             x.parts = (tgt, query_pos)          # lets the fast path fold the add into the query-term GEMM
-        xw_in, self._xw_in = self._xw_in, None     # query term computed by the previous layer's chain B (or None)
+        xw_in = run.xw_in.pop(run.i, None)     # query term computed by the previous layer's chain B (or None)
         if xw_in is not None and tuple(xw_in.shape) != (B * Lq, 192):
             xw_in = None
         f32 = torch.float32
         pose_layers = self.pose_embed.MLP.layers
-        fuse_a, fuse_b = self._fuses_chains(dt)
         o = None
         if self.proj_attn._vp_event is None and getattr(ctx, "_packed_event", None) is not None:
             # this layer's pyramid products run inline on THIS stream (no side-stream launch reached it) while the pyramid was packed
             # on the side stream (DQDecoder.pack_pyramid): order the read behind the pack and keep the allocator informed
             torch.cuda.current_stream().wait_event(ctx._packed_event)
             ctx.feat.record_stream(torch.cuda.current_stream())
-        if fuse_a:
+        if path_a == "bf16":
             # processing order of the (image, query) pairs: image-space (Morton) order, pairs outside the image last
             # (mvg_bin_pairs); shared by the sampler (L1 locality, masked pairs skipped) and chain A (all-masked
             # tiles skipped).  "first": binned once per forward from the first layer's projections.
@@ -591,7 +645,7 @@ class DQDecoderLayer(MvPDecoderLayer):
                                                 order=order, xw=xw_in)
             wts, o_masked = self._chain_a_weights(dt)
             attn, o = ops.chain_attn_pose(samp, inside.view(-1), *wts, order=order, o_masked=o_masked)
-        elif self._fuses_chains_f32(dt, Lq, ctx.levels)[0] and C == 256:
+        elif path_a == "f32h":
             # fp32, fused: G-sampling kernel + chain A on pre-split operands (csrc/f32s.hip); pairs in processing order, masked
             # pairs last (zero-filled by the sampler, all-masked tiles skipped by the chain)
             order = ops.bin_pairs(ref_lvl, inside.view(-1), ctx.levels) if (self.proj_attn.sort_pairs and Lq <= 65536) else None
@@ -622,39 +676,21 @@ class DQDecoderLayer(MvPDecoderLayer):
             for b, q in enumerate(indices):
                 forced[b, torch.as_tensor(q, dtype=torch.long, device=tgt.device)] = 1
         tgt32 = tgt.float().reshape(B * Lq, C).contiguous()
-        fuse_b = fuse_b and C == 256 and J <= 64
-        fuse_b32 = self._fuses_chains_f32(dt)[1] and C == 256 and not fuse_b
-        if fuse_b32:
-            nxt = self._next_layer[0] if self._next_layer else None
-            next_proj = None
-            if (nxt is not None and nxt.compute_dtype == dt and nxt._fuses_chains_f32(dt, Lq, ctx.levels)[0]
-                    and (query_pos is None or query_pos.shape == tgt.shape)):
-                qp = None if query_pos is None else query_pos.float().reshape(B * Lq, C).contiguous()
-                (Wn, sn), bn, n_next = nxt.proj_attn.query_term_weights_f32h()
-                next_proj = (qp, Wn, sn, bn, n_next)
-            res = ops.chain_update_ffn_class_f32h(
-                attn, V, tgt32, *self._chain_b_weights_f32h(), threshold, B, NQ, J, forced, self.open_forward_ffn,
-                tgt_out=self._tgt_out, any_valid=self._flag, next_query_proj=next_proj)
+        if path_b is not None:
+            tgt_out, flag, _ = run.outputs()
+            next_proj = self._next_query_term(run.next_layer(), path_b, tgt, query_pos, ctx.levels)
+            if path_b == "f32h":
+                res = ops.chain_update_ffn_class_f32h(
+                    attn, V, tgt32, *self._chain_b_weights_f32h(), threshold, B, NQ, J, forced, self.open_forward_ffn,
+                    tgt_out=tgt_out, any_valid=flag, next_query_proj=next_proj)
+            else:
+                res = ops.chain_update_ffn_class(
+                    attn, V, tgt32, *self._chain_b_weights(dt), threshold, B, NQ, J, forced, self.open_forward_ffn,
+                    tgt_out=tgt_out, any_valid=flag, next_query_proj=next_proj,
+                    attn_inside=inside.view(-1) if path_a == "bf16" else None)   # chain A wrote zeros for the pairs outside their image
             tgt_update, prob, valid, any_valid = res[:4]
             if next_proj is not None:
-                nxt._xw_in = res[4]
-        elif fuse_b:
-            ffn = self.open_forward_ffn
-            # the next layer's query term xw = (tgt' + query_pos) W^T + b rides on this chain (its rows are in LDS)
-            nxt = self._next_layer[0] if self._next_layer else None     # (kept in a tuple: not a sub-module)
-            next_proj = None
-            if (nxt is not None and nxt.compute_dtype == dt and nxt.use_fused_chains and nxt.proj_attn.uses_fast_path(dt)
-                    and (query_pos is None or query_pos.shape == tgt.shape)):
-                Wn, bn, n_next = nxt.proj_attn.query_term_weights(dt)
-                qp = None if query_pos is None else query_pos.float().reshape(B * Lq, C).contiguous()
-                next_proj = (qp, Wn, bn, n_next)
-            res = ops.chain_update_ffn_class(
-                attn, V, tgt32, *self._chain_b_weights(dt), threshold, B, NQ, J, forced, ffn, tgt_out=self._tgt_out,
-                any_valid=self._flag, next_query_proj=next_proj,
-                attn_inside=inside.view(-1) if fuse_a else None)      # chain A wrote zeros for the pairs outside their image
-            tgt_update, prob, valid, any_valid = res[:4]
-            if next_proj is not None:
-                nxt._xw_in = res[4]
+                run.xw_in[run.i + 1] = res[4]
         else:
             mean = ops.mean_views(attn, V)
             u = ops.linear(mean, self._w("Wu", (self.feature_update_mlp.weight,), dt),
@@ -674,7 +710,7 @@ class DQDecoderLayer(MvPDecoderLayer):
         # 4. 2D offsets from the per-view attention features (calculate_2d_offsets, dq_decoder.py:659-717)
         if o is None:
             hcur = attn
-            masked = self._pose_masked_rows(dt) if (not fuse_a and order32 is not None) else None
+            masked = self._pose_masked_rows(dt) if order32 is not None else None
             for i, lin in enumerate(pose_layers[:-1]):
                 Wi, bi = self._w("Wpe%d" % i, (lin.weight,), dt), self._w("bpe%d" % i, (lin.bias,), f32)
                 if masked is not None:
@@ -684,7 +720,7 @@ class DQDecoderLayer(MvPDecoderLayer):
             o = ops.rowdot3(hcur, self._w("Wpe_last", (pose_layers[-1].weight,), f32),
                             self._w("bpe_last", (pose_layers[-1].bias,), f32))
 
-        hook, self._after_chain_b = self._after_chain_b, None
+        hook = run.after_chain_b.pop(run.i, None)
         if hook is not None:
             hook()      # just-in-time schedule: the next layer's pyramid products run next to this layer's triangulation + the binning
         return dict(r=r, o=o, valid=valid, any_valid=any_valid, tgt_update=tgt_update.view(B, Lq, C), prob=prob,
@@ -693,14 +729,12 @@ class DQDecoderLayer(MvPDecoderLayer):
     def forward_triangulate(self, st, ctx):
         """step 5: triangulation + scatter (learnable_triangulate, dq_decoder.py:399-461,1013-1029)."""
         V, B, NQ, J = st["dims"]
-        nxt = self._next_layer[0] if (self._next_layer and self.fuse_boundary) else None
-        if nxt is not None:      # the next layer's projection of the new points rides on this launch
-            new_ref, ref2d, proj2d, proj = ops.triangulate(st["r"], st["o"], ctx.cams, st["valid"], st["any_valid"], V, B, NQ,
-                                                           J, out=self._geo_out, next_levels=ctx.levels)
-            nxt._proj_in = (new_ref, proj)
-        else:
-            new_ref, ref2d, proj2d = ops.triangulate(st["r"], st["o"], ctx.cams, st["valid"], st["any_valid"], V, B, NQ, J,
-                                                     out=self._geo_out)
+        run = self._run or _NO_RUN
+        boundary = self.fuse_boundary and run.next_layer() is not None     # the next layer's projection of the new points rides on this launch
+        new_ref, ref2d, proj2d, *proj = ops.triangulate(st["r"], st["o"], ctx.cams, st["valid"], st["any_valid"], V, B, NQ, J,
+                                                        out=run.outputs()[2], next_levels=ctx.levels if boundary else None)
+        if boundary:
+            run.proj_in[run.i + 1] = (new_ref, proj[0])
         return st["tgt_update"], new_ref, ref2d, proj2d, st["prob"]
 
 
@@ -820,9 +854,7 @@ class DQDecoder(MvPDecoder):
         by an event its consumer waits on.  Returns the side stream (pass it to join_pyramid_projections before
         the forward / the captured graph ends) or None when the projections run inline.  forked: `side` already waits for
         whatever produced ctx.feat (pack_pyramid).  jit: the caller runs the whole forward inside ONE fork / join of `side` (not the
-        segmented graphs of mvgformer_amd.dist) -- the just-in-time schedule may be used."""
-        for layer in self.layers:
-            layer._after_chain_b = None       # hooks of an earlier forward that did not reach its layer (an exception in between)
+        segmented graphs of mvgformer_amd.dist) -- the just-in-time schedule may be used; its hooks go into the layers' DecoderRun."""
         if side is None:
             side = self.fork_side_stream(ctx.feat.device)
             if side is None:
@@ -860,7 +892,7 @@ class DQDecoder(MvPDecoder):
                             side.wait_stream(torch.cuda.current_stream())     # behind the previous layer's chain B
                             with torch.cuda.stream(side):
                                 issue()
-                        self.layers[gi - 1]._after_chain_b = hook
+                        self.layers[0]._run.after_chain_b[gi - 1] = hook
                     else:
                         issue()
         return side
@@ -941,7 +973,6 @@ class DQDecoder(MvPDecoder):
         layer0 = self.layers[0]
         ctx = context
         side = None
-        hs_buf = flags = geo_buf = None
         try:
             deferred_pack = None
             if ctx is None:
@@ -957,64 +988,45 @@ class DQDecoder(MvPDecoder):
             ctx.order = None
             inter, inter_ref, inter_2d, inter_proj, classes = [], [], [], [], []
             ref_points_2d = None
-            side = self.fork_side_stream(tgt.device, (tgt.shape[1], ctx.levels.L, ctx.levels.S))
-            if deferred_pack is not None:
-                self.pack_pyramid(ctx, deferred_pack, side)
-            if side is not None:
-                self.launch_pyramid_projections(ctx, side, forked=True, jit=True)
-            # the fused chain writes every layer's hidden state straight into its slice of the stacked output
-            hs_buf = None
-            if self.return_intermediate and not torch.is_grad_enabled() and tgt.is_cuda:
-                hs_buf = torch.empty((len(self.layers),) + tuple(tgt.shape), dtype=torch.float32, device=tgt.device)
-            flags = torch.zeros((len(self.layers),), dtype=torch.int32, device=tgt.device) if tgt.is_cuda else None
-            geo_buf = None
-            if hs_buf is not None:
-                nl, Bq, Lq_ = len(self.layers), tgt.shape[0], tgt.shape[1]
-                Vn = ctx.V
-                geo_buf = (torch.empty((nl, Bq, Lq_, 3), dtype=torch.float32, device=tgt.device),
-                           torch.empty((nl, Bq, Vn, Lq_, 2), dtype=torch.float32, device=tgt.device),
-                           torch.empty((nl, Bq, Vn, Lq_, 2), dtype=torch.float32, device=tgt.device))
-            for lid, layer in enumerate(self.layers):
-                layer._ctx = ctx
-                layer._tgt_out = None if hs_buf is None else hs_buf[lid]
-                layer._flag = None if flags is None else flags[lid:lid + 1]
-                layer._geo_out = None if geo_buf is None else (geo_buf[0][lid], geo_buf[1][lid], geo_buf[2][lid])
-                layer._next_layer = ((self.layers[lid + 1],) if (self.fuse_next_query_term and lid + 1 < len(self.layers))
-                                     else None)
-                output, reference_points, ref_points_2d, projs_2d_absolute, outputs_class = layer(
-                    output, query_pos, reference_points[:, :, None] if reference_points.dim() == 3 else reference_points,
-                    src_views, src_spatial_shapes, src_level_start_index, meta, src_padding_mask,
-                    rgb_views=rgb_views, output_dir=output_dir, frame_id=frame_id, indices=indices,
-                    threshold=threshold, indices_all=indices_all)
-                if self.return_intermediate:
-                    inter.append(output)
-                    inter_ref.append(reference_points)
-                    inter_2d.append(ref_points_2d)
-                    inter_proj.append(projs_2d_absolute)
-                    classes.append(outputs_class)
+            with DecoderRun(self.layers, ctx, self.fuse_next_query_term) as run:
+                side = self.fork_side_stream(tgt.device, (tgt.shape[1], ctx.levels.L, ctx.levels.S))
+                if deferred_pack is not None:
+                    self.pack_pyramid(ctx, deferred_pack, side)
+                if side is not None:
+                    self.launch_pyramid_projections(ctx, side, forked=True, jit=True)
+                # the fused chain writes every layer's hidden state straight into its slice of the stacked output
+                if self.return_intermediate and not torch.is_grad_enabled() and tgt.is_cuda:
+                    run.hs_buf = torch.empty((len(self.layers),) + tuple(tgt.shape), dtype=torch.float32, device=tgt.device)
+                if tgt.is_cuda:
+                    run.flags = torch.zeros((len(self.layers),), dtype=torch.int32, device=tgt.device)
+                if run.hs_buf is not None:
+                    nl, Bq, Lq_, Vn = len(self.layers), tgt.shape[0], tgt.shape[1], ctx.V
+                    run.geo_buf = (torch.empty((nl, Bq, Lq_, 3), dtype=torch.float32, device=tgt.device),
+                                   torch.empty((nl, Bq, Vn, Lq_, 2), dtype=torch.float32, device=tgt.device),
+                                   torch.empty((nl, Bq, Vn, Lq_, 2), dtype=torch.float32, device=tgt.device))
+                for lid, layer in enumerate(self.layers):
+                    run.i = lid
+                    output, reference_points, ref_points_2d, projs_2d_absolute, outputs_class = layer(
+                        output, query_pos, reference_points[:, :, None] if reference_points.dim() == 3 else reference_points,
+                        src_views, src_spatial_shapes, src_level_start_index, meta, src_padding_mask,
+                        rgb_views=rgb_views, output_dir=output_dir, frame_id=frame_id, indices=indices,
+                        threshold=threshold, indices_all=indices_all)
+                    if self.return_intermediate:
+                        inter.append(output)
+                        inter_ref.append(reference_points)
+                        inter_2d.append(ref_points_2d)
+                        inter_proj.append(projs_2d_absolute)
+                        classes.append(outputs_class)
         finally:
-            for layer in self.layers:
-                layer._ctx = None
-                layer._tgt_out = None
-                layer._flag = None
-                layer._geo_out = None
-                layer._next_layer = None
-                layer._xw_in = None
-                layer._proj_in = None
-                layer._after_chain_b = None
             self.join_pyramid_projections(side)
         if self.return_intermediate:
-            in_place = hs_buf is not None and all(t.data_ptr() == hs_buf[i].data_ptr() and t.shape == hs_buf[i].shape
-                                                  for i, t in enumerate(inter))
-            hs = hs_buf if in_place else torch.stack(inter)
-
             def stacked(parts, buf):
                 same = buf is not None and all(t.data_ptr() == buf[i].data_ptr() and t.shape == buf[i].shape
                                                for i, t in enumerate(parts))
                 return buf if same else torch.stack(parts)
-            return (hs, stacked(inter_ref, None if geo_buf is None else geo_buf[0]),
-                    stacked(inter_2d, None if geo_buf is None else geo_buf[1]),
-                    stacked(inter_proj, None if geo_buf is None else geo_buf[2]), classes)
+            geo_buf = run.geo_buf or (None, None, None)
+            return (stacked(inter, run.hs_buf), stacked(inter_ref, geo_buf[0]), stacked(inter_2d, geo_buf[1]),
+                    stacked(inter_proj, geo_buf[2]), classes)
         return output, reference_points, ref_points_2d
 
 

@@ -20,6 +20,8 @@ from __future__ import annotations
 import torch
 import torch.distributed as dist
 
+from .decoder import DecoderRun
+
 
 def shard_bounds(NQ, world, rank):
     """contiguous, balanced block [lo, hi) of person-queries for `rank` (first NQ % world ranks
@@ -174,48 +176,41 @@ class GraphedShardedDecoder:
             self.graphs.append(g)
             return res
 
-        # same layer chaining as DQDecoder.forward: layer l's fused chain B also emits layer l+1's query term
-        fuse = getattr(self.dec, "fuse_next_query_term", False)
-        for l, layer in enumerate(layers):
-            layer._next_layer = (layers[l + 1],) if (fuse and l + 1 < len(layers)) else None
-            layer._xw_in = None
         ref = self.ref if self.ref.dim() == 4 else self.ref[:, :, None]
 
         def first():
             # every layer's pyramid-side GEMMs (replicated on all ranks: they bound the strong scaling) are issued on
             # the side stream in this segment, next to layer 0's query-side kernels; the later segments find them done
-            side = self.dec.fork_side_stream(self.tgt.device) if hasattr(self.dec, "fork_side_stream") else None
+            side = self.dec.fork_side_stream(self.tgt.device)
             if side is not None:
                 self.dec.pack_pyramid(self.ctx, self.src, side)
                 self.dec.launch_pyramid_projections(self.ctx, side, forked=True)
             else:
                 self.ctx.pack(self.src)
             st0 = layers[0].forward_features(self.tgt, self.qpos, ref, self.ctx, self.thr)
-            if side is not None:
-                self.dec.join_pyramid_projections(side, keep_results=True)
+            self.dec.join_pyramid_projections(side, keep_results=True)
             return st0
-        st = segment(first)
-        for l, layer in enumerate(layers):
-            self.flags.append(st["any_valid"])
-            last = l + 1 == len(layers)
 
-            def body(layer=layer, st=st, last=last, l=l):
-                o = layer.forward_triangulate(st, self.ctx)
-                outs.append(o)
-                if last:
-                    tup = (torch.stack([x[0] for x in outs]), torch.stack([x[1] for x in outs]),
-                           torch.stack([x[2] for x in outs]), torch.stack([x[3] for x in outs]), [x[4] for x in outs])
-                    return pack_outputs(tup, self.NQ, self.J, self.world, self.rank, self.gather_hidden)
-                return layers[l + 1].forward_features(o[0], self.qpos, o[1][:, :, None], self.ctx, self.thr)
-            res = segment(body)
-            if not last:
-                st = res
-        for layer in layers:
-            layer._next_layer = None
-            layer._xw_in = None
-            layer._proj_in = None
-            layer._after_chain_b = None
-            layer.proj_attn._vp_event = None
+        # ONE run over all segments (same layer chaining as DQDecoder.forward): a hand-off between two of them lives in the shared pool
+        with DecoderRun(layers, self.ctx, self.dec.fuse_next_query_term) as run:
+            st = segment(first)
+            for l, layer in enumerate(layers):
+                self.flags.append(st["any_valid"])
+                last = l + 1 == len(layers)
+
+                def body(layer=layer, st=st, last=last, l=l):
+                    o = layer.forward_triangulate(st, self.ctx)
+                    outs.append(o)
+                    if last:
+                        tup = (torch.stack([x[0] for x in outs]), torch.stack([x[1] for x in outs]),
+                               torch.stack([x[2] for x in outs]), torch.stack([x[3] for x in outs]), [x[4] for x in outs])
+                        return pack_outputs(tup, self.NQ, self.J, self.world, self.rank, self.gather_hidden)
+                    run.i = l + 1
+                    return layers[l + 1].forward_features(o[0], self.qpos, o[1][:, :, None], self.ctx, self.thr)
+                res = segment(body)
+                if not last:
+                    st = res
+        self.dec.join_pyramid_projections(None)     # the projections kept across the segments are dropped
         self.send, self.geo = res
         self.recv = self.send.new_empty((self.world * self.geo["nq_max"],) + tuple(self.send.shape[1:]))
         self.out = segment(lambda: unpack_outputs(self.recv, self.geo))
@@ -251,14 +246,11 @@ class SpeculativeShardedDecoder:
         J = layers[0].num_joints
         self.flags = torch.zeros((len(layers),), dtype=torch.int32, device=tgt.device)
         self.fallbacks = 0
-        fuse = getattr(dec, "fuse_next_query_term", False)
         ref = reference_points if reference_points.dim() == 4 else reference_points[:, :, None]
+        run = DecoderRun(layers, ctx, dec.fuse_next_query_term)
 
         def body():
-            for l, layer in enumerate(layers):
-                layer._next_layer = (layers[l + 1],) if (fuse and l + 1 < len(layers)) else None
-                layer._xw_in = None
-            side = dec.fork_side_stream(tgt.device) if hasattr(dec, "fork_side_stream") else None
+            side = dec.fork_side_stream(tgt.device)
             if side is not None:
                 dec.pack_pyramid(ctx, src_views, side)
                 dec.launch_pyramid_projections(ctx, side, forked=True, jit=True)
@@ -272,24 +264,19 @@ class SpeculativeShardedDecoder:
                 o = layer.forward_triangulate(st, ctx)
                 outs.append(o)
                 if l + 1 < len(layers):
+                    run.i = l + 1
                     st = layers[l + 1].forward_features(o[0], query_pos, o[1][:, :, None], ctx, threshold)
-            if side is not None:
-                dec.join_pyramid_projections(side)
+            dec.join_pyramid_projections(side)
             tup = (torch.stack([x[0] for x in outs]), torch.stack([x[1] for x in outs]), torch.stack([x[2] for x in outs]),
                    torch.stack([x[3] for x in outs]), [x[4] for x in outs])
             return pack_outputs(tup, NQ, J, self.world, self.rank, gather_hidden)
 
         try:
             self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph, pool=self.exact.graphs[0].pool()):
+            with run, torch.cuda.graph(self.graph, pool=self.exact.graphs[0].pool()):
                 self.send, self.geo = body()
         finally:
-            for layer in layers:
-                layer._next_layer = None
-                layer._xw_in = None
-                layer._proj_in = None
-                layer._after_chain_b = None     # a hook left by a body that raised must not fire in a later forward
-                layer.proj_attn._vp_event = None
+            dec.join_pyramid_projections(None)      # events of a body that raised
         self.recv = self.send.new_empty((self.world * self.geo["nq_max"],) + tuple(self.send.shape[1:]))
         self.unpack = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.unpack, pool=self.exact.graphs[0].pool()):

@@ -161,11 +161,31 @@ def test_deepcopy_of_a_decoder_does_not_copy_run_time_buffers():
     pa0 = dec.layers[0].proj_attn
     pa0._f32_pool["slot"] = (torch.zeros(4), torch.zeros(4))
     pa0._vp, pa0._G = torch.zeros(3), torch.zeros(3)
-    dec.layers[0]._after_chain_b = None
+    dec.layers[0]._run = None
     cp = copy.deepcopy(dec)
+    assert all(l._run is None for l in cp.layers)
     assert cp.layers[0].proj_attn._f32_pool == {} and cp.layers[0].proj_attn._f32_pool is cp.layers[1].proj_attn._f32_pool
     assert cp.layers[0].proj_attn._f32_pool is not pa0._f32_pool and cp.layers[0].proj_attn._vp is None
     a, b = dec.state_dict(), cp.state_dict()
     assert list(a) == list(b) and all(torch.equal(a[k], b[k]) and a[k].data_ptr() != b[k].data_ptr() for k in a)
     single = copy.deepcopy(pa0)
     assert single._f32_pool == {} and single._f32_pool is not pa0._f32_pool
+
+
+def test_a_forward_that_raises_leaves_no_run_attached():
+    """DecoderRun is the one place per-forward state lives: DQDecoder.forward attaches it to the layers and detaches it however the
+    forward ends.  On the CPU the first layer refuses to run; afterwards no layer holds a run.  A layer on its own never has one."""
+    import pytest
+    from mvgformer_amd.decoder import DQDecoderLayer
+    from mvgformer_amd.factory import build_decoder_for_case, case_to_device
+    from mvgformer_amd.synthetic import build_case
+    case = build_case("cfg1", seed=0, layers=2)
+    dec = build_decoder_for_case(case, "cpu", torch.float32)
+    assert all(l._run is None for l in dec.layers)
+    c = case_to_device(case, "cpu")
+    with torch.no_grad(), pytest.raises(RuntimeError, match="Not implemented on the CPU"):
+        dec(c.tgt, c.reference_points, c.src_views, c.meta, c.spatial_shapes, c.level_start_index, None, query_pos=c.query_pos,
+            threshold=0.1)
+    assert all(l._run is None for l in dec.layers)
+    layer = DQDecoderLayer([8000.0, 8000.0, 2000.0], [0.0, 0.0, 800.0], [960, 512], 3)
+    assert layer._run is None

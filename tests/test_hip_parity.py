@@ -1292,7 +1292,7 @@ def test_side_stream_pyramid_projections_change_nothing():
                 for x, y in zip(ref, got[:4]):
                     assert torch.equal(x, y)
             assert all(l.proj_attn._vp_event is None for l in dec.layers)          # every event consumed / dropped
-            assert all(l._after_chain_b is None for l in dec.layers)               # every hook fired / removed
+            assert all(l._run is None for l in dec.layers)                         # no run attached: every hook fired / dropped
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
                 out = run()
