@@ -457,6 +457,24 @@ int mvg_optim_step(const void* tensor_table, int n_tensors, const void* chunk_ta
                    int n_groups, void* state, size_t state_bytes, void* workspace, size_t workspace_bytes, const float* loss,
                    float max_norm, int zero_grad, float* norm_out, void* stream);
 
+/* ---- derived bf16 operands of the bf16 training path (csrc/operands.hip) ------------------------------------------------- */
+#define MVG_OPERANDS_TILE 64          /* one workgroup converts one 64 x 64 tile                                             */
+#define MVG_OPERANDS_RECORD_WORDS 8   /* 8-byte words per source-matrix record                                               */
+
+/* Rewrites, in one launch, the bf16 copy and / or the transposed bf16 copy of every fp32 matrix of a table: what the bf16
+ * training path multiplies by, refreshed on the device right behind mvg_optim_step (also inside a HIP graph).  Both tables are
+ * in DEVICE memory, 8-byte aligned:
+ *   record_table  n_records records of 8 x 8 bytes: src (fp32, row-major N x K), int64 N, K, src_ld (elements), dst (bf16
+ *                 row-major N x K, or NULL), int64 dst_ld, dstT (bf16 K x N, or NULL), int64 dstT_ld.  A concatenated weight is
+ *                 several records whose dst / dstT point into one buffer (a row offset in dst, a column offset in dstT).
+ *   tile_table    n_tiles records {int32 record, int32 tile}: tile t of a record covers rows [64 * (t / ceil(K / 64)), + 64) and
+ *                 columns [64 * (t % ceil(K / 64)), + 64) of its source; every tile of every record exactly once.
+ * Round to nearest even with the bits of torch's fp32 -> bf16 cast (a NaN becomes 0x7FC0).  16-byte accesses where a whole tile
+ * lies inside the matrix and the pointer and leading dimension allow them, element accesses otherwise: the stored value does not
+ * depend on the path.  Ordinary stores only; nothing outside the destinations is written, nothing is read back.  n_tiles == 0
+ * launches nothing.  MVG_E_BADARG for negative counts, NULL or unaligned tables. */
+int mvg_refresh_operands(const void* record_table, int n_records, const void* tile_table, int n_tiles, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -67,6 +67,7 @@ SIGNATURES = {
     "mvg_criterion": [_vp] * 10 + [_i] + [_vp] * 4 + [_f] * 3 + [_i] * 7 + [_vp, C.c_size_t] + [_vp] * 5,
     "mvg_optim_workspace": [_i],
     "mvg_optim_step": [_vp, _i, _vp, _i, _vp, _i, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _f, _i, _vp, _vp],
+    "mvg_refresh_operands": [_vp, _i, _vp, _i, _vp],
 }
 
 _lib = None

@@ -118,11 +118,14 @@ class DecoderHead(nn.Module):
         self.criterion, self.decay_method = criterion, decay_method
         return self
 
-    def forward_train(self, src_views, meta, spatial_shapes=None, level_start_index=None, threshold=0.1):
+    def forward_train(self, src_views, meta, spatial_shapes=None, level_start_index=None, threshold=0.1, context=None):
         """One training forward for gt_match: True (dq_transformer.py:478-731): initial reference points, ground-truth match on
         them (one launch), the decoder under autograd with the matched mask as its triangulation filter, the out dict, and the
         losses of all layers from the fused criterion.  meta[0] holds joints_3d, joints_3d_vis, num_person and every meta[v]
-        its joints_vis, on the device.  Returns (out, loss_dict); total_loss(loss_dict, weight_dict).backward() is the step."""
+        its joints_vis, on the device.  Returns (out, loss_dict); total_loss(loss_dict, weight_dict).backward() is the step.
+        context: a DecoderContext.prepare(...)d context that the caller keeps (training.GraphedTrainStep); the host-side camera
+        packing, its H2D copy and the upload of the initial reference points then happen once, not per call, and the forward can
+        be captured in a HIP graph.  None: a context per call, as before."""
         from .decoder import DecoderContext
         if self.criterion is None:
             raise RuntimeError("DecoderHead.forward_train: no criterion (set_criterion / factory.build_training_head)")
@@ -134,11 +137,17 @@ class DecoderHead(nn.Module):
         if spatial_shapes is None:
             spatial_shapes, level_start_index = level_tables(src_views)
         query_pos, tgt = person_joint_queries(self.joint_embedding.weight, self.instance_embedding.weight, batch)
-        ref = sample_space_reference_points(self.num_instance, self.space_size, self.space_center, batch, dev,
-                                            t_pose=self.t_pose)
-        pairs = self.criterion.matcher.match(ref, meta)
         layer0 = self.decoder.layers[0]
-        ctx = DecoderContext.prepare(spatial_shapes, level_start_index, meta, layer0.img_size, layer0.compute_dtype, batch, dev)
+        ctx = context
+        if ctx is None:
+            ctx = DecoderContext.prepare(spatial_shapes, level_start_index, meta, layer0.img_size, layer0.compute_dtype, batch, dev)
+        ref = getattr(ctx, "_train_ref", None) if context is not None else None
+        if ref is None or ref.shape[0] != batch or ref.device != dev:
+            ref = sample_space_reference_points(self.num_instance, self.space_size, self.space_center, batch, dev,
+                                                t_pose=self.t_pose)
+            if context is not None:
+                ctx._train_ref = ref        # a function of the head's constants alone; nobody writes to it
+        pairs = self.criterion.matcher.match(ref, meta)
         hs, refs, refs2d, projs2d, classes = self.decoder(
             tgt.contiguous(), ref, src_views, meta, spatial_shapes, level_start_index, None,
             query_pos=query_pos.contiguous(), indices=pairs[3], threshold=threshold, context=ctx)

@@ -482,6 +482,19 @@ class DQDecoderLayer(MvPDecoderLayer):
         from .functions import linear_bf16
         return linear_bf16(x, weight, bias, self._wc, "train16/%x" % id(weight), relu=relu)
 
+    def _img_size_on(self, dev):
+        """(2,) f32 image size on `dev`: uploaded once per device (an H2D copy from pageable memory synchronises, and cannot be part
+        of a graph capture)"""
+        held = self.__dict__.setdefault("_img_dev", {})
+        key = (dev, tuple(float(v) for v in self.img_size))     # a reassigned img_size gets its own upload
+        t = held.get(key)
+        if t is None:
+            if dev.type == "cuda" and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("DQDecoderLayer.forward_autograd: first call on %s inside a HIP-graph capture; run one eager "
+                                   "training forward before capturing" % (dev,))
+            t = held[key] = torch.tensor(self.img_size, dtype=torch.float32, device=dev)
+        return t
+
     def forward_autograd(self, tgt, query_pos, reference_points, src_views, src_spatial_shapes, level_start_index, meta,
                          indices=None, threshold=0.5):
         """Training path: the same layer as differentiable torch ops (fp32) with the HIP sampling op
@@ -512,7 +525,7 @@ class DQDecoderLayer(MvPDecoderLayer):
         NQ = Lq // J
         V = len(meta)
         dev = tgt.device
-        img = torch.tensor(self.img_size, dtype=torch.float32, device=dev)
+        img = self._img_size_on(dev)
         X = reference_points.reshape(B, Lq, 3)
         if self.detach_refpoints_cameraprj:
             X = X.detach()                                                    # dq_decoder.py:338-339

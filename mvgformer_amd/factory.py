@@ -118,6 +118,26 @@ def build_optimizer_from_cfg(head, cfg, optim_type=None, weight_decay=1e-4, lr=N
                      clip_max_norm=clip, zero_grad=True)
 
 
+def build_graphed_train_step(head, optimizer, case_or_shapes, weight_dict=None, threshold=0.1, capture=True, warmup=3):
+    """training.GraphedTrainStep for `head` under `optimizer` (a FusedAdam with zero_grad=True, build_optimizer_from_cfg's): the
+    whole step -- forward_train, total_loss, backward, optimizer step -- as one HIP graph.  case_or_shapes: anything with
+    src_views, meta, spatial_shapes, level_start_index on the device and the ground truth in its meta (a synthetic case after
+    case_to_device + add_ground_truth, or a namespace holding one real batch): it gives the shapes and the first batch.
+    weight_dict: the criterion's by default.  With the decoder in bf16 training (set_training_dtype) a training.TrainOperands is
+    built and attached to the optimizer unless one is attached already.  capture=True runs GraphedTrainStep.capture(warmup): its
+    `warmup` warm-up steps are real optimizer steps on this first batch -- parameters, moments and step count move."""
+    from .training import GraphedTrainStep, TrainOperands
+    c = case_or_shapes
+    weight_dict = head.criterion.weight_dict if weight_dict is None else weight_dict
+    operands = optimizer.operands
+    if operands is None and any(l.training_dtype == torch.bfloat16 for l in head.decoder.layers):
+        operands = TrainOperands(head)
+        optimizer.attach_operands(operands)
+    step = GraphedTrainStep(head, optimizer, weight_dict, c.src_views, c.meta, getattr(c, "spatial_shapes", None),
+                            getattr(c, "level_start_index", None), threshold=threshold, operands=operands)
+    return step.capture(warmup) if capture else step
+
+
 def build_decoder_for_case(case, device="cuda", dtype=torch.float32):
     """Decoder with the panoptic hyper-parameters and the case's seeded weights."""
     layer = DQDecoderLayer(list(case.space_size), list(case.space_center), list(case.img_size), 3,

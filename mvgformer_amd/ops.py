@@ -1019,3 +1019,23 @@ def optim_step(tensor_table, chunk_table, group_table, state, workspace, loss=No
                                    L.ptr(group_table), group_table.shape[0], L.ptr(state), state.numel() * 8, L.ptr(workspace),
                                    workspace.numel() * 8, L.ptr(loss), float(max_norm), int(bool(zero_grad)), L.ptr(norm_out),
                                    L.stream_ptr()), "mvg_optim_step")
+
+
+# ---- derived bf16 operands of the bf16 training path (csrc/operands.hip) ---------------------------------------------------------
+OPERANDS_TILE = 64                 # MVG_OPERANDS_TILE
+OPERANDS_RECORD_WORDS = 8          # MVG_OPERANDS_RECORD_WORDS
+
+
+def refresh_operands(record_table, tile_table):
+    """bf16 copy and / or transposed bf16 copy of every fp32 matrix of the tables in one launch on the current stream
+    (mvg_refresh_operands; the table layouts are in include/mvg_decoder.h): record_table (n_records, 8) int64, tile_table
+    (n_tiles, 2) int32, both on the device.  Writes the destinations the records point to; nothing is read back."""
+    L.require_cuda(record_table, tile_table)
+    if (record_table.dtype != torch.int64 or record_table.dim() != 2 or record_table.shape[1] != OPERANDS_RECORD_WORDS
+            or tile_table.dtype != torch.int32 or tile_table.dim() != 2 or tile_table.shape[1] != 2
+            or not record_table.is_contiguous() or not tile_table.is_contiguous()):
+        raise RuntimeError("mvg_refresh_operands: tables (n, 8) int64 / (n, 2) int32, contiguous, expected")
+    lib = L.load()
+    with _timed("refresh_operands"):
+        L.check(lib.mvg_refresh_operands(L.ptr(record_table), record_table.shape[0], L.ptr(tile_table), tile_table.shape[0],
+                                         L.stream_ptr()), "mvg_refresh_operands")

@@ -68,6 +68,7 @@ class FusedAdam(torch.optim.Optimizer):
         self._step_host = 0           # the count while there is no state block yet (before the first step / after a load)
         self._tables = None           # (signature, tensor_table, chunk_table, workspace, updated parameters)
         self._groups_dev, self._groups_host = None, None
+        self._operands = None         # attach_operands
         defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay,
                         decoupled_weight_decay=bool(decoupled_weight_decay), **_TORCH_ADAM_KEYS)
         super().__init__(params, defaults)
@@ -84,7 +85,7 @@ class FusedAdam(torch.optim.Optimizer):
     def __setstate__(self, state):
         super().__setstate__(state)
         for k, v in (("_state_dev", None), ("_step_host", 0), ("_tables", None), ("_groups_dev", None), ("_groups_host", None),
-                     ("clip_max_norm", 0.0), ("zero_grad_after_step", False)):
+                     ("_operands", None), ("clip_max_norm", 0.0), ("zero_grad_after_step", False)):
             self.__dict__.setdefault(k, v)
         for group in self.param_groups:
             for k, v in _TORCH_ADAM_KEYS.items():
@@ -248,10 +249,26 @@ class FusedAdam(torch.optim.Optimizer):
             self._sync_tables(dev)
         return self
 
+    def attach_operands(self, operands):
+        """operands: a training.TrainOperands (or None to detach) -- the bf16 copies of the weights that the bf16 training path
+        multiplies by, kept on the device.  step() then launches their refresh right behind the update kernel (one more launch,
+        also inside a captured graph) and re-stamps them after its version bump, so the next forward neither re-casts the
+        weights on the host's order nor reads last step's copies."""
+        self._operands = operands
+        return self
+
+    @property
+    def operands(self):
+        """the attached training.TrainOperands, or None"""
+        return self._operands
+
     def mark_updated(self):
-        """bump the version counters of the parameters the tables cover (after graph replays: a replay runs no host code)"""
+        """bump the version counters of the parameters the tables cover (after graph replays: a replay runs no host code); attached
+        operands were refreshed by the replayed step and are re-stamped for the new versions"""
         if self._tables is not None and self._tables[4]:
             torch.autograd.graph.increment_version(self._tables[4])
+        if self._operands is not None:
+            self._operands.restamp()
 
     @torch.no_grad()
     def step(self, loss=None, closure=None):
@@ -272,7 +289,11 @@ class FusedAdam(torch.optim.Optimizer):
             norm = torch.empty((), dtype=torch.float32, device=dev)
             ops.optim_step(tensor_table, chunk_table, self._groups_dev, self._state_dev, workspace, loss=loss,
                            max_norm=self.clip_max_norm, zero_grad=self.zero_grad_after_step, norm_out=norm)
+            if self._operands is not None:
+                self._operands.launch()     # unconditionally too: the refresh is idempotent, a skipped step rewrites the same bits
         # unconditionally: the host cannot know whether the device skipped the step
         if params:
             torch.autograd.graph.increment_version(params)
+        if self._operands is not None:
+            self._operands.restamp()
         return norm

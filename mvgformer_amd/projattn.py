@@ -43,10 +43,37 @@ class WeightCache:
 
     def __init__(self):
         self._store = {}
+        self._adopted = {}      # key -> (params, dtype, tensor): entries somebody else keeps up to date (adopt)
+
+    def __deepcopy__(self, memo):
+        """adopted entries do not travel with a copy: the buffer belongs to whoever maintains it for the ORIGINAL's parameters (a
+        graph may address it); everything else is copied as before"""
+        import copy
+        new = WeightCache()
+        new._store = copy.deepcopy({k: v for k, v in self._store.items() if k not in self._adopted}, memo)
+        return new
+
+    def adopt(self, key, params, dtype, tensor):
+        """Hand the cache a persistent tensor for `key`, current for `params` as they are now: get() returns THIS tensor while the
+        stamp holds.  Whoever rewrites it on the device after the parameters changed (training.TrainOperands, behind the optimizer's
+        update kernel) calls restamp().  If the stamp is found stale all the same (a checkpoint load, another optimizer), get()
+        rebuilds the entry as usual but INTO the adopted tensor, so its address -- which a captured graph may hold -- stays."""
+        params = tuple(params)
+        self._adopted[key] = (params, dtype, tensor)
+        self._store[key] = (self._stamp(params, dtype), tensor)
+
+    def restamp(self):
+        """the adopted entries are current for their parameters' present versions"""
+        for key, (params, dtype, tensor) in self._adopted.items():
+            self._store[key] = (self._stamp(params, dtype), tensor)
+
+    @staticmethod
+    def _stamp(params, dtype):
+        return tuple((id(p), p._version, p.device) for p in params) + (dtype,)
 
     def get(self, key, params, dtype, build=None, sync=True):
         """sync=False: the entry is only read on the stream that builds it (the training path), no wait for the build"""
-        stamp = tuple((id(p), p._version, p.device) for p in params) + (dtype,)
+        stamp = self._stamp(params, dtype)
         hit = self._store.get(key)
         if hit is not None and hit[0] == stamp:
             return hit[1]
@@ -63,6 +90,14 @@ class WeightCache:
             if isinstance(t, tuple):      # (tensor, host-side scalars ...): e.g. an operand and its power-of-two scale
                 t, extra = t[0], tuple(t[1:])
             t = t.detach().to(dtype).contiguous()
+            mine = self._adopted.get(key)
+            if mine is not None:
+                if (len(mine[0]) == len(params) and all(a is b for a, b in zip(mine[0], params)) and mine[1] == dtype
+                        and mine[2].shape == t.shape and mine[2].device == t.device):
+                    mine[2].copy_(t)
+                    t = mine[2]
+                else:           # other parameters, dtype or shape under this key: the adoption is over
+                    del self._adopted[key]
         # An entry is built on whatever stream is current and then handed out to every stream (the decoder issues
         # query-independent work on a side stream): finish the build before anybody can see the entry.  Rare (first
         # use / parameters changed).
@@ -445,7 +480,8 @@ class ProjAttn(nn.Module):
             input_flatten = packed
         else:
             input_flatten = torch.cat([s.flatten(2) for s in src_views], dim=-1).permute(0, 2, 1)
-        assert int((input_spatial_shapes[:, 0] * input_spatial_shapes[:, 1]).sum()) == input_flatten.shape[1]
+        # (from the host copy of the level table, kept on the tensor object: no D2H read per forward, none inside a graph capture)
+        assert sum(h * w for h, w in ops_host_levels_pair(input_spatial_shapes, input_level_start_index)[0]) == input_flatten.shape[1]
         xin = None
         if (self.ref_gather_native and (input_flatten.dtype == torch.float32 or bf) and not input_flatten.requires_grad
                 and not reference_points.requires_grad and c % 4 == 0):

@@ -1,12 +1,16 @@
 """Time of one training step of the decoder at cfg-2 size: forward under autograd (torch geometry +
 ProjAttn with the HIP sampling forward / backward kernels) + backward to every parameter.  GPU only.
-python tools/train_step_probe.py [config] [steps] [fp32|bf16] [--criterion] [--optimizer fused|torch]
+python tools/train_step_probe.py [config] [steps] [fp32|bf16] [--criterion] [--optimizer fused|torch] [--graph]
 (bf16: DQDecoder.set_training_dtype(torch.bfloat16))
 --criterion: the real step -- DecoderHead.forward_train (ground-truth match, decoder with the matched mask, fused criterion) on
 synthetic ground truth (5 persons, K = 5) and total_loss(...).backward() -- instead of the made-up loss of the default run.
 --optimizer: the step includes the weight update (lr 4e-4, clip 0.1, the reference's two parameter groups).  torch: `if loss > 0`
 on the host, clip_grad_norm_ and torch.optim.Adam, gradients zeroed in place; fused: optim.FusedAdam.step(loss=loss), the guard
-on the device.  Without the option the step ends at backward() and drops the gradients, as before."""
+on the device.  Without the option the step ends at backward() and drops the gradients, as before.
+--graph (with --criterion --optimizer fused): the same step captured once as a HIP graph (training.GraphedTrainStep) and replayed,
+timed next to the eager step in the same process.  Three figures: the plain step of this script (a DecoderContext per call; a block
+of `steps` runs before the runner is built), runner.eager() (the identical step the graph holds: static context, bf16 operands kept by
+the device) and runner.replay(); the last two alternate, each figure is the median over `steps` rounds."""
 import os
 import sys
 import time
@@ -19,7 +23,8 @@ from mvgformer_amd.factory import build_decoder_for_case, case_to_device  # noqa
 from mvgformer_amd.synthetic import build_case  # noqa: E402
 
 with_criterion = "--criterion" in sys.argv
-argv = [a for a in sys.argv if a != "--criterion"]
+with_graph = "--graph" in sys.argv
+argv = [a for a in sys.argv if a not in ("--criterion", "--graph")]
 optimizer = None
 if "--optimizer" in argv:
     i = argv.index("--optimizer")
@@ -27,6 +32,8 @@ if "--optimizer" in argv:
     if optimizer not in ("fused", "torch"):
         raise SystemExit("--optimizer fused|torch")
     del argv[i:i + 2]
+if with_graph and not (with_criterion and optimizer == "fused"):
+    raise SystemExit("--graph needs --criterion --optimizer fused")
 cfg = argv[1] if len(argv) > 1 else "cfg2"
 steps = int(argv[2]) if len(argv) > 2 else 5
 tdt = argv[3] if len(argv) > 3 else "fp32"
@@ -93,6 +100,60 @@ def step():
     return loss
 
 
+def graph_run():
+    """eager step and replayed step alternating in one process: median times, device launches of one eager step, peak memory"""
+    import statistics
+    from mvgformer_amd.factory import build_graphed_train_step
+    def timed(fn):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t) * 1e3, out
+    for _ in range(2):
+        step()
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    # the plain step of this script (what the run without --graph times): a context per call -- host camera packing and its H2D
+    # copy --, in bf16 the weights cast by torch.  Before the runner exists: building it attaches the device-kept operands.
+    tp = [timed(step)[0] for _ in range(steps)]
+    peak_eager = torch.cuda.max_memory_allocated() / 2 ** 30
+    runner = build_graphed_train_step(head, opt, g, weight_dict)
+    torch.cuda.synchronize()
+    te, tr = [], []
+    for _ in range(steps):
+        ms, _ = timed(runner.eager)
+        te.append(ms)
+        ms, out = timed(runner.replay)
+        tr.append(ms)
+    peak_all = torch.cuda.max_memory_allocated() / 2 ** 30
+    from torch.autograd import DeviceType
+    with torch.profiler.profile(activities=[torch.profiler.ProfilerActivity.CPU, torch.profiler.ProfilerActivity.CUDA]) as prof:
+        runner.eager()
+        torch.cuda.synchronize()
+    events = list(prof.events())
+    host = {e.name for e in events if e.device_type == DeviceType.CPU}
+    launches = sum(1 for e in events if e.device_type == DeviceType.CUDA and e.name not in host)
+    total = out[0]
+    dev_ev = [e for e in events if e.device_type == DeviceType.CUDA and e.name not in host]
+    by_name = {}
+    for e in dev_ev:
+        n, t = by_name.get(e.name, (0, 0.0))
+        by_name[e.name] = (n + 1, t + e.time_range.elapsed_us())
+    busy = sum(t for _, t in by_name.values())
+    print("device time of one runner.eager() step: %.2f ms in %d launches; the largest:" % (busy / 1e3, len(dev_ev)))
+    for name, (n, t) in sorted(by_name.items(), key=lambda kv: -kv[1][1])[:8]:
+        print("  %8.3f ms  %4d x  %s" % (t / 1e3, n, name[:110]))
+    print("%s training step (%s, match + criterion + fused optimizer): plain step %.2f ms (context per call; median of %d in a block); "
+          "runner.eager() %.2f ms (static context, operands kept by the device), graph replay %.2f ms (medians of %d, alternating; "
+          "min %.2f / %.2f); %d device launches per runner.eager() step, 1 graph launch per replay; loss %.4f; peak memory %.2f GB "
+          "plain, %.2f GB with the graph's pool" % (cfg, tdt, statistics.median(tp), steps, statistics.median(te), statistics.median(tr),
+                                                   steps, min(te), min(tr), launches, float(total), peak_eager, peak_all))
+
+
+if with_graph:
+    graph_run()
+    sys.exit(0)
 for _ in range(2):
     step()
 torch.cuda.synchronize()
