@@ -521,7 +521,8 @@ __device__ __forceinline__ float add8(float v) {
 // exchange away (lane ^ M, in the A quad and in the V quad alike), a column update is then local to the two lanes of a
 // pair, a row update local to every lane.  The operations and their order per matrix element are those of jacobi_rotate2
 // (both angles from the matrix as the round finds it; rotation 1: columns, rows, V; rotation 2: columns, rows, V; roundings
-// pinned by rot_lo / rot_hi), so the result is the one-lane Jacobi's bit for bit (tests: knob tri_lanes) -- on 8 wavefronts
+// pinned by rot_lo / rot_hi), so the result is the one-lane Jacobi's bit for bit (as measured when it was built; no knob
+// selects it and no test runs it: triangulate_kernel<true> is not instantiated) -- on 8 wavefronts
 // instead of one, and a wavefront stops when its own 8 problems have converged.
 // MEASURED SLOWER and not the default: cfg-2 forward 1.279 -> 1.309 ms.  The one-lane form is 19 200 of the kernel's 32 900
 // cycles (s_memtime) at 8.5 cycles per dependent fp64 instruction, but only ~150 instructions per round for 64 problems; this
@@ -1155,6 +1156,26 @@ __global__ __launch_bounds__(1024) void bin_scatter_kernel(const unsigned* __res
   }
 }
 
+// jacobi_angle3 forms its angle in fp32: a matrix whose entries lie outside fp32's exponent range would give theta = 0/0 or Inf/Inf for
+// every pair and leave twelve sweeps without one rotation (diagonal returned as eigenvalues, identity as eigenvectors).  The callers
+// that take arbitrary matrices (sym4_eigh_kernel, dlt_decompose: any confidences) therefore scale by 2^-e first, e the exponent of
+// the largest |entry|.  A power of two is exact: for a matrix that was in range no bit of theta, c, s or of the eigenvectors
+// changes, and the eigenvalues are scaled back by 2^e.  Returns e (0 for the zero matrix or a largest entry that is not finite).
+__device__ __forceinline__ int sym4_normalise(double (&G)[4][4]) {
+  double m = 0.0;
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int c = a; c < 4; ++c) m = fmax(m, fabs(G[a][c]));
+  if (!(m > 0.0) || !(m <= 1.7976931348623157e308)) return 0;
+  const int e = ilogb(m);
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) G[a][c] = scalbn(G[a][c], -e);
+  return e;
+}
+
 // ---- batched eigen-decomposition of symmetric 4x4 matrices (fp64, cyclic Jacobi as in triangulate_kernel): the
 // differentiable DLT of the training path (geometry_torch.dlt) takes the eigenvector of the smallest eigenvalue of the
 // Gram matrix A^T A and needs all four pairs for its backward (rocSOLVER's batched SVD of the (2V, 4) row matrices was
@@ -1171,6 +1192,7 @@ __global__ __launch_bounds__(256) void sym4_eigh_kernel(const double* __restrict
       G[a][c] = 0.5 * (Gin[idx * 16 + a * 4 + c] + Gin[idx * 16 + c * 4 + a]);
       Vm[a][c] = (a == c) ? 1.0 : 0.0;
     }
+  const int ex = sym4_normalise(G);
   for (int sweep = 0; sweep < 12; ++sweep) {
     const double off = fabs(G[0][1]) + fabs(G[0][2]) + fabs(G[0][3]) + fabs(G[1][2]) + fabs(G[1][3]) + fabs(G[2][3]);
     const double lg = fmax(fmax(fabs(G[0][0]), fabs(G[1][1])), fmax(fabs(G[2][2]), fabs(G[3][3])));
@@ -1181,7 +1203,7 @@ __global__ __launch_bounds__(256) void sym4_eigh_kernel(const double* __restrict
   }
 #pragma unroll
   for (int a = 0; a < 4; ++a) {
-    evals[idx * 4 + a] = G[a][a];
+    evals[idx * 4 + a] = scalbn(G[a][a], ex);
 #pragma unroll
     for (int c = 0; c < 4; ++c) evecs[idx * 16 + a * 4 + c] = Vm[a][c];
   }
@@ -1291,6 +1313,7 @@ __device__ __forceinline__ void dlt_decompose(const float* __restrict__ ud, cons
   for (int a = 0; a < 4; ++a)
 #pragma unroll
     for (int e = 0; e < a; ++e) G[a][e] = G[e][a];
+  const int ex = sym4_normalise(G);
   for (int sweep = 0; sweep < 12; ++sweep) {
     const double off = fabs(G[0][1]) + fabs(G[0][2]) + fabs(G[0][3]) + fabs(G[1][2]) + fabs(G[1][3]) + fabs(G[2][3]);
     const double lg = fmax(fmax(fabs(G[0][0]), fabs(G[1][1])), fmax(fabs(G[2][2]), fabs(G[3][3])));
@@ -1302,7 +1325,7 @@ __device__ __forceinline__ void dlt_decompose(const float* __restrict__ ud, cons
   E.k = 0;
 #pragma unroll
   for (int a = 0; a < 4; ++a) {
-    E.w[a] = G[a][a];
+    E.w[a] = scalbn(G[a][a], ex);
     if (a > 0 && E.w[a] < E.w[E.k]) E.k = a;
   }
 }
