@@ -475,6 +475,42 @@ int mvg_optim_step(const void* tensor_table, int n_tensors, const void* chunk_ta
  * launches nothing.  MVG_E_BADARG for negative counts, NULL or unaligned tables. */
 int mvg_refresh_operands(const void* record_table, int n_records, const void* tile_table, int n_tiles, void* stream);
 
+/* ---- serving post-processing (csrc/nms.hip) -------------------------------------------------------------------------------- */
+#define MVG_NMS_MAX_N 2048            /* candidates rows per batch element                                                    */
+#define MVG_NMS_MAX_J 32
+
+/* bytes of the (8-byte aligned) workspace of mvg_pose_nms: per batch element the candidate count, rank -> row, the fp64 distance
+ * limits and the N x ceil(N / 64) 64-bit words of the closeness matrix.  Monotone in N; 0 for shapes mvg_pose_nms rejects. */
+size_t mvg_pose_nms_workspace(int B, int N, int J);
+
+/* Classification filter + nearby-joints NMS of the packed predictions (run/validate_3d.py:228-234, lib/core/nms.py:210-283) for
+ * the whole batch in THREE launches (rank, closeness bit matrix, greedy pass + gather), fixed shapes, nothing read back by the
+ * host, no floating-point atomics, bit-reproducible: it can be captured in the HIP graph of the decoder forward.
+ *   pred (B, N, J, 5) fp32 contiguous, rows [x, y, z, flag, score]; every batch element on its own.
+ *   Candidates: row n iff pred[b, n, 0, 3] >= 0 (the flag as given, the threshold compare is not redone); score pred[b, n, 0, 4].
+ *   limit_a = sqrt(sum_c (max_j k[a,j,c] - min_j k[a,j,c])^2) * dist_thr and
+ *   close[a, c] = #{ j : sqrt((dx^2 + dy^2) + dz^2) < limit_a } > num_nearby_joints_thr in fp64 from the fp32 inputs, every
+ *   multiply and add rounded on its own, correctly rounded sqrt: numpy's arithmetic, so the matrix is the reference's bit for bit
+ *   (not symmetric: the limit belongs to the row pose; a NaN coordinate gives a NaN limit as np.max / np.min do).
+ *   Greedy pass in visiting order = descending score, among equal scores the HIGHER row first
+ *   (np.argsort(scores, kind="stable")[::-1]; the reference's default argsort is unstable, its order among tied scores is
+ *   unspecified and coincides with this rule where numpy falls back to insertion sort, N <= 16): a candidate that is already
+ *   ignored is skipped; best = the member of its row with the highest score, among equal scores the LOWEST row (np.argmax); if
+ *   best is not ignored it is appended to the keep list and the whole row is ignored from then on.  A candidate whose own row is
+ *   empty (zero extent: 0 < 0 is false; a NaN limit) is visited, counted in count[b, 1] and keeps / suppresses nothing (the
+ *   reference raises inside np.argmax there).
+ *   max_dets > 0 and more poses kept: the max_dets best scored kept poses in descending score, among equal scores the later keep
+ *   position first (np.argsort(scores[keep], kind="stable")[-1:-max_dets-1:-1]).
+ * Outputs: keep (B, N) int32 kept row indices in keep order, -1 behind the count; count (B, 2) int32 [kept, candidates skipped
+ * for an empty neighbourhood]; dets (B, dets_rows, J, 5) fp32 or NULL: the kept rows gathered in keep order (the first dets_rows
+ * of them), rows behind the count are 0 with flag -1.  Every element of keep, count and dets is written by every call; of the
+ * workspace only what the same call wrote is read.  stream: a hipStream_t.
+ * MVG_E_BADARG, and nothing launched, for dist_thr <= 0 (or NaN), num_nearby_joints_thr < 0 or >= J, J > MVG_NMS_MAX_J,
+ * N > MVG_NMS_MAX_N, B or N or J < 1, dets_rows < 1 or > MVG_NMS_MAX_N with dets given, a NULL pred / keep / count, a NULL,
+ * unaligned or too small workspace. */
+int mvg_pose_nms(const float* pred, int B, int N, int J, double dist_thr, int num_nearby_joints_thr, int max_dets, void* workspace,
+                 size_t workspace_bytes, int* keep, int* count, float* dets, int dets_rows, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

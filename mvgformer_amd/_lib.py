@@ -68,6 +68,8 @@ SIGNATURES = {
     "mvg_optim_workspace": [_i],
     "mvg_optim_step": [_vp, _i, _vp, _i, _vp, _i, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _f, _i, _vp, _vp],
     "mvg_refresh_operands": [_vp, _i, _vp, _i, _vp],
+    "mvg_pose_nms_workspace": [_i] * 3,
+    "mvg_pose_nms": [_vp, _i, _i, _i, C.c_double, _i, _i, _vp, C.c_size_t, _vp, _vp, _vp, _i, _vp],
 }
 
 _lib = None
@@ -98,6 +100,7 @@ def load():
     lib.mvg_knn_match_workspace.restype = C.c_size_t
     lib.mvg_criterion_workspace.restype = C.c_size_t
     lib.mvg_optim_workspace.restype = C.c_size_t
+    lib.mvg_pose_nms_workspace.restype = C.c_size_t
     lib.mvg_version.argtypes = []
     # every knob change goes through this wrapper, so that host-side caches that depend on a knob (DQDecoderLayer's rows of
     # all-masked tiles: computed by the GEMM form that is active) can key on its value: TUNING[key] = last value set

@@ -17,12 +17,13 @@ tests/test_evaluate.py against golden vectors produced by the reference's own fu
 """
 from __future__ import annotations
 
+import contextlib
 from collections import OrderedDict
 
 import numpy as np
 import torch
 
-__all__ = ["nearby_joints_nms", "filter_and_nms", "match_predictions", "eval_list_to_ap", "eval_list_to_mpjpe",
+__all__ = ["nearby_joints_nms", "filter_and_nms", "filter_and_nms_device", "match_predictions", "eval_list_to_ap", "eval_list_to_mpjpe",
            "eval_list_to_recall", "evaluate_panoptic", "evaluate_pcp", "MPJPE_THRESHOLDS", "PCP_LIMBS"]
 
 MPJPE_THRESHOLDS = tuple(range(25, 155, 25))            # panoptic.py:559
@@ -91,6 +92,26 @@ def filter_and_nms(pred, dist_thr=0.3, num_nearby_joints_thr=7):
     pred = pred[keep_cls]
     idx = nearby_joints_nms(pred, dist_thr, num_nearby_joints_thr)
     return pred[idx]
+
+
+def filter_and_nms_device(pred, dist_thr=0.3, num_nearby_joints_thr=7, max_dets=-1):
+    """``filter_and_nms`` as one device operator (``ops.pose_nms``: classification filter, closeness matrix and the greedy pass
+    in three launches, no N x N matrix on the host, no Python loop).  pred (N, J, 5) or (B, N, J, 5) fp32 on the device;
+    returns the surviving rows in keep order, as a list over the batch when batched.  One read-back for the whole batch: the
+    kept counts; the rows are slices of the gathered ``dets``.
+    Same arithmetic as ``nearby_joints_nms`` (numpy's fp64).  Candidates are visited in descending score and, among EQUAL scores,
+    the higher row first (``np.argsort(scores, kind="stable")[::-1]``): the reference's default argsort is unstable, so its order
+    among tied scores is unspecified; it coincides with this rule where numpy falls back to insertion sort (N <= 16).  A
+    candidate whose own neighbourhood is empty (zero-extent pose, NaN coordinate) is ignored, where ``nearby_joints_nms`` raises
+    inside ``np.argmax`` like the reference."""
+    from . import ops
+    batched = pred.dim() == 4
+    p = (pred if batched else pred[None]).contiguous()
+    with torch.cuda.device(p.device) if p.is_cuda else contextlib.nullcontext():
+        _, count, dets = ops.pose_nms(p, dist_thr, num_nearby_joints_thr, max_dets)
+    kept = count[:, 0].tolist()                                                       # the one read-back
+    rows = [dets[b, :k] for b, k in enumerate(kept)]
+    return rows if batched else rows[0]
 
 
 # --------------------------------------------------------------------------------------- AP / MPJPE / recall

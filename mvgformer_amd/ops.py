@@ -1039,3 +1039,62 @@ def refresh_operands(record_table, tile_table):
     with _timed("refresh_operands"):
         L.check(lib.mvg_refresh_operands(L.ptr(record_table), record_table.shape[0], L.ptr(tile_table), tile_table.shape[0],
                                          L.stream_ptr()), "mvg_refresh_operands")
+
+
+NMS_MAX_N = 2048                   # MVG_NMS_MAX_N
+NMS_MAX_J = 32                     # MVG_NMS_MAX_J
+
+
+def pose_nms_buffers(B, N, J, dets_rows=None, device="cuda"):
+    """the static buffers of pose_nms(out=...): keep (B, N) int32, count (B, 2) int32, dets (B, dets_rows, J, 5) fp32 and the
+    workspace.  A caller that captures pose_nms in a HIP graph allocates them once and keeps them alive with the graph."""
+    rows = N if dets_rows is None else int(dets_rows)
+    nbytes = L.load().mvg_pose_nms_workspace(B, N, J)
+    if nbytes == 0 or rows < 1:
+        raise L.MvgError("mvg_pose_nms: unsupported shape B = %d, N = %d (<= %d), J = %d (<= %d), dets_rows = %d"
+                         % (B, N, NMS_MAX_N, J, NMS_MAX_J, rows))
+    return dict(keep=torch.empty((B, N), dtype=torch.int32, device=device),
+                count=torch.empty((B, 2), dtype=torch.int32, device=device),
+                dets=torch.empty((B, rows, J, 5), dtype=torch.float32, device=device),
+                workspace=torch.empty((nbytes,), dtype=torch.uint8, device=device))
+
+
+def pose_nms(pred, dist_thr=0.3, num_nearby_joints_thr=7, max_dets=-1, dets_rows=None, out=None):
+    """Classification filter + nearby-joints NMS on the device (mvg_pose_nms: three launches, nothing read back, no
+    synchronisation; validate_3d.py:228-234, lib/core/nms.py:210-283).  pred (B, N, J, 5) fp32 contiguous, rows
+    [x, y, z, flag, score] as written by caller.pack_predictions; row n is a candidate iff pred[b, n, 0, 3] >= 0.
+    -> keep (B, N) int32: kept row indices in keep order, -1 behind the count; count (B, 2) int32: [kept, candidates skipped for an
+    empty neighbourhood]; dets (B, dets_rows, J, 5): the kept rows in keep order, rows behind the count are 0 with flag -1.
+    The arithmetic is numpy's fp64 (the closeness matrix is the reference's bit for bit).  Candidates are visited in descending
+    score and, among equal scores, the higher row first (np.argsort(scores, kind="stable")[::-1]); the reference's unstable
+    default argsort leaves the order among tied scores unspecified and coincides with this rule for N <= 16.  A candidate whose
+    own neighbourhood is empty (zero extent, NaN coordinate) is counted in count[:, 1] and otherwise ignored, where the reference
+    raises.  num_nearby_joints_thr None = J // 2.  out: the dict of pose_nms_buffers (static buffers for graph capture); None
+    allocates per call."""
+    if not dist_thr > 0:
+        raise AssertionError("`dist_thr` must be greater than 0.")                   # nms.py:233
+    if pred.dim() != 4 or pred.shape[-1] != 5 or pred.dtype != torch.float32:
+        raise RuntimeError("mvg_pose_nms: pred (B, N, J, 5) float32 expected")
+    B, N, J = pred.shape[:3]
+    if num_nearby_joints_thr is None:
+        num_nearby_joints_thr = J // 2
+    if not num_nearby_joints_thr < J:
+        raise AssertionError("`num_nearby_joints_thr` must be less than the number of joints.")
+    L.require_cuda(pred)
+    if not pred.is_contiguous():
+        raise RuntimeError("mvg_pose_nms: pred must be contiguous")
+    if out is None:
+        out = pose_nms_buffers(B, N, J, dets_rows, pred.device)
+    keep, count, dets, ws = out["keep"], out["count"], out["dets"], out["workspace"]
+    L.require_cuda(keep, count, dets, ws)
+    if (keep.dtype != torch.int32 or tuple(keep.shape) != (B, N) or count.dtype != torch.int32 or tuple(count.shape) != (B, 2)
+            or dets.dtype != torch.float32 or dets.dim() != 4 or dets.shape[0] != B or tuple(dets.shape[2:]) != (J, 5)
+            or (dets_rows is not None and dets.shape[1] != dets_rows)
+            or not (keep.is_contiguous() and count.is_contiguous() and dets.is_contiguous() and ws.is_contiguous())):
+        raise RuntimeError("mvg_pose_nms: out buffers do not fit pred %s (see pose_nms_buffers)" % (tuple(pred.shape),))
+    lib = L.load()
+    with _timed("pose_nms"):
+        L.check(lib.mvg_pose_nms(L.ptr(pred), B, N, J, float(dist_thr), int(num_nearby_joints_thr), int(max_dets), L.ptr(ws),
+                                 ws.numel() * ws.element_size(), L.ptr(keep), L.ptr(count), L.ptr(dets), dets.shape[1],
+                                 L.stream_ptr()), "mvg_pose_nms")
+    return keep, count, dets

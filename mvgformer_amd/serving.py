@@ -19,6 +19,17 @@ Static per runner: the cameras (``meta``; call ``set_cameras`` when they change 
 re-capture), map shapes, batch, query count, threshold and the decoder's weights (``refresh_weights()`` after an optimizer step
 or a checkpoint load re-captures).  A backbone that writes its deconvolution outputs into ``runner.pyramid_views`` (channels-last,
 compute dtype) makes ``load(src_views=...)`` unnecessary.
+
+``postprocess=dict(dist_thr=0.3, num_nearby_joints_thr=7, max_dets=-1, dets_rows=None)`` continues the captured region behind the
+decoder: ``caller.decoder_outputs_to_dict`` -> ``caller.pack_predictions`` (torch ops) -> ``ops.pose_nms`` (classification filter +
+nearby-joints NMS, three launches, no synchronisation) into static buffers.  ``replay()`` still returns the five decoder outputs;
+``runner.pred`` is the packed predictions (B, NQ, J, 5) and ``runner.detections`` = ``(dets, count, keep)``: the kept rows in keep
+order, ``count[b] = [kept, skipped]`` and the kept row indices -- static tensors, overwritten by the next replay:
+
+        runner.replay()
+        dets, count, keep = runner.detections
+        n = int(count[0, 0])                # the frame's one read-back
+        poses = dets[0, :n]                 # (n, J, 5) on the device
 """
 from __future__ import annotations
 
@@ -29,7 +40,7 @@ from .decoder import DecoderContext
 
 class GraphedDecoder:
     def __init__(self, decoder, meta, spatial_shapes, level_start_index, batch, num_queries, threshold=0.1, device=None,
-                 producer_writes_in_place=False, channels=256):
+                 producer_writes_in_place=False, channels=256, postprocess=None, convert_joint_format_indices=None):
         layer0 = decoder.layers[0]
         dev = torch.device(device) if device is not None else next(decoder.parameters()).device
         if dev.type != "cuda":
@@ -57,6 +68,20 @@ class GraphedDecoder:
             self.pyramid_views = None
         self.graph, self.outputs = None, None
         self._pinned, self._captured_ptrs = [], None
+        # optional device-side post-processing behind the decoder (classification filter + NMS), inside the same graph
+        self.NQ, self.J = num_queries, J
+        self.convert_joint_format_indices = convert_joint_format_indices
+        self.postprocess, self._nms, self.pred, self._graph_pred, self.detections = None, None, None, None, None
+        if postprocess is not None:
+            from . import ops
+            unknown = set(postprocess) - {"dist_thr", "num_nearby_joints_thr", "max_dets", "dets_rows"}
+            if unknown:
+                raise TypeError("GraphedDecoder: unknown postprocess keys %s" % sorted(unknown))
+            self.postprocess = dict(dist_thr=0.3, num_nearby_joints_thr=7, max_dets=-1, dets_rows=None)
+            self.postprocess.update(postprocess)
+            j_out = J if convert_joint_format_indices is None else len(convert_joint_format_indices)
+            self._nms = ops.pose_nms_buffers(batch, num_queries, j_out, self.postprocess["dets_rows"], dev)
+            self.detections = (self._nms["dets"], self._nms["count"], self._nms["keep"])
 
     # ------------------------------------------------------------------ inputs (device-side copies on the current stream)
     def load(self, src_views=None, tgt=None, query_pos=None, reference_points=None):
@@ -84,8 +109,15 @@ class GraphedDecoder:
     # ------------------------------------------------------------------ capture / replay
     def _forward(self):
         self.ctx.feat = None          # re-packed from the static source buffers (a no-op for levels produced in place)
-        return self.dec(self.tgt, self.reference_points, self.src_views, self.meta, self.spatial_shapes, self.level_start_index,
-                        None, query_pos=self.query_pos, threshold=self.thr, context=self.ctx)
+        outputs = self.dec(self.tgt, self.reference_points, self.src_views, self.meta, self.spatial_shapes, self.level_start_index,
+                           None, query_pos=self.query_pos, threshold=self.thr, context=self.ctx)
+        if self.postprocess is not None:
+            from . import caller, ops
+            out = caller.decoder_outputs_to_dict(*outputs, self.NQ, self.J, self.convert_joint_format_indices)
+            self.pred = caller.pack_predictions(out, self.thr)                       # function.py:386-396
+            pp = self.postprocess
+            ops.pose_nms(self.pred, pp["dist_thr"], pp["num_nearby_joints_thr"], pp["max_dets"], pp["dets_rows"], out=self._nms)
+        return outputs
 
     def capture(self, warmup=2):
         with torch.no_grad():
@@ -95,6 +127,7 @@ class GraphedDecoder:
             self.graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.graph):
                 self.outputs = self._forward()
+        self._graph_pred = self.pred            # allocated from the graph's pool: static, like the outputs
         # everything the graph addresses by raw pointer and does not own: the per-layer pyramid products and the cached operands
         self._pinned = self._graph_operands()
         self._captured_ptrs = self._buffer_ptrs()
@@ -106,6 +139,8 @@ class GraphedDecoder:
 
     def _graph_operands(self):
         keep = [self.ctx.cams, self.ctx.feat, getattr(self.ctx, "_buffer", None)]
+        if self._nms is not None:
+            keep += list(self._nms.values())
         for l in self.dec.layers:
             keep += [l.proj_attn._vp, l.proj_attn._G]
             for wc in (l._wc, l.proj_attn._wc):
@@ -124,9 +159,11 @@ class GraphedDecoder:
             # re-allocated): the old graph is still safe to replay (its buffers are pinned) but no longer the decoder's state
             self.capture()
         self.graph.replay()
+        self.pred = self._graph_pred
         return self.outputs
 
     def eager(self):
-        """the same forward without the graph (reference for tests; identical results)"""
+        """the same forward without the graph (reference for tests; identical results).  With ``postprocess`` it takes the same
+        path as the capture: ``pred`` is this call's packed predictions, ``detections`` the same static buffers."""
         with torch.no_grad():
             return self._forward()

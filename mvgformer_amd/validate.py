@@ -111,6 +111,9 @@ def main(argv=None):
     ap.add_argument("--pred-out", default=None, help="save the packed predictions per threshold (TEST.PRED_FILE)")
     ap.add_argument("--graph", type=int, default=1, help="1: the decoder forward captured once as a HIP graph and replayed per "
                                                          "frame (mvgformer_amd.serving.GraphedDecoder); 0: eager launches")
+    ap.add_argument("--device-nms", type=int, default=0, choices=[0, 1],
+                    help="1: classification filter + NMS as one device operator (ops.pose_nms), inside the HIP graph with --graph 1 "
+                         "(one count read-back per frame); 0: evaluate.filter_and_nms (host greedy loop)")
     args = ap.parse_args(argv)
 
     from . import evaluate as E
@@ -122,7 +125,7 @@ def main(argv=None):
     torch.manual_seed(args.seed)
     head = build_head(cfg, dev, dtype)
     report = {"cfg": args.cfg, "dtype": args.dtype, "num_instance": cfg.DECODER.num_instance,
-              "views": cfg.DATASET.CAMERA_NUM, "layers": cfg.DECODER.num_decoder_layers}
+              "views": cfg.DATASET.CAMERA_NUM, "layers": cfg.DECODER.num_decoder_layers, "device_nms": bool(args.device_nms)}
     if args.model_path:
         missing, ignored = load_checkpoint(head, args.model_path)
         report["checkpoint"] = {"path": args.model_path, "missing_keys": missing[:8], "n_missing": len(missing),
@@ -133,6 +136,7 @@ def main(argv=None):
     from .serving import GraphedDecoder
     for thr in cfg.DECODER.inference_conf_thr:                                   # validate_3d.py:185
         preds, gts, gts_vis, t_dec, n_timed = [], [], [], 0.0, 0
+        kept = []
         runner = None
         for fi, (src, meta, gt) in enumerate(frames):
             src = [s.to(dev) for s in src]
@@ -140,7 +144,9 @@ def main(argv=None):
             if args.graph and runner is None:
                 # queries and initial poses do not depend on the frame (dq_transformer.py:394-432, 298-323): loaded once
                 shapes, starts = caller.level_tables(src)
-                runner = GraphedDecoder(head.decoder, meta, shapes, starts, 1, head.num_instance, thr)
+                runner = GraphedDecoder(head.decoder, meta, shapes, starts, 1, head.num_instance, thr,
+                                        postprocess=dict(dist_thr=0.3, num_nearby_joints_thr=7) if args.device_nms else None,
+                                        convert_joint_format_indices=head.convert_joint_format_indices)
                 qpos, tgt = caller.person_joint_queries(head.joint_embedding.weight, head.instance_embedding.weight, 1)
                 ref0 = caller.sample_space_reference_points(head.num_instance, head.space_size, head.space_center, 1, dev,
                                                             t_pose=head.t_pose)
@@ -150,9 +156,12 @@ def main(argv=None):
             if runner is not None:
                 runner.set_cameras(meta).load(src_views=src)
                 hs, refs, r2d, p2d, cls = runner.replay()
-                out = caller.decoder_outputs_to_dict(hs, refs, r2d, p2d, cls, head.num_instance, head.num_joints,
-                                                     head.convert_joint_format_indices)
-                pred = caller.pack_predictions(out, thr)                         # function.py:386-396
+                if args.device_nms:
+                    pred = runner.pred.clone()                                   # static buffer: the next replay overwrites it
+                else:
+                    out = caller.decoder_outputs_to_dict(hs, refs, r2d, p2d, cls, head.num_instance, head.num_joints,
+                                                         head.convert_joint_format_indices)
+                    pred = caller.pack_predictions(out, thr)                     # function.py:386-396
             else:
                 _, pred = head(src, meta, threshold=thr)                         # function.py:372-396
             torch.cuda.synchronize()
@@ -160,10 +169,16 @@ def main(argv=None):
                 t_dec += time.perf_counter() - t0
                 n_timed += 1
             preds.extend(p for p in pred)
+            if args.device_nms and runner is not None:
+                dets, count, _ = runner.detections                               # static buffers, filled by the replayed graph
+                kept.extend(dets[b, :k].clone() for b, k in enumerate(count[:, 0].tolist()))   # the frame's one read-back
+            elif args.device_nms:
+                kept.extend(E.filter_and_nms_device(pred))
             if gt is not None:
                 gts.append(gt[0])
                 gts_vis.append(gt[1])
-        kept = [E.filter_and_nms(p) for p in preds]                              # validate_3d.py:228-234 (0.3 m, 7 joints)
+        if not args.device_nms:
+            kept = [E.filter_and_nms(p) for p in preds]                          # validate_3d.py:228-234 (0.3 m, 7 joints)
         row = {"inference_conf_thr": thr, "frames": len(preds),
                "candidates_above_thr": int(sum(int((p[:, 0, 3] >= 0).sum()) for p in preds)),
                "poses_after_nms": int(sum(len(k) for k in kept)),
