@@ -364,7 +364,12 @@ __global__ __launch_bounds__(BW_NT) void bw_reduce_kernel(
         const f32x4 top = go[u] * a_w;
         // grad_value: fixed-point contributions, |top * w * fix| <= 2^30: exact in int32, accumulated as two's complement int64.
         // Branch-free: a corner outside the map adds 0 to a legal (clamped) cell -- rare, and cheaper than 16 exec-mask changes.
-        const f32x4 ft = top * fix;
+        // A non-finite grad_output entry does not enter grad_value (bw_absmax leaves it out of the scale): its term is zeroed HERE, not
+        // left to the conversion -- NaN would convert to 0, but +-Inf times a non-zero corner weight to a saturated +-2^31, and times a
+        // zero corner weight (a sample on a texel centre) to NaN: a result that depended on where the sample sits.
+        f32x4 ft = top * fix;
+#pragma unroll
+        for (int ch = 0; ch < 4; ++ch) ft[ch] = fabsf(ft[ch]) < INFINITY ? ft[ch] : 0.f;
         const float f1 = k1 ? s_w1 : 0.f, f2 = k2 ? s_w2 : 0.f, f3 = k3 ? s_w3 : 0.f, f4 = k4 ? s_w4 : 0.f;
         // Every patch cell is one 256-byte row = all 64 LDS banks, and lane (sample g8, j) adds to banks 8 j + 2 ch (+1) of ITS
         // cell: with the same channel order on all 8 samples of the wavefront every instruction hit 16 banks 8 deep (PMC: 65 % of
