@@ -131,6 +131,36 @@ int mvg_msda_backward_det_bf16(const void* value, const int64_t* shapes_host, co
                                int N, int S, int M, int D, int L, int Lq, int P,
                                void* workspace, size_t workspace_bytes, void* stream);
 
+/* Balanced form of the deterministic backward: the same tile-binned, fixed-point chain with the reduce step launched over
+ * (bin, chunk) work items.  The entries of a bin are cut into chunks of at most `chunk` entries and every chunk is one
+ * workgroup, so a bin that holds tens of thousands of samples (training with the matcher: every unmatched query projects to
+ * one pixel per view) is spread over many CUs instead of being walked by one workgroup; a bin of at most `chunk` entries takes
+ * the det path unchanged.  Contract:
+ *   - grad_value, grad_sampling_loc and grad_attn_weight are BIT-IDENTICAL to mvg_msda_backward_det_f32 / _bf16 for every
+ *     input those accept and every legal chunk: grad_value is a sum of int32 contributions in 64-bit integers (any partition
+ *     of a bin gives the same integer; the conversion is the same expression), the other two are computed per sample.
+ *   - no host read-back and a data-independent launch: the reduce grid is the host's bound of the item count, at most
+ *     N * bins_per_image + floor(N * Lq * M * L * P / chunk) workgroups; the item table is built on the device and workgroups
+ *     past the real count exit at once.  Capturable in a HIP graph and replayable on other data in the same buffers.
+ *   - the interior pixels of a split bin are summed with 64-bit integer atomics in a region of the workspace that the call
+ *     zeroes itself (nothing depends on what the workspace held) and converted once; empty bins still write their zeros.
+ *   - work item k of head m is workgroup k * M + m: a workgroup's index modulo M is its head, as in the det form.
+ *   - chunk: per call (frozen into a captured graph), 0 = the library default, otherwise a positive multiple of 256 (one
+ *     workgroup pass); anything else: MVG_E_BADARG, and mvg_msda_backward_bal_workspace returns 0.
+ *   - same availability as the det form: mvg_msda_backward_bal_workspace is 0 exactly where mvg_msda_backward_det_workspace
+ *     is (for a legal chunk), and at least that function's size otherwise. */
+size_t mvg_msda_backward_bal_workspace(int N, int S, int M, int D, int L, int Lq, int P, const int64_t* shapes_host, int chunk);
+int mvg_msda_backward_bal_f32(const float* value, const int64_t* shapes_host, const int64_t* starts_host,
+                              const float* sampling_loc, const float* attn_weight, const float* grad_output,
+                              float* grad_value, float* grad_sampling_loc, float* grad_attn_weight,
+                              int N, int S, int M, int D, int L, int Lq, int P,
+                              void* workspace, size_t workspace_bytes, void* stream, int chunk);
+int mvg_msda_backward_bal_bf16(const void* value, const int64_t* shapes_host, const int64_t* starts_host,
+                               const float* sampling_loc, const float* attn_weight, const float* grad_output,
+                               float* grad_value, float* grad_sampling_loc, float* grad_attn_weight,
+                               int N, int S, int M, int D, int L, int Lq, int P,
+                               void* workspace, size_t workspace_bytes, void* stream, int chunk);
+
 /* ---- stage entry points of the decoder layer ------------------------------------------ */
 
 

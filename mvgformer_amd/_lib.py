@@ -29,6 +29,9 @@ SIGNATURES = {
     "mvg_msda_backward_det_workspace": [_i] * 7 + [_vp],
     "mvg_msda_backward_det_f32": [_vp] * 9 + [_i] * 7 + [_vp, C.c_size_t, _vp],
     "mvg_msda_backward_det_bf16": [_vp] * 9 + [_i] * 7 + [_vp, C.c_size_t, _vp],
+    "mvg_msda_backward_bal_workspace": [_i] * 7 + [_vp, _i],
+    "mvg_msda_backward_bal_f32": [_vp] * 9 + [_i] * 7 + [_vp, C.c_size_t, _vp, _i],
+    "mvg_msda_backward_bal_bf16": [_vp] * 9 + [_i] * 7 + [_vp, C.c_size_t, _vp, _i],
     "mvg_msda_forward_f64": [_vp] * 6 + [_i] * 7 + [_vp],
     "mvg_msda_backward_f64": [_vp] * 9 + [_i] * 7 + [_vp],
     "mvg_pack_pyramid": [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _vp],
@@ -97,6 +100,7 @@ def load():
     lib.mvg_version.restype = C.c_char_p
     lib.mvg_bin_pairs_workspace.restype = C.c_size_t
     lib.mvg_msda_backward_det_workspace.restype = C.c_size_t
+    lib.mvg_msda_backward_bal_workspace.restype = C.c_size_t
     lib.mvg_knn_match_workspace.restype = C.c_size_t
     lib.mvg_criterion_workspace.restype = C.c_size_t
     lib.mvg_optim_workspace.restype = C.c_size_t

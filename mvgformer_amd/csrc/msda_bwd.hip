@@ -38,6 +38,12 @@ constexpr int BW_P = BW_T + 1;
 constexpr int BW_D = 32;
 constexpr int BW_NT = 256;                // 8 samples x 32 channels per pass
 constexpr int BW_SPLIT = 1;               // workgroups per bin (interleaved over its entries): 2 / 4 / 8 measured 635 / 770 / 761 us against 617 us
+                                          // (a static split also splits the thousands of small bins; the `balanced` mode below
+                                          // splits only the bins that hold more than `chunk` entries: mvg_msda_backward_bal_*)
+constexpr int BW_CHUNK_DEFAULT = 2048;    // entries per (bin, chunk) work item of the balanced mode when the caller passes 0: the best
+                                          // clustered time at N = 5, the training call (512 / 1024 / 2048 / 4096: 1527 / 1377 / 1331 /
+                                          // 1383 us against det's 4717), with a uniform time below det's (1213 against 1227 us);
+                                          // at N = 1 chunk 1024 is 12 us better (325 against 337 us).  DESIGN.md section 9h
 constexpr float BW_FIX = 1073741824.f;     // 2^30: a contribution (|.| <= max |grad_output|) is an exact int32
 
 struct BwLevels {
@@ -240,36 +246,49 @@ __device__ __forceinline__ float sum8(float v) {
   return v;
 }
 
-// TV: storage type of `value` (float, or bf16_t for mixed-precision training).  Only the patch load differs: a bf16 value is
-// widened exactly to fp32 on its way into LDS, and everything after it is the fp32 kernel's.
-template <typename TV>
-__global__ __launch_bounds__(BW_NT) void bw_reduce_kernel(
-    const TV* __restrict__ value, const float* __restrict__ loc, const float* __restrict__ wgt, const float* __restrict__ gout,
-    BwLevels lv, const int* __restrict__ offset, const unsigned* __restrict__ list, const unsigned* __restrict__ gmax_bits,
-    unsigned long long* __restrict__ accum, float* __restrict__ gvalue, float* __restrict__ gloc, float* __restrict__ gwgt, int N,
-    int S, int Lq, int M, int P) {
-  __shared__ float vpatch[BW_P * BW_P][BW_D];                           // 10.1 KB
-  __shared__ unsigned long long apatch[BW_P * BW_P][BW_D];              // 20.3 KB
-  // BW_SPLIT workgroups share a bin (interleaved passes over its entries): bins differ a lot in size -- a coarse-level tile
-  // collects 15x the samples of a fine-level one -- and one workgroup per bin left the kernel waiting for the largest ones.
-  // Every workgroup adds its own patch to the global accumulator: integers, so still order-independent.
-  // blockIdx = ((image, tile) * BW_SPLIT + split) * M + head: with M = 8, blockIdx % 8 -- the XCD the block is dispatched to --
-  // is the HEAD, so an XCD's 4-MB L2 holds one head's slice of grad_output (2 MB at cfg-2) and of value; a mapping that put
-  // all heads on every XCD ran 2.3x slower (its grad_output rows came from HBM / Infinity Cache)
-  const int m_ = blockIdx.x % M, rest_ = blockIdx.x / M;
-  const int split = rest_ % BW_SPLIT, bin = (rest_ / BW_SPLIT) * M + m_;
-  static_assert(BW_SPLIT == 1, "the interior of a tile is written by exactly one workgroup");
-  const int e0 = offset[bin], e1 = offset[bin + 1];
-  const int m = bin % M;
+// (image, level, patch origin in pixels) of the tile of a bin (bin = (image * T_total + tile) * M + head)
+struct BwTile {
+  int n, l, y0, x0;
+};
+__device__ __forceinline__ BwTile bw_tile_of(const BwLevels& lv, int bin, int M) {
   const int nt = bin / M;
-  const int n = nt / lv.T_total, tile = nt - n * lv.T_total;
-  int l = 0;
+  BwTile t;
+  t.n = nt / lv.T_total;
+  const int tile = nt - t.n * lv.T_total;
+  t.l = 0;
 #pragma unroll
   for (int k = 1; k < MVG_MAX_LEVELS; ++k)
-    if (k < lv.L && tile >= lv.tile0[k]) l = k;
-  const int tl = tile - lv.tile0[l];
+    if (k < lv.L && tile >= lv.tile0[k]) t.l = k;
+  const int tl = tile - lv.tile0[t.l];
+  t.y0 = (tl / lv.tiles_w[t.l]) * BW_T;
+  t.x0 = (tl % lv.tiles_w[t.l]) * BW_T;
+  return t;
+}
+
+// TV: storage type of `value` (float, or bf16_t for mixed-precision training).  Only the patch load differs: a bf16 value is
+// widened exactly to fp32 on its way into LDS, and everything after it is the fp32 kernel's.
+//
+// The work of one workgroup on the entries [e0, e1) of `bin`, shared by the two reduce kernels:
+//   bw_reduce_kernel      (det)       all entries of the bin; BAL = false, `shared_interior` is not read;
+//   bw_reduce_bal_kernel  (balanced)  one chunk of the bin's entries; `shared_interior` = the bin has more than one chunk, so its
+//                                     interior pixels get contributions from several workgroups and go through `accum` like the
+//                                     border pixels (bw_plan_kernel zeroed them, bw_finish_kernel converts them once).
+// The location / weight gradients of a sample depend on the sample alone (its 8 lanes, a fixed DPP tree), and grad_value is a
+// sum of integers: any cut of a bin into chunks gives det's bits.
+template <typename TV, bool BAL>
+__device__ __forceinline__ void bw_reduce_entries(
+    const TV* __restrict__ value, const float* __restrict__ loc, const float* __restrict__ wgt, const float* __restrict__ gout,
+    const BwLevels& lv, const unsigned* __restrict__ list, const unsigned* __restrict__ gmax_bits,
+    unsigned long long* __restrict__ accum, float* __restrict__ gvalue, float* __restrict__ gloc, float* __restrict__ gwgt,
+    const int S, const int Lq, const int M, const int P, const int bin, const int split, const int e0, const int e1,
+    const bool shared_interior) {
+  __shared__ float vpatch[BW_P * BW_P][BW_D];                           // 10.1 KB
+  __shared__ unsigned long long apatch[BW_P * BW_P][BW_D];              // 20.3 KB
+  const int m = bin % M;
+  const BwTile bt = bw_tile_of(lv, bin, M);
+  const int n = bt.n, l = bt.l;
   const int H = lv.H[l], W = lv.W[l];
-  const int y0 = (tl / lv.tiles_w[l]) * BW_T, x0 = (tl % lv.tiles_w[l]) * BW_T;     // patch origin (pixel)
+  const int y0 = bt.y0, x0 = bt.x0;                                     // patch origin (pixel)
   const int tid = threadIdx.x;
   const long row_stride = (long)M * BW_D;
   // Pixels with x % T != 0 and y % T != 0 receive contributions from THIS tile only (a neighbour's patch reaches just its first
@@ -415,9 +434,133 @@ __global__ __launch_bounds__(BW_NT) void bw_reduce_kernel(
     const int y = y0 + py, x = x0 + pxx;
     const unsigned long long v = apatch[px][ch];
     if (y >= H || x >= W) continue;
-    if (py % BW_T != 0 && pxx % BW_T != 0) gbase[((long)y * W + x) * row_stride + ch] = (float)((double)(long long)v * inv);
+    if (py % BW_T != 0 && pxx % BW_T != 0 && !(BAL && shared_interior))
+      gbase[((long)y * W + x) * row_stride + ch] = (float)((double)(long long)v * inv);
     else if (v != 0ull) atomicAdd(abase + ((long)y * W + x) * M * BW_D + ch, v);
   }
+}
+
+template <typename TV>
+__global__ __launch_bounds__(BW_NT) void bw_reduce_kernel(
+    const TV* __restrict__ value, const float* __restrict__ loc, const float* __restrict__ wgt, const float* __restrict__ gout,
+    BwLevels lv, const int* __restrict__ offset, const unsigned* __restrict__ list, const unsigned* __restrict__ gmax_bits,
+    unsigned long long* __restrict__ accum, float* __restrict__ gvalue, float* __restrict__ gloc, float* __restrict__ gwgt, int N,
+    int S, int Lq, int M, int P) {
+  // BW_SPLIT workgroups share a bin (interleaved passes over its entries): bins differ a lot in size -- a coarse-level tile
+  // collects 15x the samples of a fine-level one -- and one workgroup per bin left the kernel waiting for the largest ones.
+  // Every workgroup adds its own patch to the global accumulator: integers, so still order-independent.
+  // blockIdx = ((image, tile) * BW_SPLIT + split) * M + head: with M = 8, blockIdx % 8 -- the XCD the block is dispatched to --
+  // is the HEAD, so an XCD's 4-MB L2 holds one head's slice of grad_output (2 MB at cfg-2) and of value; a mapping that put
+  // all heads on every XCD ran 2.3x slower (its grad_output rows came from HBM / Infinity Cache)
+  const int m_ = blockIdx.x % M, rest_ = blockIdx.x / M;
+  const int split = rest_ % BW_SPLIT, bin = (rest_ / BW_SPLIT) * M + m_;
+  static_assert(BW_SPLIT == 1, "the interior of a tile is written by exactly one workgroup");
+  bw_reduce_entries<TV, false>(value, loc, wgt, gout, lv, list, gmax_bits, accum, gvalue, gloc, gwgt, S, Lq, M, P, bin, split,
+                               offset[bin], offset[bin + 1], false);
+}
+
+// ---- balanced mode: the reduce step over (bin, chunk) work items -----------------------------------------------------------------
+// A bin of cnt entries is cut into max(1, ceil(cnt / chunk)) items; an item is one workgroup of bw_reduce_bal_kernel.  The items
+// are numbered PER HEAD (bw_plan_kernel: an exclusive scan of the chunk counts over the (image, tile) bins of head m) and item k
+// of head m is workgroup k * M + m, so blockIdx % M is still the head -- the XCD locality of bw_reduce_kernel.  A head holds
+// exactly N * Lq * L * P samples, so it has at most N * T_total + floor(N * Lq * L * P / chunk) items: the grid is M times that,
+// known on the host (no read-back, the same launch for any data: capturable), and at most N * bpi + floor(N * per_img / chunk).
+// Workgroups past nitems[m] exit at once.
+
+// the interior pixels (x % T != 0 and y % T != 0) of a SPLIT bin's tile, by one wavefront:
+//   MODE 0: accum <- 0 (before the reduce kernel)   MODE 1: grad_value <- accum / scale (bw_reduce_entries' own expression)
+template <int MODE>
+__device__ __forceinline__ void bw_split_interior(unsigned long long* __restrict__ accum, const unsigned* __restrict__ gmax_bits,
+                                                  float* __restrict__ gvalue, const BwLevels& lv, int bin, int S, int M, int lane) {
+  const BwTile t = bw_tile_of(lv, bin, M);
+  const int H = lv.H[t.l], W = lv.W[t.l];
+  const long base = (((long)t.n * S + lv.start[t.l]) * M + bin % M) * BW_D;
+  const double inv = MODE == 1 ? bw_inv_of(bw_fix_of(gmax_bits, t.n)) : 0.0;
+  for (int i = lane; i < (BW_T - 1) * (BW_T - 1) * BW_D; i += 64) {
+    const int px = i >> 5, ch = i & 31;
+    const int y = t.y0 + 1 + px / (BW_T - 1), x = t.x0 + 1 + px % (BW_T - 1);
+    if (y >= H || x >= W) continue;
+    const long idx = base + ((long)y * W + x) * M * BW_D + ch;
+    if (MODE == 0) accum[idx] = 0ull;
+    else gvalue[idx] = (float)((double)(long long)accum[idx] * inv);
+  }
+}
+
+// workgroups [0, M): the item table of head m -- items[k * M + m] = (bin, chunk index) of the head's k-th item, nitems[m];
+// workgroups [M, M + ceil(nbins / 4)): one wavefront per bin zeroes the interior of `accum` of every split bin (total > chunk).
+// Both read only the bin totals of bw_prefix_kernel.  NT = N * T_total bins per head.
+__global__ __launch_bounds__(256) void bw_plan_kernel(const int* __restrict__ total, int2* __restrict__ items,
+                                                      int* __restrict__ nitems, unsigned long long* __restrict__ accum, BwLevels lv,
+                                                      int NT, int S, int M, int chunk) {
+  const int tid = threadIdx.x;
+  if ((int)blockIdx.x >= M) {
+    const int bin = ((int)blockIdx.x - M) * 4 + (tid >> 6);
+    if (bin < NT * M && total[bin] > chunk) bw_split_interior<0>(accum, nullptr, nullptr, lv, bin, S, M, tid & 63);
+    return;
+  }
+  const int m = blockIdx.x;
+  __shared__ int wsum[4];
+  __shared__ int carry;
+  if (tid == 0) carry = 0;
+  __syncthreads();
+  for (int base = 0; base < NT; base += 256 * 4) {
+    int v[4], s = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int i = base + tid * 4 + k;
+      const int cnt = i < NT ? total[(long)i * M + m] : 0;
+      v[k] = i < NT ? (cnt > 0 ? (cnt - 1) / chunk + 1 : 1) : 0;      // an empty bin keeps one item: it writes its interior zeros
+      s += v[k];
+    }
+    int incl = s;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const int up = __shfl_up(incl, d, 64);
+      if ((tid & 63) >= d) incl += up;
+    }
+    if ((tid & 63) == 63) wsum[tid >> 6] = incl;
+    __syncthreads();
+    int wbase = 0, tot = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      const int t = wsum[w];
+      wbase += (w < (tid >> 6)) ? t : 0;
+      tot += t;
+    }
+    int ex = carry + wbase + incl - s;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int i = base + tid * 4 + k;
+      for (int c = 0; c < v[k]; ++c) items[(long)(ex + c) * M + m] = make_int2(i * M + m, c);
+      ex += v[k];
+    }
+    __syncthreads();
+    if (tid == 0) carry += tot;
+    __syncthreads();
+  }
+  if (tid == 0) nitems[m] = carry;
+}
+
+template <typename TV>
+__global__ __launch_bounds__(BW_NT) void bw_reduce_bal_kernel(
+    const TV* __restrict__ value, const float* __restrict__ loc, const float* __restrict__ wgt, const float* __restrict__ gout,
+    BwLevels lv, const int* __restrict__ offset, const unsigned* __restrict__ list, const unsigned* __restrict__ gmax_bits,
+    const int2* __restrict__ items, const int* __restrict__ nitems, unsigned long long* __restrict__ accum,
+    float* __restrict__ gvalue, float* __restrict__ gloc, float* __restrict__ gwgt, int S, int Lq, int M, int P, int chunk) {
+  if ((int)(blockIdx.x / M) >= nitems[blockIdx.x % M]) return;           // the grid is the host's bound, not the item count
+  const int2 it = items[blockIdx.x];
+  const int bin = it.x, off = offset[bin], cnt = offset[bin + 1] - off;
+  const int done = it.y * chunk;                                           // it.y >= 1 only where cnt > it.y * chunk
+  bw_reduce_entries<TV, true>(value, loc, wgt, gout, lv, list, gmax_bits, accum, gvalue, gloc, gwgt, S, Lq, M, P, bin, 0,
+                              off + done, off + done + min(cnt - done, chunk), cnt > chunk);
+}
+
+// one wavefront per bin: the interior of every split bin, accum -> grad_value (after the reduce kernel)
+__global__ __launch_bounds__(256) void bw_finish_kernel(const int* __restrict__ total, unsigned long long* __restrict__ accum,
+                                                        const unsigned* __restrict__ gmax_bits, float* __restrict__ gvalue,
+                                                        BwLevels lv, int nbins, int S, int M, int chunk) {
+  const int bin = (int)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (bin < nbins && total[bin] > chunk) bw_split_interior<1>(accum, gmax_bits, gvalue, lv, bin, S, M, threadIdx.x & 63);
 }
 
 // The shared pixels (x % T == 0 or y % T == 0) of every map, one workgroup per (map row, 32-pixel segment):
@@ -478,6 +621,28 @@ BwLayout bw_layout(long N, long S, long M, long Lq, long LP, long bpi) {
   return w;
 }
 
+// balanced mode: det's workspace, then the item table and the per-head item counts
+struct BwBalLayout {
+  size_t items, nitems, bytes;
+  long per_head;                          // bound of a head's items: the reduce grid is M * per_head workgroups
+};
+
+BwBalLayout bw_bal_layout(size_t det_bytes, long N, long M, long Lq, long LP, long T_total, long chunk) {
+  auto up = [](size_t x) { return (x + 255) / 256 * 256; };
+  BwBalLayout w;
+  w.per_head = N * T_total + (N * Lq * LP) / chunk;
+  w.items = det_bytes;
+  w.nitems = w.items + up((size_t)w.per_head * M * sizeof(int2));
+  w.bytes = w.nitems + up((size_t)M * 4);
+  return w;
+}
+
+// 0 -> the library default; otherwise a positive multiple of one workgroup pass (BW_NT entries); -1: illegal
+int bw_chunk_of(int chunk) {
+  if (chunk == 0) return BW_CHUNK_DEFAULT;
+  return (chunk > 0 && chunk % BW_NT == 0) ? chunk : -1;
+}
+
 }  // namespace
 
 extern "C" {
@@ -493,19 +658,39 @@ size_t mvg_msda_backward_det_workspace(int N, int S, int M, int D, int L, int Lq
   return bw_layout(N, S, M, Lq, (long)L * P, bpi).bytes;
 }
 
+size_t mvg_msda_backward_bal_workspace(int N, int S, int M, int D, int L, int Lq, int P, const int64_t* shapes_host, int chunk) {
+  const size_t det = mvg_msda_backward_det_workspace(N, S, M, D, L, Lq, P, shapes_host);
+  const int c = bw_chunk_of(chunk);
+  if (det == 0 || c < 0) return 0;
+  BwLevels lv;
+  int64_t zeros[MVG_MAX_LEVELS] = {0};
+  if (fill_bw_levels(&lv, shapes_host, zeros, L)) return 0;
+  return bw_bal_layout(det, N, M, Lq, (long)L * P, lv.T_total, c).bytes;
+}
+
 }  // extern "C"
 
 namespace {
 
+// The tile-binned backward, both deterministic modes: the chain up to the binned entry list (bw_shared<0>, bw_absmax, bw_part<0>,
+// bw_prefix, bw_scan, bw_part<1>) and the closing bw_shared<1> are the same launches; only the reduce step between them differs --
+// PerBin: bw_reduce_kernel, one workgroup per bin (mvg_msda_backward_det_*); Balanced: bw_plan, bw_reduce_bal over (bin, chunk) items,
+// bw_finish (mvg_msda_backward_bal_*).  chunk_arg: the caller's chunk of the balanced mode (0 = BW_CHUNK_DEFAULT), not read by PerBin.
+enum class BwReduce { PerBin, Balanced };
+
 template <typename TV>
-int backward_det(const TV* value, const int64_t* shapes_host, const int64_t* starts_host, const float* sampling_loc,
-                 const float* attn_weight, const float* grad_output, float* grad_value, float* grad_sampling_loc,
-                 float* grad_attn_weight, int N, int S, int M, int D, int L, int Lq, int P, void* workspace, size_t workspace_bytes,
-                 void* stream) {
+int backward_binned(const TV* value, const int64_t* shapes_host, const int64_t* starts_host, const float* sampling_loc,
+                    const float* attn_weight, const float* grad_output, float* grad_value, float* grad_sampling_loc,
+                    float* grad_attn_weight, int N, int S, int M, int D, int L, int Lq, int P, void* workspace, size_t workspace_bytes,
+                    void* stream, BwReduce reduce, int chunk_arg) {
+  const bool balanced = reduce == BwReduce::Balanced;
   if (!value || !shapes_host || !starts_host || !sampling_loc || !attn_weight || !grad_output || !grad_value ||
       !grad_sampling_loc || !grad_attn_weight || !workspace)
     return MVG_E_BADARG;
-  const size_t need = mvg_msda_backward_det_workspace(N, S, M, D, L, Lq, P, shapes_host);
+  const int bal_chunk = balanced ? bw_chunk_of(chunk_arg) : 0;
+  if (bal_chunk < 0) return MVG_E_BADARG;
+  const size_t det_need = mvg_msda_backward_det_workspace(N, S, M, D, L, Lq, P, shapes_host);
+  const size_t need = balanced ? mvg_msda_backward_bal_workspace(N, S, M, D, L, Lq, P, shapes_host, chunk_arg) : det_need;
   if (need == 0 || workspace_bytes < need) return MVG_E_BADARG;
   BwLevels lv;
   int e = fill_bw_levels(&lv, shapes_host, starts_host, L);
@@ -553,9 +738,24 @@ int backward_det(const TV* value, const int64_t* shapes_host, const int64_t* sta
   hipLaunchKernelGGL(bw_scan_kernel, dim3(1), dim3(1024), 0, st, (const int*)total, offset, (int)nbins);
   hipLaunchKernelGGL((bw_part_kernel<1>), dim3(N * BW_PARTS), dim3(1024), lds, st, sampling_loc, lv, cnt, (const int*)offset,
                      list, Lq, M, P, (int)bpi, per_img, chunk, grad_sampling_loc, grad_attn_weight);
-  hipLaunchKernelGGL(bw_reduce_kernel<TV>, dim3((unsigned)(nbins * BW_SPLIT)), dim3(BW_NT), 0, st, value, sampling_loc, attn_weight,
-                     grad_output, lv, (const int*)offset, (const unsigned*)list, (const unsigned*)gmax, accum, grad_value,
-                     grad_sampling_loc, grad_attn_weight, N, S, Lq, M, P);
+  if (balanced) {
+    const BwBalLayout b = bw_bal_layout(det_need, N, M, Lq, LP, lv.T_total, bal_chunk);
+    int2* items = reinterpret_cast<int2*>(ws + b.items);
+    int* nitems = reinterpret_cast<int*>(ws + b.nitems);
+    const unsigned per_bin = (unsigned)((nbins + 3) / 4);                     // one wavefront per bin
+    hipLaunchKernelGGL(bw_plan_kernel, dim3((unsigned)M + per_bin), dim3(256), 0, st, (const int*)total, items, nitems, accum, lv,
+                       N * lv.T_total, S, M, bal_chunk);
+    hipLaunchKernelGGL(bw_reduce_bal_kernel<TV>, dim3((unsigned)(b.per_head * M)), dim3(BW_NT), 0, st, value, sampling_loc,
+                       attn_weight, grad_output, lv, (const int*)offset, (const unsigned*)list, (const unsigned*)gmax,
+                       (const int2*)items, (const int*)nitems, accum, grad_value, grad_sampling_loc, grad_attn_weight, S, Lq, M, P,
+                       bal_chunk);
+    hipLaunchKernelGGL(bw_finish_kernel, dim3(per_bin), dim3(256), 0, st, (const int*)total, accum, (const unsigned*)gmax,
+                       grad_value, lv, (int)nbins, S, M, bal_chunk);
+  } else {
+    hipLaunchKernelGGL(bw_reduce_kernel<TV>, dim3((unsigned)(nbins * BW_SPLIT)), dim3(BW_NT), 0, st, value, sampling_loc, attn_weight,
+                       grad_output, lv, (const int*)offset, (const unsigned*)list, (const unsigned*)gmax, accum, grad_value,
+                       grad_sampling_loc, grad_attn_weight, N, S, Lq, M, P);
+  }
   hipLaunchKernelGGL((bw_shared_kernel<1>), shared_grid, dim3(256), 0, st, accum, gmax, grad_value, lv, S, M, rows_per_img);
   MVG_LAUNCH_CHECK();
   return 0;
@@ -569,17 +769,34 @@ int mvg_msda_backward_det_f32(const float* value, const int64_t* shapes_host, co
                               const float* sampling_loc, const float* attn_weight, const float* grad_output,
                               float* grad_value, float* grad_sampling_loc, float* grad_attn_weight, int N, int S, int M,
                               int D, int L, int Lq, int P, void* workspace, size_t workspace_bytes, void* stream) {
-  return backward_det<float>(value, shapes_host, starts_host, sampling_loc, attn_weight, grad_output, grad_value, grad_sampling_loc,
-                             grad_attn_weight, N, S, M, D, L, Lq, P, workspace, workspace_bytes, stream);
+  return backward_binned<float>(value, shapes_host, starts_host, sampling_loc, attn_weight, grad_output, grad_value, grad_sampling_loc,
+                                grad_attn_weight, N, S, M, D, L, Lq, P, workspace, workspace_bytes, stream, BwReduce::PerBin, 0);
 }
 
 int mvg_msda_backward_det_bf16(const void* value, const int64_t* shapes_host, const int64_t* starts_host,
                                const float* sampling_loc, const float* attn_weight, const float* grad_output,
                                float* grad_value, float* grad_sampling_loc, float* grad_attn_weight, int N, int S, int M,
                                int D, int L, int Lq, int P, void* workspace, size_t workspace_bytes, void* stream) {
-  return backward_det<bf16_t>(reinterpret_cast<const bf16_t*>(value), shapes_host, starts_host, sampling_loc, attn_weight, grad_output,
+  return backward_binned<bf16_t>(reinterpret_cast<const bf16_t*>(value), shapes_host, starts_host, sampling_loc, attn_weight, grad_output,
                               grad_value, grad_sampling_loc, grad_attn_weight, N, S, M, D, L, Lq, P, workspace, workspace_bytes,
-                              stream);
+                              stream, BwReduce::PerBin, 0);
+}
+
+int mvg_msda_backward_bal_f32(const float* value, const int64_t* shapes_host, const int64_t* starts_host,
+                              const float* sampling_loc, const float* attn_weight, const float* grad_output,
+                              float* grad_value, float* grad_sampling_loc, float* grad_attn_weight, int N, int S, int M,
+                              int D, int L, int Lq, int P, void* workspace, size_t workspace_bytes, void* stream, int chunk) {
+  return backward_binned<float>(value, shapes_host, starts_host, sampling_loc, attn_weight, grad_output, grad_value, grad_sampling_loc,
+                             grad_attn_weight, N, S, M, D, L, Lq, P, workspace, workspace_bytes, stream, BwReduce::Balanced, chunk);
+}
+
+int mvg_msda_backward_bal_bf16(const void* value, const int64_t* shapes_host, const int64_t* starts_host,
+                               const float* sampling_loc, const float* attn_weight, const float* grad_output,
+                               float* grad_value, float* grad_sampling_loc, float* grad_attn_weight, int N, int S, int M,
+                               int D, int L, int Lq, int P, void* workspace, size_t workspace_bytes, void* stream, int chunk) {
+  return backward_binned<bf16_t>(reinterpret_cast<const bf16_t*>(value), shapes_host, starts_host, sampling_loc, attn_weight, grad_output,
+                              grad_value, grad_sampling_loc, grad_attn_weight, N, S, M, D, L, Lq, P, workspace, workspace_bytes,
+                              stream, BwReduce::Balanced, chunk);
 }
 
 }  // extern "C"

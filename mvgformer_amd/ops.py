@@ -15,8 +15,26 @@ import torch
 from . import _lib as L
 
 # backward of the sampling op: "det" = deterministic tile-binned form where the shape allows (D = 32), "atomic" = always the
-# fp32-atomics form of round 1 (the reference's own scheme)
+# fp32-atomics form of round 1 (the reference's own scheme), "balanced" = the deterministic form with its reduce step launched over
+# (bin, chunk) work items (mvg_msda_backward_bal_*: det's bits, a time that does not depend on where the samples fall)
 BACKWARD_MODE = __import__("os").environ.get("MVG_BACKWARD", "det")
+# entries per work item of the balanced mode: None = the library default, otherwise a positive multiple of 256.  Read at every
+# call and passed as an argument: a captured graph keeps the value it was captured with.
+BACKWARD_CHUNK = None
+
+
+def _det_entry(lib, bf16, dims, shapes_c):
+    """(function, name, workspace bytes, trailing arguments) of the deterministic backward that BACKWARD_MODE selects; workspace
+    bytes 0: the shape is not supported, the caller falls back to the atomic kernel."""
+    kind = "bf16" if bf16 else "f32"
+    if BACKWARD_MODE == "balanced":
+        chunk = 0 if BACKWARD_CHUNK is None else int(BACKWARD_CHUNK)
+        if chunk < 0 or chunk % 256:
+            raise L.MvgError("BACKWARD_CHUNK must be None, 0 or a positive multiple of 256 (got %r)" % (BACKWARD_CHUNK,))
+        name = "mvg_msda_backward_bal_" + kind
+        return getattr(lib, name), name, int(lib.mvg_msda_backward_bal_workspace(*dims, shapes_c, chunk)), (chunk,)
+    name = "mvg_msda_backward_det_" + kind
+    return getattr(lib, name), name, int(lib.mvg_msda_backward_det_workspace(*dims, shapes_c)), ()
 
 
 # ---- optional per-launch timing with HIP events on the launch stream (bench.py roofline) -----
@@ -131,7 +149,8 @@ def msda_backward(value, spatial_shapes, level_start_index, sampling_loc, attn_w
     """Deformable.deform_backward (lib/models/ops/src/deform.h:53-72).  host: host_levels(...) of the two tables when the
     caller already has them (DeformFunction keeps the forward's).
 
-    float32 with D = 32 runs the deterministic form (MVG_BACKWARD=atomic selects the reference's fp32-atomic scheme): grad_value is
+    float32 with D = 32 runs the deterministic form (MVG_BACKWARD=atomic selects the reference's fp32-atomic scheme,
+    MVG_BACKWARD=balanced the same deterministic chain with large bins cut into chunks of BACKWARD_CHUNK entries: det's bits): grad_value is
     summed in 64-bit fixed point with one scale PER IMAGE, 2^30 / (max |grad_output[n]| * max |attn_weight[n]|) over the finite
     entries -- any weight magnitude and any gradient magnitude down to 2^-96 are exact int32 contributions; what is smaller than
     2^-31 of its image's largest possible contribution rounds to zero.  Non-finite grad_output entries do not enter grad_value."""
@@ -150,14 +169,14 @@ def msda_backward(value, spatial_shapes, level_start_index, sampling_loc, attn_w
         # deterministic form (csrc/msda_bwd.hip): binned by destination tile, fixed-point accumulation in LDS
         lib = L.load()
         shapes_c, starts_c = host if host is not None else host_levels(spatial_shapes, level_start_index)
-        ws_bytes = int(lib.mvg_msda_backward_det_workspace(N, S, M, D, nl, Lq, P, shapes_c))
+        fn, fn_name, ws_bytes, tail = _det_entry(lib, False, (N, S, M, D, nl, Lq, P), shapes_c)
         if ws_bytes:
             ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=value.device)
             gv, gl, ga = torch.empty_like(value), torch.empty_like(sampling_loc), torch.empty_like(attn_weight)
             with _timed("msda_backward_det"):
-              L.check(lib.mvg_msda_backward_det_f32(L.ptr(value), shapes_c, starts_c, L.ptr(sampling_loc), L.ptr(attn_weight),
-                                                    L.ptr(grad_output), L.ptr(gv), L.ptr(gl), L.ptr(ga), N, S, M, D, nl, Lq, P,
-                                                    L.ptr(ws), ws_bytes, L.stream_ptr()), "mvg_msda_backward_det_f32")
+              L.check(fn(L.ptr(value), shapes_c, starts_c, L.ptr(sampling_loc), L.ptr(attn_weight),
+                         L.ptr(grad_output), L.ptr(gv), L.ptr(gl), L.ptr(ga), N, S, M, D, nl, Lq, P,
+                         L.ptr(ws), ws_bytes, L.stream_ptr(), *tail), fn_name)
             return gv, gl, ga
     gv = torch.zeros_like(value)                                             # deform_cuda.cu:132-134
     gl = torch.empty_like(sampling_loc)
@@ -186,15 +205,15 @@ def _msda_backward_bf16(value, spatial_shapes, level_start_index, sampling_loc, 
     lib = L.load()
     if BACKWARD_MODE != "atomic":
         shapes_c, starts_c = host if host is not None else host_levels(spatial_shapes, level_start_index)
-        ws_bytes = int(lib.mvg_msda_backward_det_workspace(N, S, M, D, nl, Lq, P, shapes_c))
+        fn, fn_name, ws_bytes, tail = _det_entry(lib, True, (N, S, M, D, nl, Lq, P), shapes_c)
         if ws_bytes:
             ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=value.device)
             gv = torch.empty(value.shape, dtype=torch.float32, device=value.device)
             gl, ga = torch.empty_like(sampling_loc), torch.empty_like(attn_weight)
             with _timed("msda_backward_det_bf16"):
-              L.check(lib.mvg_msda_backward_det_bf16(L.ptr(value), shapes_c, starts_c, L.ptr(sampling_loc), L.ptr(attn_weight),
-                                                     L.ptr(grad_output), L.ptr(gv), L.ptr(gl), L.ptr(ga), N, S, M, D, nl, Lq, P,
-                                                     L.ptr(ws), ws_bytes, L.stream_ptr()), "mvg_msda_backward_det_bf16")
+              L.check(fn(L.ptr(value), shapes_c, starts_c, L.ptr(sampling_loc), L.ptr(attn_weight),
+                         L.ptr(grad_output), L.ptr(gv), L.ptr(gl), L.ptr(ga), N, S, M, D, nl, Lq, P,
+                         L.ptr(ws), ws_bytes, L.stream_ptr(), *tail), fn_name)
             return gv, gl, ga
     v32 = value.float()
     gv = torch.zeros_like(v32)

@@ -1,6 +1,7 @@
 """Time of one training step of the decoder at cfg-2 size: forward under autograd (torch geometry +
 ProjAttn with the HIP sampling forward / backward kernels) + backward to every parameter.  GPU only.
 python tools/train_step_probe.py [config] [steps] [fp32|bf16] [--criterion] [--optimizer fused|torch] [--graph]
+                                 [--backward det|balanced] [--chunk c]
 (bf16: DQDecoder.set_training_dtype(torch.bfloat16))
 --criterion: the real step -- DecoderHead.forward_train (ground-truth match, decoder with the matched mask, fused criterion) on
 synthetic ground truth (5 persons, K = 5) and total_loss(...).backward() -- instead of the made-up loss of the default run.
@@ -10,7 +11,9 @@ on the device.  Without the option the step ends at backward() and drops the gra
 --graph (with --criterion --optimizer fused): the same step captured once as a HIP graph (training.GraphedTrainStep) and replayed,
 timed next to the eager step in the same process.  Three figures: the plain step of this script (a DecoderContext per call; a block
 of `steps` runs before the runner is built), runner.eager() (the identical step the graph holds: static context, bf16 operands kept by
-the device) and runner.replay(); the last two alternate, each figure is the median over `steps` rounds."""
+the device) and runner.replay(); the last two alternate, each figure is the median over `steps` rounds.
+--backward: the mode of the sampling op's backward (ops.BACKWARD_MODE; default: the library's, det); --chunk: ops.BACKWARD_CHUNK of
+the balanced mode.  The --graph run also prints the device time of the bw_reduce* kernels in its profiled eager step."""
 import os
 import sys
 import time
@@ -32,6 +35,21 @@ if "--optimizer" in argv:
     if optimizer not in ("fused", "torch"):
         raise SystemExit("--optimizer fused|torch")
     del argv[i:i + 2]
+backward = chunk = None
+if "--backward" in argv:
+    i = argv.index("--backward")
+    backward = argv[i + 1] if i + 1 < len(argv) else ""
+    if backward not in ("det", "balanced"):
+        raise SystemExit("--backward det|balanced")
+    del argv[i:i + 2]
+if "--chunk" in argv:
+    i = argv.index("--chunk")
+    if i + 1 >= len(argv) or not argv[i + 1].isdigit():
+        raise SystemExit("--chunk needs a number (0 or a positive multiple of 256)")
+    chunk = int(argv[i + 1])
+    del argv[i:i + 2]
+    if backward != "balanced":
+        raise SystemExit("--chunk needs --backward balanced")
 if with_graph and not (with_criterion and optimizer == "fused"):
     raise SystemExit("--graph needs --criterion --optimizer fused")
 cfg = argv[1] if len(argv) > 1 else "cfg2"
@@ -39,6 +57,9 @@ steps = int(argv[2]) if len(argv) > 2 else 5
 tdt = argv[3] if len(argv) > 3 else "fp32"
 if tdt not in ("fp32", "bf16"):
     raise SystemExit("training dtype must be fp32 or bf16")
+from mvgformer_amd import ops  # noqa: E402
+if backward is not None:
+    ops.BACKWARD_MODE, ops.BACKWARD_CHUNK = backward, chunk
 case = build_case(cfg, seed=0)
 dec = build_decoder_for_case(case, "cuda", torch.float32)
 if tdt == "bf16":
@@ -144,6 +165,9 @@ def graph_run():
     print("device time of one runner.eager() step: %.2f ms in %d launches; the largest:" % (busy / 1e3, len(dev_ev)))
     for name, (n, t) in sorted(by_name.items(), key=lambda kv: -kv[1][1])[:8]:
         print("  %8.3f ms  %4d x  %s" % (t / 1e3, n, name[:110]))
+    reduce = [(n, t) for name, (n, t) in by_name.items() if "bw_reduce" in name]
+    print("bw_reduce* kernels of that step (backward mode %s): %.3f ms in %d launches"
+          % (ops.BACKWARD_MODE + ("" if ops.BACKWARD_CHUNK is None else ", chunk %d" % ops.BACKWARD_CHUNK), sum(t for _, t in reduce) / 1e3, sum(n for n, _ in reduce)))
     print("%s training step (%s, match + criterion + fused optimizer): plain step %.2f ms (context per call; median of %d in a block); "
           "runner.eager() %.2f ms (static context, operands kept by the device), graph replay %.2f ms (medians of %d, alternating; "
           "min %.2f / %.2f); %d device launches per runner.eager() step, 1 graph launch per replay; loss %.4f; peak memory %.2f GB "
