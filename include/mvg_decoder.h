@@ -428,6 +428,20 @@ int mvg_knn_match(const float* poses, const float* joints_3d, const void* num_pe
                   void* workspace, size_t workspace_bytes, int* pair_query, int* pair_gt, int* pair_count, uint8_t* matched,
                   void* stream);
 
+/* mvg_knn_match between predictions with Jp joints per query and a ground truth with Jc joints per person (the Shelf / Campus
+ * joint format, lib/models/dq_transformer.py:90-104: the reference gathers the initial poses with convert_joint_format_indices
+ * before its matcher).  poses (B, NQ*Jp, 3); joints_3d (B, Gmax, Jc, 3); joint_map: Jc HOST ints, converted joint j is prediction
+ * joint joint_map[j]: cost[g][q] = 0.01 * sum_{j < Jc, c} |pose[q][joint_map[j]][c] - gt'[g][j][c]|, j ascending, then c.  The
+ * map travels by value in the launch arguments: no device table, no upload, no further launch; a captured graph keeps the map
+ * it was captured with, as it keeps K.  joint_map NULL = the identity and requires Jc == Jp: that call IS mvg_knn_match, bit
+ * for bit.  Everything else -- norm round trip, tie rules, pair layout, pair_count, matched, workspace -- as mvg_knn_match.
+ * MVG_E_BADARG, nothing launched: an entry repeated or outside [0, Jp), Jp or Jc outside [1, 64], NULL with Jc != Jp, and every
+ * limit of mvg_knn_match. */
+int mvg_knn_match_jm(const float* poses, const float* joints_3d, const void* num_person, int num_person_is64,
+                     const float* space_size, const float* space_center, int method, int K, float value, int B, int NQ, int Gmax,
+                     int Jp, int Jc, const int* joint_map, int Pmax, void* workspace, size_t workspace_bytes, int* pair_query,
+                     int* pair_gt, int* pair_count, uint8_t* matched, void* stream);
+
 /* bytes of the (8-byte aligned) workspace of mvg_criterion: the projected ground truth and the per-(layer, batch) partial sums */
 size_t mvg_criterion_workspace(int L, int B, int Gmax, int V, int J);
 
@@ -453,6 +467,26 @@ int mvg_criterion(const float* logits, const float* poses, const float* poses_2d
                   const float* space_center, float pred_conf_threshold, float focal_alpha, float focal_gamma, int L, int B, int NQ,
                   int J, int V, int Gmax, int Pmax, void* workspace, size_t workspace_bytes, float* table, float* grad_logits,
                   float* grad_poses, float* grad_poses_2d, void* stream);
+
+/* mvg_criterion on predictions with Jp joints per query against a ground truth with Jc joints per person (dq_transformer.py:
+ * 582-594: the reference gathers 3D poses and 2D points with convert_joint_format_indices before SetCriterion, and the gradient
+ * flows back through that gather).  poses (L,B,NQ*Jp,3), poses_2d (L,B,V,NQ*Jp,2); joints_3d, joints_3d_vis (B,Gmax,Jc,3);
+ * joints_vis (V,B,Gmax,Jc,2); joint_map: Jc HOST ints as for mvg_knn_match_jm, by value in the launch arguments.  Every loop over
+ * joints and every divisor that depends on the joint count uses the Jc converted joints; converted joint j reads the prediction
+ * at joint_map[j], and the fp64 sums visit the (query, converted joint, coordinate) elements in the order and with the thread
+ * assignment of a mvg_criterion call on gathered predictions (J = Jc): table and gradients equal that call's bit for bit.
+ * grad_poses / grad_poses_2d keep the inputs' shapes (Jp joints) and are written densely by every call: the term of converted
+ * joint j lands on joint_map[j] (entries are distinct: one writer per element), prediction joints that no entry names get zeros,
+ * and so do unmatched queries.  Workspace: mvg_criterion_workspace(L, B, Gmax, V, Jc).  joint_map NULL = the identity and
+ * requires Jc == Jp: that call IS mvg_criterion, same launches, same bits.  MVG_E_BADARG, nothing launched: as for
+ * mvg_knn_match_jm, and every limit of mvg_criterion. */
+int mvg_criterion_jm(const float* logits, const float* poses, const float* poses_2d, const int* pair_query, const int* pair_gt,
+                     const int* pair_count, const float* joints_3d, const float* joints_3d_vis, const float* joints_vis,
+                     const void* num_person, int num_person_is64, const float* num_samples, const float* cams,
+                     const float* space_size, const float* space_center, float pred_conf_threshold, float focal_alpha,
+                     float focal_gamma, int L, int B, int NQ, int Jp, int Jc, const int* joint_map, int V, int Gmax, int Pmax,
+                     void* workspace, size_t workspace_bytes, float* table, float* grad_logits, float* grad_poses,
+                     float* grad_poses_2d, void* stream);
 
 /* ---- optimizer step (csrc/optim.hip) -------------------------------------------------------------------------------------- */
 #define MVG_OPTIM_CHUNK 4096          /* elements of one tensor that one workgroup handles                                  */

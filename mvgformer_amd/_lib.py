@@ -66,8 +66,10 @@ SIGNATURES = {
     "mvg_sym4_eigh": [_vp] * 3 + [C.c_long, _vp],
     "mvg_knn_match_workspace": [_i] * 3,
     "mvg_knn_match": [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _f] + [_i] * 5 + [_vp, C.c_size_t] + [_vp] * 5,
+    "mvg_knn_match_jm": [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _f] + [_i] * 5 + [_vp, _i, _vp, C.c_size_t] + [_vp] * 5,
     "mvg_criterion_workspace": [_i] * 5,
     "mvg_criterion": [_vp] * 10 + [_i] + [_vp] * 4 + [_f] * 3 + [_i] * 7 + [_vp, C.c_size_t] + [_vp] * 5,
+    "mvg_criterion_jm": [_vp] * 10 + [_i] + [_vp] * 4 + [_f] * 3 + [_i] * 5 + [_vp] + [_i] * 3 + [_vp, C.c_size_t] + [_vp] * 5,
     "mvg_optim_workspace": [_i],
     "mvg_optim_step": [_vp, _i, _vp, _i, _vp, _i, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _f, _i, _vp, _vp],
     "mvg_refresh_operands": [_vp, _i, _vp, _i, _vp],

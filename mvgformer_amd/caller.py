@@ -65,14 +65,15 @@ def level_tables(src_views):
 
 def decoder_outputs_to_dict(hs, inter_references, inter_references_2d, inter_references_2d_projs, outputs_classes,
                             num_instance, num_joints, convert_joint_format_indices=None):
-    """final-layer ``out`` dict of DyanmicQueryTransformer.forward (+ per-layer lists)."""
+    """final-layer ``out`` dict of DyanmicQueryTransformer.forward (+ per-layer lists).  convert_joint_format_indices: a list of
+    ints, or a long tensor on the outputs' device (no host-to-device copy of the indices: usable under graph capture)."""
     batch = hs.shape[1]
     logits = [inverse_sigmoid(c) for c in outputs_classes]
     coords, coords2d, coords2dp = [], [], []
     for lvl in range(hs.shape[0]):
         c3, c2, cp = inter_references[lvl], inter_references_2d[lvl], inter_references_2d_projs[lvl]
         if convert_joint_format_indices is not None:
-            idx = list(convert_joint_format_indices)
+            idx = convert_joint_format_indices if torch.is_tensor(convert_joint_format_indices) else list(convert_joint_format_indices)
             c3 = c3.view(batch, num_instance, num_joints, -1)[..., idx, :].flatten(1, 2)
             nv = c2.shape[1]
             c2 = c2.view(batch, nv, num_instance, num_joints, -1)[..., idx, :].flatten(2, 3)
@@ -111,6 +112,7 @@ class DecoderHead(nn.Module):
         self.instance_embedding = nn.Embedding(num_instance, d_model * 2)
         self.space_size, self.space_center = list(space_size), list(space_center)
         self.convert_joint_format_indices = convert_joint_format_indices
+        self._convert_index = None                 # (indices, the same as a device tensor), made by the first forward_train
         self.criterion, self.decay_method = None, "none"
 
     def set_criterion(self, criterion, decay_method="none"):
@@ -125,12 +127,13 @@ class DecoderHead(nn.Module):
         its joints_vis, on the device.  Returns (out, loss_dict); total_loss(loss_dict, weight_dict).backward() is the step.
         context: a DecoderContext.prepare(...)d context that the caller keeps (training.GraphedTrainStep); the host-side camera
         packing, its H2D copy and the upload of the initial reference points then happen once, not per call, and the forward can
-        be captured in a HIP graph.  None: a context per call, as before."""
+        be captured in a HIP graph.  None: a context per call, as before.
+        With convert_joint_format_indices (Shelf / Campus: ground truth with len(indices) joints, dq_transformer.py:90-104,
+        582-603) the matcher and the criterion get the indices as their joint map and the UNconverted decoder outputs -- there
+        is no gather on the loss path -- and `out` is the converted dict, as in forward."""
         from .decoder import DecoderContext
         if self.criterion is None:
             raise RuntimeError("DecoderHead.forward_train: no criterion (set_criterion / factory.build_training_head)")
-        if self.convert_joint_format_indices is not None:
-            raise NotImplementedError("forward_train with convert_joint_format_indices (Shelf / Campus joint format)")
         dev = src_views[0].device
         V = len(meta)
         batch = src_views[0].shape[0] // V
@@ -147,13 +150,20 @@ class DecoderHead(nn.Module):
                                                 t_pose=self.t_pose)
             if context is not None:
                 ctx._train_ref = ref        # a function of the head's constants alone; nobody writes to it
-        pairs = self.criterion.matcher.match(ref, meta)
+        jmap = self.convert_joint_format_indices
+        pairs = self.criterion.matcher.match(ref, meta, joint_map=jmap, num_joints=self.num_joints)
         hs, refs, refs2d, projs2d, classes = self.decoder(
             tgt.contiguous(), ref, src_views, meta, spatial_shapes, level_start_index, None,
             query_pos=query_pos.contiguous(), indices=pairs[3], threshold=threshold, context=ctx)
-        out = decoder_outputs_to_dict(hs, refs, refs2d, projs2d, classes, self.num_instance, self.num_joints, None)
+        jidx = None
+        if jmap is not None:                       # uploaded once: a captured step must not copy from the host
+            key = tuple(int(i) for i in jmap)
+            if self._convert_index is None or self._convert_index[0] != key or self._convert_index[1].device != dev:
+                self._convert_index = (key, torch.as_tensor(key, dtype=torch.long, device=dev))
+            jidx = self._convert_index[1]
+        out = decoder_outputs_to_dict(hs, refs, refs2d, projs2d, classes, self.num_instance, self.num_joints, jidx)
         loss_dict, _ = criterion_all_layers(self.criterion, torch.stack(out["all_logits"]), refs, refs2d, meta, ref,
-                                            self.decay_method, cams=ctx.cams, pairs=pairs)
+                                            self.decay_method, cams=ctx.cams, pairs=pairs, joint_map=jmap)
         return out, loss_dict
 
     @torch.no_grad()

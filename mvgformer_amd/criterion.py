@@ -7,6 +7,13 @@ per-layer sum of lib/models/dq_transformer.py:653-731) on the fused HIP kernels 
   criterion_all_layers  all decoder layers of a step in one mvg_criterion call: summed dict + dict_losses_layers + loss_init
   total_loss            lib/core/function.py:127-128
 
+Shelf / Campus joint format (DECODER.convert_joint_format_indices of configs/shelf_campus/*.yaml): the decoder's queries keep
+their 15 Panoptic joints, the ground truth has 14.  KNNMatcher.match, SetCriterion.table and criterion_all_layers take the
+indices as `joint_map` and hand them to the kernels (mvg_knn_match_jm / mvg_criterion_jm), which read prediction joint
+joint_map[j] for converted joint j and write the gradients back in the 15-joint shape: no gathered copy of the predictions, no
+index / index_put launch, the same launch counts as without a map.  SetCriterion.forward is the reference's signature: its
+callers pass already converted tensors, it takes no map.
+
 Not built (no shipped YAML uses them): Hungarian assignment, aux_loss / enc_outputs, per-bone and 3D-projection losses, views
 flagged 'padding'.  They raise; nothing falls back to torch or scipy."""
 from __future__ import annotations
@@ -67,13 +74,15 @@ class KNNMatcher(nn.Module):
         self.method, self.method_value = method, method_value
         self.grid_size = self.grid_center = None              # set by SetCriterion, as in the reference
 
-    def match(self, poses, meta, method=None, value=None):
-        """poses (B, NQ*J, 3) abs mm -> (pair_query, pair_gt, pair_count, matched) device tensors; no host synchronisation"""
+    def match(self, poses, meta, method=None, value=None, joint_map=None, num_joints=None):
+        """poses (B, NQ*J, 3) abs mm -> (pair_query, pair_gt, pair_count, matched) device tensors; no host synchronisation.
+        joint_map: the ground truth's joint j is joint joint_map[j] of the poses, which have num_joints joints per query"""
         if self.grid_size is None:
             raise RuntimeError("KNNMatcher.grid_size / grid_center are not set (SetCriterion sets them)")
         return ops.knn_match(poses.float(), meta[0]["joints_3d"].float(), meta[0]["num_person"],
                              [float(v) for v in self.grid_size], [float(v) for v in self.grid_center],
-                             method or self.method, self.method_value if value is None else value)
+                             method or self.method, self.method_value if value is None else value, joint_map=joint_map,
+                             num_joints=num_joints)
 
     @torch.no_grad()
     def forward(self, outputs, meta, method=None, value=None):
@@ -118,9 +127,10 @@ class SetCriterion(nn.Module):
         torch.distributed.all_reduce(n)
         return torch.clamp(n / torch.distributed.get_world_size(), min=1)
 
-    def table(self, logits, poses, poses_2d, pairs, meta, cams=None):
+    def table(self, logits, poses, poses_2d, pairs, meta, cams=None, joint_map=None):
         """(L, 8) loss table (ops.CRITERION_COLUMNS) of L layers against one pair list; differentiable in its first three
-        arguments.  cams: the packed camera records (DecoderContext.cams); packed here from meta if not given."""
+        arguments.  cams: the packed camera records (DecoderContext.cams); packed here from meta if not given.  joint_map: the
+        ground truth's joint j is joint joint_map[j] of poses / poses_2d (unconverted decoder outputs)."""
         _check_meta(meta)
         if cams is None:
             cams = ops.pack_cameras(meta, self.img_size, logits.device)
@@ -130,7 +140,8 @@ class SetCriterion(nn.Module):
         return CriterionFunction.apply(logits.float(), poses.float(), poses_2d.float(), pq, pg, pc, m0["joints_3d"].float(),
                                        m0["joints_3d_vis"].float(), vis2d, m0["num_person"], cams,
                                        [float(v) for v in self.grid_size], [float(v) for v in self.grid_center],
-                                       float(self.pred_conf_threshold), self.num_samples(meta), float(self.focal_alpha), 2.0)
+                                       float(self.pred_conf_threshold), self.num_samples(meta), float(self.focal_alpha), 2.0,
+                                       None if joint_map is None else [int(v) for v in joint_map])
 
     @staticmethod
     def row_to_dict(row):
@@ -148,13 +159,16 @@ class SetCriterion(nn.Module):
         return self.row_to_dict(table[0]), indices
 
 
-def criterion_all_layers(criterion, logits, poses, poses_2d, meta, init_poses, decay_method="none", cams=None, pairs=None):
+def criterion_all_layers(criterion, logits, poses, poses_2d, meta, init_poses, decay_method="none", cams=None, pairs=None,
+                         joint_map=None):
     """The training step's loss dict for gt_match (dq_transformer.py:653-731, loss_for_each_layers): logits (L,B,NQ,2), poses
     (L,B,NQ*J,3), poses_2d (L,B,V,NQ*J,2) of all layers against the match of the initial poses init_poses (B,NQ*J,3) (or the
-    pair list `pairs` if the caller matched already).  One matcher launch and three criterion launches, nothing read back."""
+    pair list `pairs` if the caller matched already).  One matcher launch and three criterion launches, nothing read back.
+    joint_map: the unconverted outputs against a ground truth in another joint format (Shelf / Campus), see the module docstring."""
     if pairs is None:
-        pairs = criterion.matcher.match(init_poses.detach(), meta)
-    table = criterion.table(logits, poses, poses_2d, pairs, meta, cams)
+        pairs = criterion.matcher.match(init_poses.detach(), meta, joint_map=joint_map,
+                                        num_joints=None if joint_map is None else poses.shape[2] // logits.shape[2])
+    table = criterion.table(logits, poses, poses_2d, pairs, meta, cams, joint_map)
     Ln = table.shape[0]
     w = layer_weights(decay_method, Ln, table.device)
     loss_dict = {}

@@ -6,8 +6,14 @@
 //   mvg_knn_match   1 launch : one workgroup per batch element, one wavefront per ground-truth person for the K arg-min rounds
 //   mvg_criterion   3 launches: (A) ground truth -> 2D in all views, (B) one workgroup per (layer, batch element): partial sums,
 //                               counts and the dense gradients, (C) one workgroup: the (L, 8) table
+//   mvg_knn_match_jm / mvg_criterion_jm: the same launches with a joint map between predictions and ground truth (below)
 // The losses are tiny (B x NQ x 2 logits, at most B x G x K pairs), so (A)-(C) evaluate them in fp64 from the fp32 inputs; the
 // matcher keeps the reference's fp32 arithmetic (the selection must be the one an fp32 cdist gives).
+//
+// Joint map (Shelf / Campus joint format, dq_transformer.py:90-104, 582-594): the predictions have Jp joints per query, the ground
+// truth Jc, and converted joint j is prediction joint map[j].  The map travels by value in the launch arguments (JointMap); every
+// loop and divisor below runs over the Jc converted joints, prediction reads and gradient writes go through the map.  The
+// kernels are templates on MAPPED: the instantiation without a map (Jp == Jc, identity) is the code as it was before the map.
 #include <math.h>
 
 #include "common.h"
@@ -22,6 +28,9 @@
 
 struct SpaceBox {
   float size[3], center[3];
+};
+struct JointMap {
+  uint8_t m[64];               // m[j] = prediction joint of converted joint j, j < Jc
 };
 
 // absolute -> norm -> absolute exactly as matcher.py:65-78 rounds it in fp32 (no contraction into FMAs)
@@ -54,26 +63,30 @@ __device__ __forceinline__ void wave_argmin(float& c, int& q) {
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
-// matcher.  cost[g][q] = 0.01 * sum_{3J} |pose[q] - gt'[g]| (torch.cdist(p=1), matcher.py:165-169).
+// matcher.  cost[g][q] = 0.01 * sum_{3J} |pose[q] - gt'[g]| (torch.cdist(p=1), matcher.py:165-169); J = the Jc joints of the
+// ground truth, pose joint map[j] against ground-truth joint j when MAPPED (poses then have Jp joints per query).
 //   KNN     : the K smallest-cost queries of every person, pair slot g * K + k (person-major, ascending cost, ties to the lower
 //             query index); pair_count = G * K.
 //   multiple: every query whose nearest person (ties to the lower person index) is closer than `value`, in ascending query order
 //             (matcher.py:201-230: torch.where order); pair_count <= NQ.
+template <bool MAPPED>
 __global__ __launch_bounds__(CRIT_THREADS) void knn_match_kernel(const float* __restrict__ poses, const float* __restrict__ gt,
                                                                  const void* __restrict__ num_person, int np_is64, SpaceBox box,
                                                                  int method, int K, float value, int NQ, int Gmax, int J, int Pmax,
                                                                  float* __restrict__ cost_ws, int* __restrict__ pair_query,
                                                                  int* __restrict__ pair_gt, int* __restrict__ pair_count,
-                                                                 uint8_t* __restrict__ matched) {
+                                                                 uint8_t* __restrict__ matched, int Jp, JointMap map) {
   __shared__ float cost_lds[KNN_LDS_COSTS];
   __shared__ float gt_lds[64 * 3];
   __shared__ int wave_cnt[CRIT_WAVES];
   __shared__ int base_cnt;
+  __shared__ int s_map3[MAPPED ? 64 : 1];                        // 3 * map[j]: the float offset of converted joint j in a query
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & (MVG_WAVE - 1), wave = tid / MVG_WAVE;
+  if (MAPPED && tid < J) s_map3[tid] = 3 * (int)map.m[tid];      // visible after the first barrier of the person loop
   long Gl = load_count(num_person, np_is64, b);
   const int G = (int)(Gl < 0 ? 0 : (Gl > Gmax ? Gmax : Gl));
   float* cost = ((long)NQ * Gmax <= KNN_LDS_COSTS) ? cost_lds : cost_ws + (long)b * NQ * Gmax;
-  const float* pb = poses + (long)b * NQ * J * 3;
+  const float* pb = poses + (long)b * NQ * (MAPPED ? Jp : J) * 3;
   const float* gb = gt + (long)b * Gmax * J * 3;
   int* pq = pair_query + (long)b * Pmax;
   int* pg = pair_gt + (long)b * Pmax;
@@ -91,9 +104,16 @@ __global__ __launch_bounds__(CRIT_THREADS) void knn_match_kernel(const float* __
       gt_lds[e] = norm_round_trip_f32(gb[(long)g * J * 3 + e], box.size[e % 3], box.center[e % 3]);
     __syncthreads();
     for (int q = tid; q < NQ; q += CRIT_THREADS) {
-      const float* x = pb + (long)q * J * 3;
+      const float* x = pb + (long)q * (MAPPED ? Jp : J) * 3;
       float s = 0.f;
-      for (int e = 0; e < J * 3; ++e) s += fabsf(x[e] - gt_lds[e]);
+      if (MAPPED) {
+        for (int j = 0; j < J; ++j) {
+          const float* xj = x + s_map3[j];
+          for (int c = 0; c < 3; ++c) s += fabsf(xj[c] - gt_lds[j * 3 + c]);
+        }
+      } else {
+        for (int e = 0; e < J * 3; ++e) s += fabsf(x[e] - gt_lds[e]);
+      }
       s *= 0.01f;
       cost[(long)g * NQ + q] = (s < INFINITY) ? s : INFINITY;    // NaN / inf poses sort last
     }
@@ -217,8 +237,8 @@ __device__ __forceinline__ double block_sum(double v, double* scratch) {
 
 struct CritArgs {
   const float* logits;        // (L, B, NQ, 2)
-  const float* poses;         // (L, B, NQ*J, 3)
-  const float* poses_2d;      // (L, B, V, NQ*J, 2)
+  const float* poses;         // (L, B, NQ*Jp, 3)
+  const float* poses_2d;      // (L, B, V, NQ*Jp, 2)
   const int* pair_query;      // (B, Pmax)
   const int* pair_gt;         // (B, Pmax)
   const int* pair_count;      // (B,)
@@ -233,20 +253,38 @@ struct CritArgs {
   float* g_poses;
   float* g_poses_2d;
   SpaceBox box;
-  int np_is64, L, B, NQ, J, V, Gmax, Pmax;
+  int np_is64, L, B, NQ, J, V, Gmax, Pmax;       // J: joints of the ground truth (Jc)
   float conf_thr, alpha, gamma;
+  int Jp;                     // joints per query of the predictions and their gradients; read by the MAPPED kernel only
+  JointMap map;
 };
 
 // (B) one workgroup per (layer, batch element).  part[l][b] = {sum focal, sum 3D L1, sum 2D L1, pairs classified right, pairs
 // recalled, predicted positives, true positives, predictions over the threshold}; the three gradients with their final scale.
+// MAPPED: the two pose loops still run over the (query, converted joint, coordinate) elements in the same order and with the same
+// thread assignment as a call on gathered predictions would, so the fp64 sums are the same; only the address of the prediction
+// read and of the gradient write goes through the map.  Prediction joints that no map entry names are zeroed in a pass of their
+// own: every gradient element has exactly one writer.
+template <bool MAPPED>
 __global__ __launch_bounds__(CRIT_THREADS) void crit_layer_kernel(CritArgs a) {
   __shared__ short s_pq[CRIT_MAX_PAIRS], s_pg[CRIT_MAX_PAIRS], s_next[CRIT_MAX_PAIRS];
   __shared__ short s_first[CRIT_MAX_NQ];
   __shared__ int s_off[CRIT_MAX_B + 1];
   __shared__ double s_red[CRIT_WAVES];
   __shared__ double s_ns;
+  __shared__ int s_map[MAPPED ? 64 : 1];         // converted joint -> prediction joint
+  __shared__ int s_named[MAPPED ? 64 : 1];       // prediction joint -> 1 if a map entry names it
   const int l = blockIdx.x / a.B, b = blockIdx.x % a.B, tid = threadIdx.x;
   const int NQ = a.NQ, J = a.J, V = a.V, B = a.B;
+  const int Jp = MAPPED ? a.Jp : J;
+  if (MAPPED) {                                  // visible after the barriers below
+    if (tid < 64) s_named[tid] = 0;
+    __syncthreads();
+    if (tid < J) {
+      s_map[tid] = a.map.m[tid];
+      s_named[a.map.m[tid]] = 1;                 // entries are distinct: one writer per element
+    }
+  }
 
   if (tid == 0) {
     int off = 0;
@@ -325,32 +363,37 @@ __global__ __launch_bounds__(CRIT_THREADS) void crit_layer_kernel(CritArgs a) {
   }
 
   // ---- per-joint 3D L1 on the matched pairs (:653-696, loss.py:87-97); prediction as is, target = norm round trip
-  const float* ps = a.poses + ((long)l * B + b) * NQ * J * 3;
-  float* gps = a.g_poses + ((long)l * B + b) * NQ * J * 3;
+  const float* ps = a.poses + ((long)l * B + b) * NQ * Jp * 3;
+  float* gps = a.g_poses + ((long)l * B + b) * NQ * Jp * 3;
   const double sc3 = 1.0 / ns / (double)(J * 3);
   double s_3d = 0.0;
   for (int e = tid; e < NQ * J * 3; e += CRIT_THREADS) {
     const int c = e % 3, j = (e / 3) % J, q = e / (3 * J);
+    const int ep = MAPPED ? (q * Jp + s_map[j]) * 3 + c : e;      // the element of the prediction and of its gradient
     double g = 0.0;
     for (int p = s_first[q]; p >= 0; p = s_next[p]) {
       const long gi = (((long)b * a.Gmax + s_pg[p]) * J + j) * 3;
       const double w = a.vis3d[gi];                                // joints_3d_vis[..., 0:1]
       const double tg = norm_round_trip_f64(a.gt[gi + c], a.box.size[c], a.box.center[c]);
-      const double d = (double)ps[e] * w - tg * w;
+      const double d = (double)ps[ep] * w - tg * w;
       s_3d += fabs(d);
       g += (d > 0.0 ? w : (d < 0.0 ? -w : 0.0));
     }
-    gps[e] = (float)(g * sc3);
+    gps[ep] = (float)(g * sc3);
   }
+  if (MAPPED && J < Jp)
+    for (int e = tid; e < NQ * Jp * 3; e += CRIT_THREADS)
+      if (!s_named[(e / 3) % Jp]) gps[e] = 0.f;
 
   // ---- 2D L1 against the projected ground truth (:732-772, loss.py:245-297).  Row r = pair * V + view of the pair-major
   // predictions is weighted by row r of the VIEW-major weights: view r / P, pair r % P over the pairs of the whole batch.
-  const float* p2 = a.poses_2d + ((long)l * B + b) * V * NQ * J * 2;
-  float* gp2 = a.g_poses_2d + ((long)l * B + b) * V * NQ * J * 2;
+  const float* p2 = a.poses_2d + ((long)l * B + b) * V * NQ * Jp * 2;
+  float* gp2 = a.g_poses_2d + ((long)l * B + b) * V * NQ * Jp * 2;
   const double sc2 = 1.0 / (ns * (double)V) / (double)(J * 2);
   double s_2d = 0.0;
   for (long e = tid; e < (long)V * NQ * J * 2; e += CRIT_THREADS) {
     const int c = (int)(e & 1), j = (int)((e >> 1) % J), q = (int)((e >> 1) / J % NQ), v = (int)((e >> 1) / ((long)J * NQ));
+    const long ep = MAPPED ? (((long)v * NQ + q) * Jp + s_map[j]) * 2 + c : e;
     double g = 0.0;
     for (int p = s_first[q]; p >= 0; p = s_next[p]) {
       const long r = (long)(s_off[b] + p) * V + v;
@@ -361,12 +404,15 @@ __global__ __launch_bounds__(CRIT_THREADS) void crit_layer_kernel(CritArgs a) {
       double w = 0.0;
       if (gw >= 0 && gw < a.Gmax) w = a.vis2d[((((long)vw * B + bw) * a.Gmax + gw) * J + j) * 2];   // joints_vis[..., 0:1]
       const double tg = a.gt2d[((((long)b * a.Gmax + s_pg[p]) * V + v) * J + j) * 2 + c];
-      const double d = (double)p2[e] * w - tg * w;
+      const double d = (double)p2[ep] * w - tg * w;
       s_2d += fabs(d);
       g += (d > 0.0 ? w : (d < 0.0 ? -w : 0.0));
     }
-    gp2[e] = (float)(g * sc2);
+    gp2[ep] = (float)(g * sc2);
   }
+  if (MAPPED && J < Jp)
+    for (long e = tid; e < (long)V * NQ * Jp * 2; e += CRIT_THREADS)
+      if (!s_named[(int)((e >> 1) % Jp)]) gp2[e] = 0.f;
 
   double* out = a.part + ((long)l * B + b) * CRIT_PART;
   const double r0 = block_sum(s_ce, s_red), r1 = block_sum(s_3d, s_red), r2 = block_sum(s_2d, s_red);
@@ -411,6 +457,21 @@ __global__ __launch_bounds__(CRIT_THREADS) void crit_final_kernel(const double* 
   }
 }
 
+// joint_map (Jc HOST ints, distinct, inside [0, Jp)) -> the by-value table; NULL = the identity, Jc == Jp.  0 on a bad map.
+static int pack_joint_map(int Jp, int Jc, const int* joint_map, JointMap* out) {
+  if (Jp < 1 || Jp > 64 || Jc < 1 || Jc > 64) return 0;
+  for (int j = 0; j < 64; ++j) out->m[j] = 0;
+  if (!joint_map) return Jc == Jp;
+  bool seen[64] = {};
+  for (int j = 0; j < Jc; ++j) {
+    const int m = joint_map[j];
+    if (m < 0 || m >= Jp || seen[m]) return 0;
+    seen[m] = true;
+    out->m[j] = (uint8_t)m;
+  }
+  return 1;
+}
+
 extern "C" {
 
 size_t mvg_knn_match_workspace(int B, int NQ, int Gmax) {
@@ -418,13 +479,14 @@ size_t mvg_knn_match_workspace(int B, int NQ, int Gmax) {
   return ((long)NQ * Gmax <= KNN_LDS_COSTS) ? 0 : (size_t)B * NQ * Gmax * sizeof(float);
 }
 
-int mvg_knn_match(const float* poses, const float* joints_3d, const void* num_person, int num_person_is64, const float* space_size,
-                  const float* space_center, int method, int K, float value, int B, int NQ, int Gmax, int J, int Pmax,
-                  void* workspace, size_t workspace_bytes, int* pair_query, int* pair_gt, int* pair_count, uint8_t* matched,
-                  void* stream) {
+int mvg_knn_match_jm(const float* poses, const float* joints_3d, const void* num_person, int num_person_is64,
+                     const float* space_size, const float* space_center, int method, int K, float value, int B, int NQ, int Gmax,
+                     int Jp, int Jc, const int* joint_map, int Pmax, void* workspace, size_t workspace_bytes, int* pair_query,
+                     int* pair_gt, int* pair_count, uint8_t* matched, void* stream) {
   if (!poses || !joints_3d || !num_person || !space_size || !space_center || !pair_query || !pair_gt || !pair_count || !matched)
     return MVG_E_BADARG;
-  if (B < 1 || NQ < 1 || Gmax < 1 || Gmax > 64 || J < 1 || J > 64) return MVG_E_BADARG;
+  JointMap map;
+  if (B < 1 || NQ < 1 || Gmax < 1 || Gmax > 64 || !pack_joint_map(Jp, Jc, joint_map, &map)) return MVG_E_BADARG;
   if (method == MVG_MATCH_KNN) {
     if (K < 1 || K > 16 || K > NQ || Pmax < Gmax * K) return MVG_E_BADARG;
   } else if (method == MVG_MATCH_MULTIPLE) {
@@ -439,11 +501,24 @@ int mvg_knn_match(const float* poses, const float* joints_3d, const void* num_pe
     box.size[i] = space_size[i];
     box.center[i] = space_center[i];
   }
-  hipLaunchKernelGGL(knn_match_kernel, dim3(B), dim3(CRIT_THREADS), 0, (hipStream_t)stream, poses, joints_3d, num_person,
-                     num_person_is64, box, method, K, value, NQ, Gmax, J, Pmax, (float*)workspace, pair_query, pair_gt, pair_count,
-                     matched);
+  if (joint_map)
+    hipLaunchKernelGGL(knn_match_kernel<true>, dim3(B), dim3(CRIT_THREADS), 0, (hipStream_t)stream, poses, joints_3d, num_person,
+                       num_person_is64, box, method, K, value, NQ, Gmax, Jc, Pmax, (float*)workspace, pair_query, pair_gt,
+                       pair_count, matched, Jp, map);
+  else
+    hipLaunchKernelGGL(knn_match_kernel<false>, dim3(B), dim3(CRIT_THREADS), 0, (hipStream_t)stream, poses, joints_3d, num_person,
+                       num_person_is64, box, method, K, value, NQ, Gmax, Jc, Pmax, (float*)workspace, pair_query, pair_gt,
+                       pair_count, matched, Jp, map);
   MVG_LAUNCH_CHECK();
   return 0;
+}
+
+int mvg_knn_match(const float* poses, const float* joints_3d, const void* num_person, int num_person_is64, const float* space_size,
+                  const float* space_center, int method, int K, float value, int B, int NQ, int Gmax, int J, int Pmax,
+                  void* workspace, size_t workspace_bytes, int* pair_query, int* pair_gt, int* pair_count, uint8_t* matched,
+                  void* stream) {
+  return mvg_knn_match_jm(poses, joints_3d, num_person, num_person_is64, space_size, space_center, method, K, value, B, NQ, Gmax,
+                          J, J, nullptr, Pmax, workspace, workspace_bytes, pair_query, pair_gt, pair_count, matched, stream);
 }
 
 size_t mvg_criterion_workspace(int L, int B, int Gmax, int V, int J) {
@@ -451,20 +526,22 @@ size_t mvg_criterion_workspace(int L, int B, int Gmax, int V, int J) {
   return ((size_t)B * Gmax * V * J * 2 + (size_t)L * B * CRIT_PART) * sizeof(double);
 }
 
-int mvg_criterion(const float* logits, const float* poses, const float* poses_2d, const int* pair_query, const int* pair_gt,
-                  const int* pair_count, const float* joints_3d, const float* joints_3d_vis, const float* joints_vis,
-                  const void* num_person, int num_person_is64, const float* num_samples, const float* cams, const float* space_size,
-                  const float* space_center, float pred_conf_threshold, float focal_alpha, float focal_gamma, int L, int B, int NQ,
-                  int J, int V, int Gmax, int Pmax, void* workspace, size_t workspace_bytes, float* table, float* grad_logits,
-                  float* grad_poses, float* grad_poses_2d, void* stream) {
+int mvg_criterion_jm(const float* logits, const float* poses, const float* poses_2d, const int* pair_query, const int* pair_gt,
+                     const int* pair_count, const float* joints_3d, const float* joints_3d_vis, const float* joints_vis,
+                     const void* num_person, int num_person_is64, const float* num_samples, const float* cams,
+                     const float* space_size, const float* space_center, float pred_conf_threshold, float focal_alpha,
+                     float focal_gamma, int L, int B, int NQ, int Jp, int Jc, const int* joint_map, int V, int Gmax, int Pmax,
+                     void* workspace, size_t workspace_bytes, float* table, float* grad_logits, float* grad_poses,
+                     float* grad_poses_2d, void* stream) {
+  const int J = Jc;
   if (!logits || !poses || !poses_2d || !pair_query || !pair_gt || !pair_count || !joints_3d || !joints_3d_vis || !joints_vis ||
       !num_person || !cams || !space_size || !space_center || !workspace || !table || !grad_logits || !grad_poses || !grad_poses_2d)
     return MVG_E_BADARG;
-  if (L < 1 || B < 1 || B > CRIT_MAX_B || NQ < 1 || NQ > CRIT_MAX_NQ || J < 1 || J > 64 || V < 1 || Gmax < 1 || Gmax > 64 ||
-      Pmax < 1 || Pmax > CRIT_MAX_PAIRS)
+  CritArgs a;
+  if (L < 1 || B < 1 || B > CRIT_MAX_B || NQ < 1 || NQ > CRIT_MAX_NQ || !pack_joint_map(Jp, Jc, joint_map, &a.map) || V < 1 ||
+      Gmax < 1 || Gmax > 64 || Pmax < 1 || Pmax > CRIT_MAX_PAIRS)
     return MVG_E_BADARG;
   if (workspace_bytes < mvg_criterion_workspace(L, B, Gmax, V, J) || ((uintptr_t)workspace & 7)) return MVG_E_BADARG;
-  CritArgs a;
   a.logits = logits; a.poses = poses; a.poses_2d = poses_2d;
   a.pair_query = pair_query; a.pair_gt = pair_gt; a.pair_count = pair_count;
   a.gt = joints_3d; a.vis3d = joints_3d_vis; a.vis2d = joints_vis;
@@ -477,18 +554,33 @@ int mvg_criterion(const float* logits, const float* poses, const float* poses_2d
     a.box.size[i] = space_size[i];
     a.box.center[i] = space_center[i];
   }
-  a.L = L; a.B = B; a.NQ = NQ; a.J = J; a.V = V; a.Gmax = Gmax; a.Pmax = Pmax;
+  a.L = L; a.B = B; a.NQ = NQ; a.J = J; a.V = V; a.Gmax = Gmax; a.Pmax = Pmax; a.Jp = Jp;
   a.conf_thr = pred_conf_threshold; a.alpha = focal_alpha; a.gamma = focal_gamma;
   const long total = (long)B * Gmax * V * J;
   hipLaunchKernelGGL(crit_project_gt_kernel, dim3(mvg_ceil_div(total, CRIT_THREADS)), dim3(CRIT_THREADS), 0, (hipStream_t)stream,
                      joints_3d, cams, a.box, gt2d, B, Gmax, V, J, total);
   MVG_LAUNCH_CHECK();
-  hipLaunchKernelGGL(crit_layer_kernel, dim3(L * B), dim3(CRIT_THREADS), 0, (hipStream_t)stream, a);
+  if (joint_map)
+    hipLaunchKernelGGL(crit_layer_kernel<true>, dim3(L * B), dim3(CRIT_THREADS), 0, (hipStream_t)stream, a);
+  else
+    hipLaunchKernelGGL(crit_layer_kernel<false>, dim3(L * B), dim3(CRIT_THREADS), 0, (hipStream_t)stream, a);
   MVG_LAUNCH_CHECK();
   hipLaunchKernelGGL(crit_final_kernel, dim3(1), dim3(CRIT_THREADS), 0, (hipStream_t)stream, (const double*)a.part, pair_count,
                      num_person, num_person_is64, num_samples, table, L, B, NQ, J, V, Pmax);
   MVG_LAUNCH_CHECK();
   return 0;
+}
+
+int mvg_criterion(const float* logits, const float* poses, const float* poses_2d, const int* pair_query, const int* pair_gt,
+                  const int* pair_count, const float* joints_3d, const float* joints_3d_vis, const float* joints_vis,
+                  const void* num_person, int num_person_is64, const float* num_samples, const float* cams, const float* space_size,
+                  const float* space_center, float pred_conf_threshold, float focal_alpha, float focal_gamma, int L, int B, int NQ,
+                  int J, int V, int Gmax, int Pmax, void* workspace, size_t workspace_bytes, float* table, float* grad_logits,
+                  float* grad_poses, float* grad_poses_2d, void* stream) {
+  return mvg_criterion_jm(logits, poses, poses_2d, pair_query, pair_gt, pair_count, joints_3d, joints_3d_vis, joints_vis, num_person,
+                          num_person_is64, num_samples, cams, space_size, space_center, pred_conf_threshold, focal_alpha,
+                          focal_gamma, L, B, NQ, J, J, nullptr, V, Gmax, Pmax, workspace, workspace_bytes, table, grad_logits,
+                          grad_poses, grad_poses_2d, stream);
 }
 
 }  // extern "C"

@@ -84,12 +84,15 @@ def build_criterion_from_cfg(cfg):
 
 
 def build_training_head(cfg, decoder=None, t_pose=None):
-    """caller.DecoderHead around the cfg's decoder with the cfg's criterion set: forward_train is ready.  Returns (head, weight_dict)."""
+    """caller.DecoderHead around the cfg's decoder with the cfg's criterion set: forward_train is ready.  Returns (head, weight_dict).
+    DECODER.convert_joint_format_indices (the shelf_campus YAMLs) becomes the head's joint map: forward_train then takes ground
+    truth with that many joints."""
     from .caller import DecoderHead
     d = cfg.DECODER
     decoder = build_decoder_from_cfg(cfg) if decoder is None else decoder
+    conv = getattr(d, "convert_joint_format_indices", None)
     head = DecoderHead(decoder, d.num_instance, d.num_keypoints, d.d_model, cfg.MULTI_PERSON.SPACE_SIZE, cfg.MULTI_PERSON.SPACE_CENTER,
-                       t_pose=t_pose)
+                       convert_joint_format_indices=None if conv is None else [int(i) for i in conv], t_pose=t_pose)
     criterion, weight_dict, decay = build_criterion_from_cfg(cfg)
     head.set_criterion(criterion, decay)
     return head, weight_dict

@@ -208,14 +208,14 @@ class CriterionFunction(Function):
     """(L, 8) loss table of ops.criterion (columns ops.CRITERION_COLUMNS) for all decoder layers of one step.  The kernels
     produce the gradients of loss_ce, loss_pose_perjoint and loss_pose_perprojection_2d in the forward pass; backward scales them
     per layer by the table's grad_output (the 2D term also by keep_2d: a guarded layer gives a zero gradient).  The metric columns
-    carry no gradient."""
+    carry no gradient.  joint_map (not differentiable): ops.criterion's; the pose gradients keep the predictions' joint count."""
 
     @staticmethod
     def forward(ctx, logits, poses, poses_2d, pair_query, pair_gt, pair_count, joints_3d, joints_3d_vis, joints_vis, num_person,
-                cams, space_size, space_center, pred_conf_threshold, num_samples, focal_alpha, focal_gamma):
+                cams, space_size, space_center, pred_conf_threshold, num_samples, focal_alpha, focal_gamma, joint_map=None):
         table, gl, gp, gp2 = ops.criterion(logits, poses, poses_2d, pair_query, pair_gt, pair_count, joints_3d, joints_3d_vis,
                                            joints_vis, num_person, cams, space_size, space_center, pred_conf_threshold,
-                                           num_samples, focal_alpha, focal_gamma)
+                                           num_samples, focal_alpha, focal_gamma, joint_map=joint_map)
         ctx.save_for_backward(gl, gp, gp2, table)
         return table
 
@@ -229,4 +229,4 @@ class CriterionFunction(Function):
         g_logits = gl * g[:, 0].view(-1, 1, 1, 1)
         g_poses = gp * g[:, 5].view(-1, 1, 1, 1)
         g_2d = torch.where(keep.view(-1, 1, 1, 1, 1), gp2 * g[:, 6].view(-1, 1, 1, 1, 1), zero)
-        return (g_logits, g_poses, g_2d) + (None,) * 14
+        return (g_logits, g_poses, g_2d) + (None,) * 15

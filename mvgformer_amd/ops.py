@@ -924,22 +924,46 @@ def _count_tensor(num_person, B):
     return num_person.contiguous(), int(num_person.dtype == torch.int64)
 
 
-def knn_match(poses, joints_3d, num_person, space_size, space_center, method="KNN", value=5):
+def _joint_map_arg(joint_map, Jp, joints_3d, what):
+    """joint_map (Jc distinct ints inside [0, Jp): converted joint j is prediction joint joint_map[j]) -> the host int array the
+    *_jm entry points take, checked against the joint counts before the library sees it; None stays None (the identity)"""
+    if joint_map is None:
+        return None
+    jm = [int(v) for v in joint_map]
+    if Jp is None or Jp < 1 or Jp > 64:
+        raise ValueError("%s: joint_map needs the joints per query of the predictions (1..64), got %r" % (what, Jp))
+    if not jm or len(jm) > 64:
+        raise ValueError("%s: joint_map must hold 1..64 entries, got %d" % (what, len(jm)))
+    if len(set(jm)) != len(jm):
+        raise ValueError("%s: joint_map repeats an entry: %r" % (what, jm))
+    if min(jm) < 0 or max(jm) >= Jp:
+        raise ValueError("%s: joint_map entries must lie in [0, %d): %r" % (what, Jp, jm))
+    if joints_3d.dim() != 4 or joints_3d.shape[2] != len(jm):
+        raise RuntimeError("%s: joints_3d %s does not have the %d joints of joint_map" % (what, tuple(joints_3d.shape), len(jm)))
+    return (C.c_int * len(jm))(*jm)
+
+
+def knn_match(poses, joints_3d, num_person, space_size, space_center, method="KNN", value=5, joint_map=None, num_joints=None):
     """poses (B, NQ*J, 3) abs mm, joints_3d (B, Gmax, J, 3) abs mm, num_person (B,) -> pair_query, pair_gt (B, Pmax) int32 (-1 in
     unused slots), pair_count (B,) int32, matched (B, NQ) uint8 (mvg_knn_match: one launch, nothing read back).  method 'KNN'
-    (value = K, Pmax = Gmax*K) or 'multiple' (value = cost threshold, Pmax = NQ)."""
+    (value = K, Pmax = Gmax*K) or 'multiple' (value = cost threshold, Pmax = NQ).
+    joint_map (Shelf / Campus joint format, mvg_knn_match_jm): Jc distinct ints, converted joint j is prediction joint
+    joint_map[j]; poses then are (B, NQ*Jp, 3) with Jp = num_joints (poses alone do not tell NQ from Jp) and joints_3d
+    (B, Gmax, Jc, 3).  Still one launch; the map is a launch argument."""
     if method in ("hungarian", "hungarian-dis"):
         raise NotImplementedError("match method %r: the Hungarian assignment is not built (no shipped YAML uses it)" % method)
     if method not in MATCH_METHODS:
         raise ValueError("unknown match method %r" % (method,))
+    jm = _joint_map_arg(joint_map, num_joints, joints_3d, "mvg_knn_match_jm")
     L.require_cuda(poses, joints_3d, num_person)
     if poses.dtype != torch.float32 or joints_3d.dtype != torch.float32 or joints_3d.dim() != 4 or joints_3d.shape[-1] != 3 \
             or poses.dim() != 3 or poses.shape[-1] != 3 or poses.shape[0] != joints_3d.shape[0]:
         raise RuntimeError("mvg_knn_match: poses (B, NQ*J, 3) / joints_3d (B, Gmax, J, 3) float32 expected")
     B, Gmax, J = joints_3d.shape[:3]
-    if poses.shape[1] % J:
-        raise RuntimeError("mvg_knn_match: poses rows (%d) are not a multiple of J = %d" % (poses.shape[1], J))
-    NQ = poses.shape[1] // J
+    Jp = J if jm is None else int(num_joints)
+    if poses.shape[1] % Jp:
+        raise RuntimeError("mvg_knn_match: poses rows (%d) are not a multiple of J = %d" % (poses.shape[1], Jp))
+    NQ = poses.shape[1] // Jp
     num_person, is64 = _count_tensor(num_person, B)
     poses, joints_3d = poses.detach().contiguous(), joints_3d.contiguous()
     knn = method == "KNN"
@@ -954,18 +978,31 @@ def knn_match(poses, joints_3d, num_person, space_size, space_center, method="KN
     nbytes = lib.mvg_knn_match_workspace(B, NQ, Gmax)
     ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev) if nbytes else None
     with _timed("knn_match"):
-        L.check(lib.mvg_knn_match(L.ptr(poses), L.ptr(joints_3d), L.ptr(num_person), is64, _host3(space_size), _host3(space_center),
-                                  MATCH_METHODS[method], K, float(value), B, NQ, Gmax, J, Pmax, L.ptr(ws), nbytes, L.ptr(pq),
-                                  L.ptr(pg), L.ptr(pc), L.ptr(matched), L.stream_ptr()), "mvg_knn_match")
+        if jm is None:
+            L.check(lib.mvg_knn_match(L.ptr(poses), L.ptr(joints_3d), L.ptr(num_person), is64, _host3(space_size),
+                                      _host3(space_center), MATCH_METHODS[method], K, float(value), B, NQ, Gmax, J, Pmax, L.ptr(ws),
+                                      nbytes, L.ptr(pq), L.ptr(pg), L.ptr(pc), L.ptr(matched), L.stream_ptr()), "mvg_knn_match")
+        else:
+            L.check(lib.mvg_knn_match_jm(L.ptr(poses), L.ptr(joints_3d), L.ptr(num_person), is64, _host3(space_size),
+                                         _host3(space_center), MATCH_METHODS[method], K, float(value), B, NQ, Gmax, Jp, J, jm, Pmax,
+                                         L.ptr(ws), nbytes, L.ptr(pq), L.ptr(pg), L.ptr(pc), L.ptr(matched), L.stream_ptr()),
+                    "mvg_knn_match_jm")
     return pq, pg, pc, matched
 
 
 def criterion(logits, poses, poses_2d, pair_query, pair_gt, pair_count, joints_3d, joints_3d_vis, joints_vis, num_person, cams,
-              space_size, space_center, pred_conf_threshold, num_samples=None, focal_alpha=0.25, focal_gamma=2.0):
+              space_size, space_center, pred_conf_threshold, num_samples=None, focal_alpha=0.25, focal_gamma=2.0, joint_map=None):
     """All layers' losses, metrics and gradients in three launches (mvg_criterion).  logits (L,B,NQ,2), poses (L,B,NQ*J,3),
     poses_2d (L,B,V,NQ*J,2) fp32; the pair list of knn_match; joints_3d / joints_3d_vis (B,Gmax,J,3), joints_vis (V,B,Gmax,J,2)
     fp32; cams = pack_cameras(...).  -> table (L, 8) fp32 in the order of CRITERION_COLUMNS, grad_logits, grad_poses,
-    grad_poses_2d (shaped like the inputs; the 2D gradient is the unguarded one, to be multiplied by keep_2d)."""
+    grad_poses_2d (shaped like the inputs; the 2D gradient is the unguarded one, to be multiplied by keep_2d).
+    joint_map (Shelf / Campus joint format, mvg_criterion_jm): Jc distinct ints, converted joint j is prediction joint
+    joint_map[j]; poses / poses_2d keep their Jp joints per query, the ground truth has Jc.  The losses are those of the
+    gathered predictions, the gradients come back in the Jp shape (zeros at joints the map does not name).  Still three launches."""
+    Jp = None
+    if joint_map is not None and logits.dim() == 4 and poses.dim() == 4 and logits.shape[2] and poses.shape[2] % logits.shape[2] == 0:
+        Jp = poses.shape[2] // logits.shape[2]
+    jm = _joint_map_arg(joint_map, Jp, joints_3d, "mvg_criterion_jm")
     tensors = (logits, poses, poses_2d, pair_query, pair_gt, pair_count, joints_3d, joints_3d_vis, joints_vis, num_person, cams)
     L.require_cuda(*tensors, num_samples)
     if any(t.dtype != torch.float32 for t in (logits, poses, poses_2d, joints_3d, joints_3d_vis, joints_vis, cams)):
@@ -978,7 +1015,8 @@ def criterion(logits, poses, poses_2d, pair_query, pair_gt, pair_count, joints_3
     Gmax, J = joints_3d.shape[1:3]
     V = poses_2d.shape[2]
     Pmax = pair_query.shape[-1]
-    if (tuple(poses.shape) != (Ln, B, NQ * J, 3) or tuple(poses_2d.shape) != (Ln, B, V, NQ * J, 2)
+    Jp = J if jm is None else Jp
+    if (tuple(poses.shape) != (Ln, B, NQ * Jp, 3) or tuple(poses_2d.shape) != (Ln, B, V, NQ * Jp, 2)
             or tuple(joints_3d.shape) != (B, Gmax, J, 3) or tuple(joints_3d_vis.shape) != (B, Gmax, J, 3)
             or tuple(joints_vis.shape) != (V, B, Gmax, J, 2) or tuple(pair_query.shape) != (B, Pmax)
             or tuple(pair_gt.shape) != (B, Pmax) or pair_count.numel() != B or tuple(cams.shape) != (V * B, L.CAM_STRIDE)):
@@ -996,12 +1034,20 @@ def criterion(logits, poses, poses_2d, pair_query, pair_gt, pair_count, joints_3
     table = torch.empty((Ln, len(CRITERION_COLUMNS)), dtype=torch.float32, device=dev)
     gl, gp, gp2 = torch.empty_like(logits), torch.empty_like(poses), torch.empty_like(poses_2d)
     with _timed("criterion"):
-        L.check(lib.mvg_criterion(L.ptr(logits), L.ptr(poses), L.ptr(poses_2d), L.ptr(pair_query), L.ptr(pair_gt), L.ptr(pair_count),
-                                  L.ptr(joints_3d), L.ptr(joints_3d_vis), L.ptr(joints_vis), L.ptr(num_person), is64,
-                                  L.ptr(num_samples), L.ptr(cams), _host3(space_size), _host3(space_center),
-                                  float(pred_conf_threshold), float(focal_alpha), float(focal_gamma), Ln, B, NQ, J, V, Gmax, Pmax,
-                                  L.ptr(ws), nbytes, L.ptr(table), L.ptr(gl), L.ptr(gp), L.ptr(gp2), L.stream_ptr()),
-                "mvg_criterion")
+        if jm is None:
+            L.check(lib.mvg_criterion(L.ptr(logits), L.ptr(poses), L.ptr(poses_2d), L.ptr(pair_query), L.ptr(pair_gt),
+                                      L.ptr(pair_count), L.ptr(joints_3d), L.ptr(joints_3d_vis), L.ptr(joints_vis), L.ptr(num_person),
+                                      is64, L.ptr(num_samples), L.ptr(cams), _host3(space_size), _host3(space_center),
+                                      float(pred_conf_threshold), float(focal_alpha), float(focal_gamma), Ln, B, NQ, J, V, Gmax, Pmax,
+                                      L.ptr(ws), nbytes, L.ptr(table), L.ptr(gl), L.ptr(gp), L.ptr(gp2), L.stream_ptr()),
+                    "mvg_criterion")
+        else:
+            L.check(lib.mvg_criterion_jm(L.ptr(logits), L.ptr(poses), L.ptr(poses_2d), L.ptr(pair_query), L.ptr(pair_gt),
+                                         L.ptr(pair_count), L.ptr(joints_3d), L.ptr(joints_3d_vis), L.ptr(joints_vis),
+                                         L.ptr(num_person), is64, L.ptr(num_samples), L.ptr(cams), _host3(space_size),
+                                         _host3(space_center), float(pred_conf_threshold), float(focal_alpha), float(focal_gamma),
+                                         Ln, B, NQ, Jp, J, jm, V, Gmax, Pmax, L.ptr(ws), nbytes, L.ptr(table), L.ptr(gl), L.ptr(gp),
+                                         L.ptr(gp2), L.stream_ptr()), "mvg_criterion_jm")
     return table, gl, gp, gp2
 
 

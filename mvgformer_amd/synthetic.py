@@ -360,3 +360,16 @@ def add_ground_truth(case, num_person, Gmax=10, seed=0):
     for m in case.meta:
         m["joints_vis"] = torch.from_numpy(np.repeat((rs.rand(B, Gmax, J, 1) > 0.15).astype(np.float32), 2, -1)).to(dev)
     return case
+
+
+def convert_ground_truth(case, joint_map):
+    """The targets of add_ground_truth in another joint format (Shelf / Campus: DECODER.convert_joint_format_indices), in place:
+    converted joint j is joint joint_map[j] of the synthetic persons, so joints_3d / joints_3d_vis become (B, Gmax, Jc, 3) and
+    every view's joints_vis (B, Gmax, Jc, 2) with Jc = len(joint_map)."""
+    idx = [int(i) for i in joint_map]
+    m0 = case.meta[0]
+    m0["joints_3d"] = m0["joints_3d"][:, :, idx].contiguous()
+    m0["joints_3d_vis"] = m0["joints_3d_vis"][:, :, idx].contiguous()
+    for m in case.meta:
+        m["joints_vis"] = m["joints_vis"][:, :, idx].contiguous()
+    return case

@@ -86,7 +86,7 @@ def npz_frames(path):
         src = [torch.from_numpy(z["feat%d" % l][f]) for l in range(L)]
         meta = []
         for v in range(V):
-            cam = {k: torch.from_numpy(z["camera_" + k][f, v])[None] for k in ("R", "T", "fx", "fy", "cx", "cy", "k", "p")}
+            cam = {k: torch.from_numpy(np.asarray(z["camera_" + k][f, v]))[None] for k in ("R", "T", "fx", "fy", "cx", "cy", "k", "p")}
             meta.append(dict(camera=cam, center=torch.from_numpy(z["center"][f, v])[None],
                              scale=torch.from_numpy(z["scale"][f, v])[None],
                              inv_affine_trans=torch.from_numpy(z["inv_affine_trans"][f, v])[None]))
@@ -97,6 +97,26 @@ def npz_frames(path):
 def to_device(meta, device):
     mv = lambda t: t.to(device)
     return [{k: ({kk: mv(vv) for kk, vv in v.items()} if isinstance(v, dict) else mv(v)) for k, v in m.items()} for m in meta]
+
+
+def actor_ground_truth(gts, gts_vis):
+    """per-frame ground truth (G, 14, 3) + visibility -> evaluate_pcp's actor_gts: person slot g is actor g, and an actor is not
+    annotated (None) in a frame where its visibility is all zero"""
+    n_actor = max(len(g) for g in gts)
+    return [[np.asarray(g[a], np.float64) if a < len(g) and np.any(np.asarray(v[a]) != 0) else None for g, v in zip(gts, gts_vis)]
+            for a in range(n_actor)]
+
+
+def pcp_report(kept, gts, gts_vis):
+    """the PCP entry of a result row (Shelf.evaluate / Campus.evaluate through evaluate.evaluate_pcp), in percent"""
+    from . import evaluate as E
+    try:
+        actor, avg, bones, recall = E.evaluate_pcp(kept, actor_ground_truth(gts, gts_vis))
+    except ValueError as e:            # a frame with ground truth in which no prediction passed the classification filter
+        return {"error": str(e)}
+    return {"actor": [round(100 * float(a), 2) for a in actor], "average": round(100 * float(avg), 2),
+            "bones": {k: [round(100 * float(x), 2) for x in v] for k, v in bones.items()},
+            "recall500": round(100 * float(recall), 2)}
 
 
 def main(argv=None):
@@ -184,7 +204,10 @@ def main(argv=None):
                "poses_after_nms": int(sum(len(k) for k in kept)),
                "decoder_ms_per_frame": round(1e3 * t_dec / max(n_timed, 1), 3),    # host-timed, incl. the camera H2D copy
                "hip_graph": runner is not None}
-        if gts and getattr(cfg.DECODER, "convert_joint_format_indices", None) is None:
+        if gts and getattr(cfg.DECODER, "convert_joint_format_indices", None) is not None:
+            if np.asarray(gts[0]).shape[-2] == len(cfg.DECODER.convert_joint_format_indices):
+                row["PCP"] = pcp_report(kept, gts, gts_vis)                       # shelf.py:255-330
+        elif gts:
             aps, recs, mpjpe, recall500 = E.evaluate_panoptic(kept, gts, gts_vis)   # panoptic.py:493-574
             row.update(AP={str(t): round(100 * a, 2) for t, a in zip(E.MPJPE_THRESHOLDS, aps)},
                        recall={str(t): round(100 * r, 2) for t, r in zip(E.MPJPE_THRESHOLDS, recs)},
