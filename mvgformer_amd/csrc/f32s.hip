@@ -376,7 +376,7 @@ __global__ __launch_bounds__(NT, MT == 1 ? 4 : 2) void chain_a_f32h_small_kernel
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
           const float v = __builtin_ldexpf(acc[mt][4 * g + t], un) + bvr[g][t];
-          y[mt][g][t] = st == 0 ? (keep[mt] ? v : 0.f) : fmaxf(v, 0.f);
+          y[mt][g][t] = st == 0 ? (keep[mt] ? v : 0.f) : relu_keep_nan(v);     // a NaN row of attn stays NaN down to o (chain B's NaN rows ride on the residual t1)
           m[mt] = fmaxf(m[mt], fabsf(y[mt][g][t]));
         }
       if (st == 0 && grow[mt] >= 0) {

@@ -29,6 +29,9 @@ __device__ __forceinline__ int row_scale(float m) {
   return min(13 - e, 100);
 }
 
+// ReLU that keeps a NaN (fmaxf(NaN, 0) is 0, which would turn a NaN row back into a finite one): IEEE 754-2019 maximum, one v_maximum3_f32
+__device__ __forceinline__ float relu_keep_nan(float v) { return __builtin_elementwise_maximum(v, 0.f); }
+
 // 4 fp32, already scaled -> (h, l) as two 8-byte packs of 4 fp16
 __device__ __forceinline__ void split4_h2(const f32x4& xs, uint2& ph, uint2& pl) {
   const half2_t h0 = {(_Float16)xs[0], (_Float16)xs[1]}, h1 = {(_Float16)xs[2], (_Float16)xs[3]};

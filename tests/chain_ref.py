@@ -23,12 +23,35 @@ past the values themselves.  The pieces (all typical sizes):
             arithmetic of the kernels' LayerNorm carried as input error.
 Tests compare with the returned bounds as they are and print max |err| / bound; a test that uses lin_err / ln_err directly
 multiplies by LAMBDA itself.
+
+The fp32 kernels on two-part fp16 operands (csrc/f32s.hip, "f32h": pyramid_f32h, chain_a_f32h, chain_b_f32h below).  The truth
+is the plain fp64 operation with NO operand rounding; the bound says how far a kernel that forms every product as
+  x 2^s = h + l,  h = fp16(x 2^s),  l = fp16(x 2^s - h)   (split_h2; s = row_scale of the row maximum, one s per weight tensor),
+  a w ~ 2^-(s_a + s_w) (l_a h_w + h_a l_w + h_a h_w),      fp32 accumulation of the 3 K terms, exact ldexpf, + bias
+may be from it.  The constants come from the fp16 format (11 significand bits, normal down to 2^-14, subnormal spacing 2^-24):
+  H2_LL   2^-22 |a w|: the dropped l_a l_w (|l| <= 2^-11 |x 2^s|: half a unit in the last place of h);
+  H2_PART 2^-23 |x|:   x 2^s - h - l, half a unit in the last place of l (|l| < 2^-11 |h|'s binade);
+  H2_SUB  2^-24 2^-s:  where x 2^s - h falls into fp16's subnormal range (entries under 2^-16 of the maximum) the rounding of l
+          is absolute, half the subnormal spacing 2^-25 in scaled units -- times 2 because the kernel takes s from the maximum of
+          ITS row, which may sit in the binade under the reference's (the reference takes s from max (|x| + dx)).  With
+          2^-s <= 2^-13 max|row| this is 2^-37 of the row / tensor maximum; for rows under 2^-87 (s capped at 100) it is 2^-124.
+Where worst case, where typical size: H2_LL / H2_PART / H2_SUB are WORST-case sizes of one product term's error; the K terms of
+a dot product are combined as independent errors (root sum of squares, lin_err_h2), times LAMBDA.  No sqrt(K) averaging is assumed
+for a row: a heavy-tailed row, whose sum is one term, gets that term's worst case times LAMBDA.  The fp32 accumulation is
+lin_err's, over 3 K + 1 terms.  Rounding points of the chains (the errors carried on through prop / ln_err):
+  chain A  the planes of samp, of h0 and of h1 (re-split after ReLU, s from the row maximum over the eight wavefronts' partial
+           maxima); attn is stored as the exact fp32 stage result; the 3-output layer runs in fp32 on the fp32 h1.
+  chain B  the planes of the view mean (fp32 sum over the views in order, divided by (float)V); the planes of t1 as the FFN operand
+           (the fp32 t1 stays the residual); the planes of each 256-column hidden chunk with a row scale of its own, the four
+           chunk results added in fp32; the planes of tgt' + query_pos for the next layer's term.  LayerNorms, sigmoid and the
+           joint mean as in chain_b.
 """
 import torch
 
 U32 = 2.0 ** -24          # fp32 unit roundoff
 LN_EPS = 1e-5
 LAMBDA = 8.0
+H2_LL, H2_PART, H2_SUB = 2.0 ** -22, 2.0 ** -23, 2.0 ** -24      # two-part fp16 operands, see the module notes
 
 
 def bf(x, on=True):
@@ -164,4 +187,103 @@ def chain_b(attn, tgt, Wu, bu, g2, be2, W1, b1, W2, b2, g3, be3, Wc, bc, thresho
             x = t + (0 if qpos is None else qpos.double())
             exb = round_err(x, et + U32 * x.abs())
             out["xw_err"] = LAMBDA * lin_err(xb, exb, Wn, bn)[:, :n_next]
+    return out
+
+
+# ------------------------------------------------------------------------------------- two-part fp16 operands (csrc/f32s.hip)
+def row_scale(m):
+    """f32s_dev.h::row_scale: min(13 - exponent(m), 100) from the fp32 bit pattern of m >= 0 (zero / subnormal maxima: 100)."""
+    e = ((m.float().contiguous().view(torch.int32) >> 23) & 0xFF) - 127
+    return torch.clamp(13 - e, max=100)
+
+
+def weight_scale(W):
+    """the tensor scale ops.split_swizzle_weight_h2 returns: row_scale of max |W| within [-100, 100]; 0 for a zero / non-finite maximum."""
+    m = W.detach().float().abs().max()
+    if not (bool(m > 0) and bool(torch.isfinite(m))):
+        return 0
+    return int(row_scale(m).clamp(min=-100))
+
+
+def split_h2(x, s):
+    """(h, l) as f32s_dev.h::split4_h2 and ops.split_swizzle_weight_h2 form them: fp16(x 2^s) and fp16(x 2^s - h), fp32 arithmetic.
+    s: int or an integer tensor that broadcasts against x."""
+    xs = torch.ldexp(x.float(), torch.as_tensor(s, device=x.device))
+    h = xs.to(torch.float16)
+    return h, (xs - h.float()).to(torch.float16)
+
+
+def lin_err_h2(x, dx, W, b=None, w_scale=None):
+    """typical size of the error of  x W^T + b  formed on two-part fp16 operands with fp32 accumulation (module notes), the
+    input off by at most dx (None: exact).  w_scale: the scale of the tensor W is a block of (default: W's own)."""
+    K = W.shape[1]
+    x, Wd = x.double(), W.double()
+    ax, aW = x.abs(), Wd.abs()
+    sq = (x ** 2) @ (Wd ** 2).t()
+    acc = U32 * (3 * K + 1) ** 0.5 * torch.sqrt(sq + (0 if b is None else b.double() ** 2)) + U32 * lin(x, W, b).abs()
+    m = (ax if dx is None else ax + dx.double()).amax(-1, keepdim=True)
+    qx = H2_SUB * torch.ldexp(torch.ones_like(m), -row_scale(m).double())               # absolute part of an activation entry
+    qw = H2_SUB * 2.0 ** -(weight_scale(W) if w_scale is None else w_scale)              # ... of a weight entry
+    c = H2_LL + 2 * H2_PART
+    # sum over k of (c |x w| + qx |w| + |x| qw)^2, expanded
+    op2 = (c * c * sq + qx ** 2 * (Wd ** 2).sum(1) + qw ** 2 * (x ** 2).sum(-1, keepdim=True)
+           + 2 * c * qx * (ax @ (Wd ** 2).t()) + 2 * c * qw * ((x ** 2) @ aW.t()) + 2 * qx * qw * (ax @ aW.t()))
+    e = acc + torch.sqrt(op2)
+    return e if dx is None else e + prop(dx, W)
+
+
+def pyramid_f32h(feat, Wv, bv, Wg):
+    """value = feat Wv^T + bv, G = feat Wg^T (fp64) and the bounds of mvg_pyramid_f32h: dict(value, G, value_err, G_err)."""
+    return dict(value=lin(feat, Wv, bv), G=lin(feat, Wg), value_err=LAMBDA * lin_err_h2(feat, None, Wv, bv),
+                G_err=LAMBDA * lin_err_h2(feat, None, Wg))
+
+
+def chain_a_f32h(samp, inside, Wp, bp, W0, b0, W1, b1, W2, b2, bounds=True):
+    """chain A in fp64 (chain_a, no rounding) with the bounds of mvg_chain_attn_pose_f32h: attn_err, o_err."""
+    out = chain_a(samp, inside, Wp, bp, W0, b0, W1, b1, W2, b2)
+    if bounds:
+        keep = inside.double().view(-1, 1) != 0
+        ea = torch.where(keep, lin_err_h2(samp, None, Wp, bp), torch.zeros((), dtype=torch.float64, device=samp.device))
+        e0 = lin_err_h2(out["attn"], ea, W0, b0)                   # ReLU does not enlarge an error
+        e1 = lin_err_h2(out["h0"], e0, W1, b1)
+        out["attn_err"] = LAMBDA * ea
+        out["o_err"] = LAMBDA * lin_err(out["h1"], e1, W2, b2)
+    return out
+
+
+def chain_b_f32h(attn, tgt, Wu, bu, g2, be2, W1, b1, W2, b2, g3, be3, Wc, bc, threshold, J, has_ffn=True, forced=None,
+                 qpos=None, Wn=None, bn=None, n_next=0, bounds=True):
+    """chain B in fp64 (chain_b, no rounding) with the bounds of mvg_chain_update_ffn_class_f32h: tgt_err, prob_err[, xw_err]."""
+    out = chain_b(attn, tgt, Wu, bu, g2, be2, W1, b1, W2, b2, g3, be3, Wc, bc, threshold, J, has_ffn=has_ffn, forced=forced,
+                  qpos=qpos, Wn=Wn, bn=bn, n_next=n_next)
+    if not bounds:
+        return out
+    V = attn.shape[0]
+    a, tg = attn.double(), tgt.double()
+    m, t1, t = out["mean"], out["t1"], out["tgt"]
+    dm = (V + 2) * U32 * a.abs().mean(0)
+    u = tg + lin(m, Wu, bu)
+    et1 = ln_err(u, lin_err_h2(m, dm, Wu, bu) + U32 * (tg.abs() + u.abs()), g2)
+    if has_ffn:
+        hid = torch.relu(lin(t1, W1, b1))
+        eh = lin_err_h2(t1, et1, W1, b1)
+        s2 = weight_scale(W2)
+        e2sq, part = 0, 0
+        for c in range(0, W2.shape[1], 256):                        # one row scale per 256-column chunk, the results added in fp32
+            e2sq = e2sq + lin_err_h2(hid[:, c:c + 256], eh[:, c:c + 256], W2[:, c:c + 256], None, w_scale=s2) ** 2
+            part = part + lin(hid[:, c:c + 256], W2[:, c:c + 256]).abs()
+        y = t1 + lin(hid, W2, b2)
+        ey = et1 + torch.sqrt(e2sq) + U32 * (part + (y - t1).abs() + t1.abs() + y.abs())
+        et = ln_err(y, ey, g3)
+    else:
+        et = et1
+    sg = torch.sigmoid(lin(t, Wc, bc))
+    el = lin_err(t, et, Wc, bc)
+    es = (sg * (1 - sg) + el).clamp(max=0.25) * el + 4 * U32 * sg
+    out["tgt_err"] = LAMBDA * et
+    # the J rows of a person carry independent errors (each row its own operand roundings and sums): root sum of squares / J
+    out["prob_err"] = LAMBDA * (torch.sqrt((es ** 2).view(-1, J, 2).sum(1)) / J + (J + 1) * U32 * out["prob"])
+    if Wn is not None:
+        x = t + (0 if qpos is None else qpos.double())
+        out["xw_err"] = LAMBDA * lin_err_h2(x, et + U32 * x.abs(), Wn, bn)[:, :n_next]
     return out

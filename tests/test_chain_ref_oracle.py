@@ -10,8 +10,12 @@ from tests import chain_ref as R
 from tests.golden.cases import LAYER_CASES
 
 
-@pytest.mark.parametrize("cname", ["mini5_half", "mini5_b2"])
-def test_chain_statements_match_the_oracle_layer(cname):
+ORACLE_CASES = ["mini5_half", "mini5_b2"]
+
+
+def check_statements_against_oracle_layer(cname, chain_a, chain_b):
+    """one oracle layer against the chain statements `chain_a` / `chain_b` (signatures of chain_ref.chain_a / chain_b, rounding
+    off); tests/test_f32h_ref_cpu.py sends the f32h statements down the same route."""
     spec = LAYER_CASES[cname]
     case = build_case(spec["config"], B=spec.get("B", 1), seed=spec["seed"], NQ=spec.get("NQ"), layers=spec.get("layers"),
                       valid_fraction=spec.get("valid_fraction"))
@@ -30,7 +34,7 @@ def test_chain_statements_match_the_oracle_layer(cname):
     ffn = [P(n) for n in ("feature_update_mlp.weight", "feature_update_mlp.bias", "norm2.weight", "norm2.bias", "linear1.weight",
                           "linear1.bias", "linear2.weight", "linear2.bias", "norm3.weight", "norm3.bias",
                           "class_embed.weight", "class_embed.bias")]
-    b = R.chain_b(attn, case.tgt.reshape(rows, C).double(), *ffn, thr, J)
+    b = chain_b(attn, case.tgt.reshape(rows, C).double(), *ffn, thr, J)
     assert float((b["tgt"] - hs.reshape(rows, C)).abs().max()) < 1e-12
     assert float((b["prob"] - prob.reshape(-1, 2)).abs().max()) < 1e-14
     assert torch.equal(b["valid"], (prob[..., 1] > thr).reshape(-1))
@@ -47,8 +51,8 @@ def test_chain_statements_match_the_oracle_layer(cname):
         src_v = [s[v * B:(v + 1) * B].double() for s in case.src_views]
         _, it = O.proj_attn_forward(pa, "layers.0.proj_attn.", case.tgt.double() + case.query_pos.double(), r.unsqueeze(2) * WH / (WH - 1),
                                     src_v, case.spatial_shapes, case.level_start_index, return_intermediates=True)
-        a = R.chain_a(it["sampled"].reshape(rows, C), inside.reshape(rows), P("proj_attn.output_proj.weight"),
-                      P("proj_attn.output_proj.bias"), *pose)
+        a = chain_a(it["sampled"].reshape(rows, C), inside.reshape(rows), P("proj_attn.output_proj.weight"),
+                    P("proj_attn.output_proj.bias"), *pose)
         assert float((a["attn"] - attn[v]).abs().max()) < 1e-12
         assert int((inside.reshape(rows) == 0).sum()) > 0 and bool((a["attn"][inside.reshape(rows) == 0] == 0).all())
         ref2d = (r.reshape(rows, 2) + a["o"][:, :2] / img) * img
@@ -56,6 +60,11 @@ def test_chain_statements_match_the_oracle_layer(cname):
         logits.append(a["o"][:, 2])
     conf = torch.softmax(torch.stack(logits, 0), 0)
     assert float((conf - ex["conf"].transpose(0, 1).reshape(V, rows)).abs().max()) < 1e-14
+
+
+@pytest.mark.parametrize("cname", ORACLE_CASES)
+def test_chain_statements_match_the_oracle_layer(cname):
+    check_statements_against_oracle_layer(cname, R.chain_a, R.chain_b)
 
 
 def test_bf16_bounds_cover_an_fp32_emulation_of_the_kernels():

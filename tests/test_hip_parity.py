@@ -1941,7 +1941,7 @@ def test_pyramid_products_on_two_part_fp16_operands():
 
 def test_fp32_chains_on_two_part_fp16_operands():
     """mvg_chain_attn_pose_f32h / mvg_chain_update_ffn_class_f32h (three fp16 MFMAs per product, per-row scales exchanged between the
-    wavefronts) against fp64, with the bars tools/check_f32s.py applies to the six-product kernels; masked rows of mixed tiles equal the
+    wavefronts) against fp64 with whole-tensor bars (elementwise derived bounds, shapes and edges: tests/test_f32h_fp64.py); masked rows of mixed tiles equal the
     cached constant bit for bit; a row's result does not depend on its tile (rows permuted / a second launch with other neighbours)."""
     from mvgformer_amd import ops
     gen = torch.Generator().manual_seed(33)

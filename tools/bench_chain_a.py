@@ -37,6 +37,19 @@ def graph_time(fn, n=20, reps=10):
     return s.elapsed_time(e) / (n * reps) * 1e3
 
 
+if "--fp32" in sys.argv:
+    # the fp32 chain A on two-part fp16 operands (mvg_chain_attn_pose_f32h) at cfg-2: 5 views x 1024 queries x 15 joints, 2 / 3 in-image
+    rows = 5 * 1024 * 15
+    pl = [ops.split_swizzle_weight_h2(torch.randn(256, 256, device=dev) / 16) for _ in range(3)]
+    samp = torch.randn(rows, 256, device=dev)
+    inside = (torch.arange(rows, device=dev) % 3 != 0).to(torch.uint8)
+    args = (pl[0][0], pl[0][1], bp, pl[1][0], pl[1][1], b0, pl[2][0], pl[2][1], b1, W2, b2)
+    om = ops.chain_masked_row_output_f32h(*args)
+    order = torch.argsort(1 - inside.int(), stable=True).to(torch.int32)
+    t = graph_time(lambda: ops.chain_attn_pose_f32h(samp, inside, *args, order=order, o_masked=om))
+    print("chain A fp32 (f32h) cfg-2 %6d rows: %6.1f us" % (rows, t))
+    sys.exit(0)
+
 tiles = [int(a) for a in sys.argv[1:]] or [128, 256, 384, 448, 512, 513, 520, 540, 600, 640, 768, 1024]
 print("# chain A, every row live; 128-row tiles, 2 workgroups per CU -> 512 resident tiles")
 for nt in tiles:
