@@ -539,6 +539,22 @@ int mvg_optim_step(const void* tensor_table, int n_tensors, const void* chunk_ta
  * launches nothing.  MVG_E_BADARG for negative counts, NULL or unaligned tables. */
 int mvg_refresh_operands(const void* record_table, int n_records, const void* tile_table, int n_tiles, void* stream);
 
+/* ---- query self-attention (csrc/mha.hip) ------------------------------------------------------------------------------------ */
+/* The attention of nn.MultiheadAttention between its in- and out-projection (DQDecoderLayer.self_attn with init_self_attention,
+ * dq_decoder.py:281-283,532-539), flash-style: no Lq x Lq matrix in memory, online softmax with a running maximum and sum per
+ * query row.  q, k, v: (B, Lq, C) `dtype` with element strides (Lq * ld, ld, 1), ld = ldq / ldk / ldv >= C -- head h in columns
+ * 32 h .. 32 h + 31, no transposed copies; so the three may be column blocks of one wider projection output.  out (B, Lq, C)
+ * `dtype`, contiguous:  out[b,i,h,:] = sum_j softmax_j(q[b,i,h] . k[b,j,h] / sqrt(32)) v[b,j,h,:]; nothing crosses b.
+ *   MVG_BF16: bf16 MFMA products with fp32 accumulation; scores, maximum, sum and rescale fp32; P rounded to bf16 only as the
+ *             operand of P V; out rounded once.
+ *   MVG_F32 : fp32 MFMA products (k-ordered fp32 fma chains: the reference's arithmetic class, valid at every input range).
+ * Finite inputs only (a NaN / Inf spreads over every row that reads it); finite results for any finite scores, rows of equal
+ * scores included.  One launch, no workspace, no atomics, a fixed reduction order: bit-identical from run to run, and rows of one
+ * batch element do not depend on the others.  MVG_E_BADARG, nothing launched: C != 256, M != 8, B or Lq < 1, B > 65535,
+ * Lq > 2^24, a NULL or not 16-byte aligned pointer, ld < C or not a multiple of 16 bytes. */
+int mvg_self_attention(const void* q, const void* k, const void* v, void* out, int ldq, int ldk, int ldv, int B, int Lq, int C, int M,
+                       int dtype, void* stream);
+
 /* ---- serving post-processing (csrc/nms.hip) -------------------------------------------------------------------------------- */
 #define MVG_NMS_MAX_N 2048            /* candidates rows per batch element                                                    */
 #define MVG_NMS_MAX_J 32

@@ -74,6 +74,7 @@ SIGNATURES = {
     "mvg_optim_step": [_vp, _i, _vp, _i, _vp, _i, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _f, _i, _vp, _vp],
     "mvg_refresh_operands": [_vp, _i, _vp, _i, _vp],
     "mvg_pose_nms_workspace": [_i] * 3,
+    "mvg_self_attention": [_vp] * 4 + [_i] * 8 + [_vp],
     "mvg_pose_nms": [_vp, _i, _i, _i, C.c_double, _i, _i, _vp, C.c_size_t, _vp, _vp, _vp, _i, _vp],
 }
 

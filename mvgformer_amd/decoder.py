@@ -248,7 +248,8 @@ class DQDecoderLayer(MvPDecoderLayer):
         fp32-accurate GEMMs.  torch.bfloat16: mixed precision -- bf16 GEMM operands with fp32 accumulation, fp32 master weights and
         fp32 gradients, a bf16 value for the sampling op (rounding points: forward_autograd).  LayerNorm, softmax, dropout, sigmoid
         and all geometry stay fp32 / fp64.  The native inference path, compute_dtype, GraphedDecoder and the query-sharded
-        runners do not read it.  torch.autocast is NOT consulted: this switch alone selects the bf16 path."""
+        runners do not read it.  torch.autocast is NOT consulted: this switch alone selects the bf16 path.  The self-attention block
+        of init_self_attention stays fp32 either way (_attend_queries_autograd): its bf16 training is not built."""
         if dtype not in (torch.float32, torch.bfloat16):
             raise ValueError("training dtype must be float32 or bfloat16")
         self.training_dtype = dtype
@@ -259,8 +260,11 @@ class DQDecoderLayer(MvPDecoderLayer):
         bad = None
         if self.feature_update_method != "MLP":
             bad = "feature_update_method=%r" % self.feature_update_method
-        elif self.init_self_attention:
-            bad = "init_self_attention=True"
+            if self.feature_update_method.startswith("attention"):
+                bad += " (the attention* feature updates of dq_decoder.py:779-830 are not built)"
+        elif self.init_self_attention and (self.d_model != 256 or self.self_attn.num_heads != 8):
+            bad = "init_self_attention=True with d_model=%d, nhead=%d (the attention kernel is built for 256 / 8)" \
+                % (self.d_model, self.self_attn.num_heads)
         elif self.open_bayesian_update:
             bad = "bayesian_update=True"
         elif self.triangulation_method not in ("linalg", "batch", "default", "cpu"):
@@ -274,10 +278,10 @@ class DQDecoderLayer(MvPDecoderLayer):
         elif not self.proj_attn.fused_supported(3):
             bad = "ProjAttn geometry (need d_model=256, nhead=8, dec_n_points=8, num_feature_levels=1)"
         if bad:
-            # cross-query variants couple the queries and are not built
-            raise NotImplementedError("DQDecoderLayer: %s is outside the built hot path (the shipped YAMLs use "
-                                      "feature_update_method='MLP', init_self_attention=False, "
-                                      "triangulation_method='linalg', bayesian_update=False)" % bad)
+            # of the cross-query variants only init_self_attention is built (attend_queries)
+            raise NotImplementedError("DQDecoderLayer: %s is outside the built hot path (feature_update_method='MLP', "
+                                      "init_self_attention=False | True, triangulation_method='linalg', "
+                                      "bayesian_update=False)" % bad)
 
     def _w(self, key, params, dtype, build=None):
         return self._wc.get(key, params, dtype, build)
@@ -392,12 +396,51 @@ class DQDecoderLayer(MvPDecoderLayer):
         return ("bf16" if a16 else "f32h" if (a32 and C == 256) else None,
                 "bf16" if (b16 and C == 256 and J <= 64) else "f32h" if (b32 and C == 256) else None)
 
+    def _self_attn_weights(self, dt):
+        """cached operands of attend_queries: ([Wq; Wk] (512, C), its bias, Wv, its bias, out_proj weight, bias, norm2 weight, bias)"""
+        f32 = torch.float32
+        sa, C = self.self_attn, self.d_model
+        if sa.in_proj_weight is None or sa.in_proj_bias is None or sa.bias_k is not None:
+            raise NotImplementedError("DQDecoderLayer: self_attn with separate projection weights, without bias or with bias_k / "
+                                      "bias_v is not built")
+        return (self._w("sa_Wqk", (sa.in_proj_weight,), dt, lambda w: w[:2 * C]), self._w("sa_bqk", (sa.in_proj_bias,), f32, lambda b: b[:2 * C]),
+                self._w("sa_Wv", (sa.in_proj_weight,), dt, lambda w: w[2 * C:]), self._w("sa_bv", (sa.in_proj_bias,), f32, lambda b: b[2 * C:]),
+                self._w("sa_Wo", (sa.out_proj.weight,), dt), self._w("sa_bo", (sa.out_proj.bias,), f32),
+                self._w("g2", (self.norm2.weight,), f32), self._w("b2", (self.norm2.bias,), f32))
+
+    def attend_queries(self, tgt, query_pos):
+        """The block init_self_attention puts at the head of the layer (dq_decoder.py:532-539), eval mode, on the native kernels:
+            norm2(tgt + out_proj(attention(Wq x, Wk x, Wv tgt))),  x = tgt + query_pos
+        over the Lq = NQ * J tokens of each batch element -- (B, Lq, C) fp32.  In-projection ([Wq; Wk] as one 512-wide product with
+        the sum folded into its load; Wv) and out_proj on mvg_linear in the compute dtype, the attention on mvg_self_attention
+        (csrc/mha.hip) where the projections lie, the residual + LayerNorm on mvg_add_layernorm.  In the reference the result is a
+        local of generate_features: it stands in for tgt in the projective attention's query and nowhere else (forward_features)."""
+        if not tgt.is_cuda:
+            raise RuntimeError("Not implemented on the CPU")
+        B, Lq, C = tgt.shape
+        dt = self.compute_dtype
+        Wqk, bqk, Wv, bv, Wo, bo, g2, b2 = self._self_attn_weights(dt)
+        t32 = tgt.float().reshape(B * Lq, C).contiguous()
+        if query_pos is None:
+            qk = ops.linear(t32, Wqk, bqk, out_dtype=dt)
+        elif query_pos.shape == tgt.shape:
+            qk = ops.linear(t32, Wqk, bqk, out_dtype=dt, add=query_pos.float().reshape(B * Lq, C).contiguous())
+        else:
+            qk = ops.linear((tgt.float() + query_pos.float()).reshape(B * Lq, C).contiguous(), Wqk, bqk, out_dtype=dt)
+        v = ops.linear(t32, Wv, bv, out_dtype=dt)
+        qk = qk.view(B, Lq, 2 * C)
+        a = ops.self_attention(qk[..., :C], qk[..., C:], v.view(B, Lq, C))
+        o = ops.linear(a.view(B * Lq, C), Wo, bo, out_dtype=dt)
+        return ops.add_layernorm(t32, o, g2, b2).view(B, Lq, C)
+
     def _next_query_term(self, nxt, path_b, tgt, query_pos, levels):
         """operands with which this layer's fused chain B also computes xw = (tgt' + query_pos) W^T + b, the query term of the next layer
         `nxt` (its rows are in LDS): (qp, W, b, n) for the bf16 chain, (qp, W, scale, b, n) for the f32h one; None: not taken"""
         dt = self.compute_dtype
         if nxt is None or nxt.compute_dtype != dt or not (query_pos is None or query_pos.shape == tgt.shape):
             return None
+        if nxt.init_self_attention:
+            return None         # its query is attend_queries(tgt') + query_pos: tgt' + query_pos is not what it projects
         if not (nxt._fuses_chains_f32(dt, tgt.shape[1], levels)[0] if path_b == "f32h" else
                 nxt.use_fused_chains and nxt.proj_attn.uses_fast_path(dt)):
             return None
@@ -413,6 +456,8 @@ class DQDecoderLayer(MvPDecoderLayer):
         and stay unwritten until the first replay -- WeightCache.get refuses to do that.  DQDecoder calls this before
         it forks its side stream, the sharded runners (mvgformer_amd.dist) before they capture."""
         dt = dtype or self.compute_dtype
+        if self.init_self_attention:
+            self._self_attn_weights(dt)
         if self.proj_attn.uses_fast_path(dt):
             self.proj_attn.prepare_fast_path(dt)
         else:
@@ -530,7 +575,7 @@ class DQDecoderLayer(MvPDecoderLayer):
         if self.detach_refpoints_cameraprj:
             X = X.detach()                                                    # dq_decoder.py:338-339
         WH = src_spatial_shapes.flip(-1).float()
-        x = self.with_pos_embed(tgt, query_pos)
+        x = self.with_pos_embed(self._attend_queries_autograd(tgt, query_pos) if self.init_self_attention else tgt, query_pos)
         # Per-forward constants of the geometry (packed camera records, level table, projection matrices): built once and kept on the
         # DecoderContext when the layer runs inside DQDecoder.forward -- as torch ops per layer they were ~40 launches each.
         ctx = (self._run or _NO_RUN).ctx
@@ -607,11 +652,28 @@ class DQDecoderLayer(MvPDecoderLayer):
         proj2d_o = torch.where(vm2, proj2d.view(B, V, NQ, J, 2), zero).reshape(B, V, Lq, 2)
         return tgt_update, new_ref, ref2d_o, proj2d_o, prob
 
+    def _attend_queries_autograd(self, tgt, query_pos):
+        """attend_queries as differentiable torch ops through the layer's own self_attn module (dq_decoder.py:532-539): torch's
+        attention op with need_weights=False (no Lq x Lq probabilities are returned or kept for the caller), attention dropout
+        and dropout2 as in the reference.  fp32 whatever training_dtype says: bf16 mixed-precision training of this block and
+        a HIP attention backward are not built."""
+        f32 = torch.float32
+        t = tgt.to(f32)
+        qk = self.with_pos_embed(t, None if query_pos is None else query_pos.to(f32)).transpose(0, 1)
+        with torch.autocast(device_type=tgt.device.type, enabled=False):
+            tgt2 = self.self_attn(qk, qk, t.transpose(0, 1), need_weights=False)[0].transpose(0, 1)
+        return self.norm2(t + self.dropout2(tgt2))
+
     # The layer in two halves, so that a query-sharded run can put its one per-layer exchange (the global
     # "any query valid" flag, mvgformer_amd.dist) between two captured HIP-graph segments.
-    def forward_features(self, tgt, query_pos, reference_points, ctx, threshold, indices=None):
+    def forward_features(self, tgt, query_pos, reference_points, ctx, threshold, indices=None, query_tgt=None):
         """steps 1-4 of dq_decoder.py:850-1045: projection, projective attention, feature update, class
-        head + filter, 2D offsets.  Returns the state consumed by forward_triangulate."""
+        head + filter, 2D offsets.  Returns the state consumed by forward_triangulate.
+        query_tgt: what stands in for tgt in the projective attention's query x = tgt + query_pos; with init_self_attention the
+        layer computes it itself (attend_queries).  As in the reference, where the attended tgt is a local of generate_features
+        (dq_decoder.py:532-540), the feature update still adds its residual to the layer's own tgt (dq_decoder.py:882)."""
+        if query_tgt is None and self.init_self_attention:
+            query_tgt = self.attend_queries(tgt, query_pos)
         B, Lq, C = tgt.shape
         J = self.num_joints
         NQ = Lq // J
@@ -627,13 +689,14 @@ class DQDecoderLayer(MvPDecoderLayer):
             r, ref_lvl, inside = proj_in[1]      # projected by the previous layer's triangulation launch (same arithmetic)
         else:
             r, ref_lvl, inside = ops.project(X, ctx.cams, ctx.levels, V, B)
-        x = lambda: self.with_pos_embed(tgt.float(), None if query_pos is None else query_pos.float()).contiguous()
-        if (query_pos is not None and tgt.dtype == torch.float32 and query_pos.dtype == torch.float32 and tgt.is_contiguous()
-                and query_pos.is_contiguous() and query_pos.shape == tgt.shape):
-            x.parts = (tgt, query_pos)          # lets the fast path fold the add into the query-term GEMM
+        qt = tgt if query_tgt is None else query_tgt
+        x = lambda: self.with_pos_embed(qt.float(), None if query_pos is None else query_pos.float()).contiguous()
+        if (query_pos is not None and qt.dtype == torch.float32 and query_pos.dtype == torch.float32 and qt.is_contiguous()
+                and query_pos.is_contiguous() and query_pos.shape == qt.shape):
+            x.parts = (qt, query_pos)          # lets the fast path fold the add into the query-term GEMM
         xw_in = run.xw_in.pop(run.i, None)     # query term computed by the previous layer's chain B (or None)
-        if xw_in is not None and tuple(xw_in.shape) != (B * Lq, 192):
-            xw_in = None
+        if xw_in is not None and (tuple(xw_in.shape) != (B * Lq, 192) or query_tgt is not None):
+            xw_in = None                        # (computed from tgt + query_pos: not this layer's query)
         f32 = torch.float32
         pose_layers = self.pose_embed.MLP.layers
         o = None

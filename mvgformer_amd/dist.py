@@ -2,7 +2,9 @@
 
 Every person-query is an independent unit of work in the shipped configuration
 (init_self_attention=False, feature_update_method='MLP'): nothing in ProjAttn, the MLP/FFN,
-the class head, the view-softmax, the undistortion or the DLT couples two queries.  So the
+the class head, the view-softmax, the undistortion or the DLT couples two queries.  (A decoder
+with init_self_attention=True couples them and is refused at every entry point here:
+refuse_coupled_queries.)  So the
 NQ person-queries are split into contiguous blocks, one per rank (one process per GPU), each
 rank runs the whole decoder on its block with the feature pyramid / cameras / weights
 replicated, and ONE all-gather at the end of the forward assembles the pose set.  The only other
@@ -21,6 +23,16 @@ import torch
 import torch.distributed as dist
 
 from .decoder import DecoderRun
+
+
+def refuse_coupled_queries(decoder):
+    """Query sharding rests on every person-query being independent.  init_self_attention attends over ALL tokens of a batch
+    element: a rank that holds a block of the queries would attend over that block only.  Refused at entry, before any
+    collective; query sharding with coupled queries is not built."""
+    if any(getattr(layer, "init_self_attention", False) for layer in decoder.layers):
+        raise NotImplementedError("query-sharded execution of a decoder with init_self_attention=True is not built: its self-attention "
+                                  "couples the queries of a batch element, a rank's block of queries cannot be decoded on its own "
+                                  "(run the decoder unsharded, or shard the batch)")
 
 
 def shard_bounds(NQ, world, rank):
@@ -100,6 +112,7 @@ def gather_outputs(outputs, NQ, num_joints, group=None, gather_hidden=False):
 def sharded_decoder_forward(decoder, tgt, reference_points, src_views, meta, spatial_shapes, level_start_index,
                             query_pos, threshold, group=None, gather_hidden=False, context=None):
     """Run DQDecoder.forward on this rank's block of queries and all-gather the pose set."""
+    refuse_coupled_queries(decoder)
     world = dist.get_world_size(group)
     rank = dist.get_rank(group)
     J = decoder.layers[0].num_joints
@@ -146,6 +159,7 @@ class GraphedShardedDecoder:
 
     def __init__(self, decoder, tgt, reference_points, src_views, query_pos, ctx, threshold, NQ, group=None,
                  gather_hidden=False):
+        refuse_coupled_queries(decoder)
         self.dec, self.ctx, self.group, self.thr, self.NQ = decoder, ctx, group, threshold, NQ
         self.tgt, self.ref, self.src, self.qpos = tgt, reference_points, src_views, query_pos
         self.world, self.rank = dist.get_world_size(group), dist.get_rank(group)

@@ -763,6 +763,35 @@ def add_layernorm(res, h, gamma, beta):
     return y
 
 
+def self_attention(q, k, v):
+    """softmax(q k^T / sqrt(32)) v per (batch element, head) on the fused kernel (csrc/mha.hip): q, k, v (B, Lq, 256) float32 or
+    bfloat16 (all the same), 8 heads in columns 32 h .. 32 h + 31 -- what nn.MultiheadAttention computes between its in- and
+    out-projection.  Each may be a column block of a wider (B, Lq, n) tensor (last stride 1, batch stride Lq * row stride): the
+    in-projection's output is attended where it lies.  Returns (B, Lq, 256) in the inputs' dtype.  Finite inputs only."""
+    L.require_cuda(q, k, v)
+    if q.dim() != 3 or q.shape != k.shape or q.shape != v.shape:
+        raise RuntimeError("self_attention: q, k, v of one shape (B, Lq, C) expected, got %s %s %s"
+                           % (tuple(q.shape), tuple(k.shape), tuple(v.shape)))
+    B, Lq, Cc = q.shape
+    if Cc != 256 or Lq < 1 or B < 1:
+        raise RuntimeError("self_attention: built for d_model 256 (8 heads of 32), B >= 1, Lq >= 1; got %s" % (tuple(q.shape),))
+    if q.dtype not in (torch.float32, torch.bfloat16) or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise RuntimeError("self_attention: q, k, v all float32 or all bfloat16, got %s %s %s" % (q.dtype, k.dtype, v.dtype))
+    if q.device != k.device or q.device != v.device:
+        raise RuntimeError("self_attention: q, k, v on one device expected")
+    vec = 16 // q.element_size()
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if t.stride(2) != 1 or (B > 1 and t.stride(0) != Lq * t.stride(1)) or t.stride(1) < Cc or t.stride(1) % vec \
+                or t.data_ptr() % 16:
+            raise RuntimeError("self_attention: %s must be row-major (a column block of a row-major tensor at most), 16-byte "
+                               "aligned rows; strides %s" % (name, t.stride()))
+    out = torch.empty((B, Lq, Cc), dtype=q.dtype, device=q.device)
+    with _timed("self_attention"):
+      L.check(L.load().mvg_self_attention(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(out), q.stride(1), k.stride(1), v.stride(1), B, Lq, Cc,
+                                          8, L.dtype_code(q.dtype), L.stream_ptr()), "mvg_self_attention")
+    return out
+
+
 def class_head(tgt, Wc, bc, threshold, B, NQ, J, forced_valid=None):
     Cc = tgt.shape[-1]
     prob = torch.empty((B, NQ, 2), dtype=torch.float32, device=tgt.device)
