@@ -15,6 +15,7 @@ What differs from the reference by design (MI355X-first, results identical):
 """
 from __future__ import annotations
 
+import collections
 import copy
 import os
 
@@ -23,8 +24,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import ops
-from .projattn import ProjAttn, WeightCache
-
+from .projattn import ProjAttn, WeightCache, f32_split_on
 
 
 class MLP(nn.Module):
@@ -75,6 +75,22 @@ def _mask_indices(indices, B, NQ, device):
         raise RuntimeError("indices as a tensor: (B, NQ) = (%d, %d) uint8 / bool mask on %s expected, got %s %s on %s"
                            % (B, NQ, device, tuple(indices.shape), indices.dtype, indices.device))
     return indices.to(torch.uint8).clone()
+
+
+LayerPlan = collections.namedtuple("LayerPlan", "dt sampler chain_a chain_b binning skip_masked query_term products_ahead grouped")
+LayerPlan.__doc__ = """What one DQDecoderLayer.forward_features call runs (DQDecoderLayer.plan decides, everybody else reads):
+  dt              compute dtype
+  sampler         ProjAttn.sampler_form: "gsamp" | "gfused_f32h" | "gfused_f32" | "gather"
+  chain_a / _b    "bf16" (fused LDS-resident chains, csrc/chain.hip), "f32h" (fp32 on pre-split two-part fp16 operands, csrc/f32s.hip)
+                  or None (one launch per GEMM / row op); the two can differ
+  binning         the (image, query) pairs get a processing order (mvg_bin_pairs: image-space Morton order, pairs outside their image
+                  last): "layer" binned per layer, "first" once per forward from the first layer's projections, None: query order
+  skip_masked     unfused fp32: output projection + pose MLP skip the tiles whose pairs are all outside their image
+  query_term      the previous layer's fused chain B may compute this layer's query term when it runs as this path; None: never
+  products_ahead  the pyramid products may be issued ahead of the layer on the decoder's side stream
+  grouped         ... and may share a launch with other layers' (ops.pyramid_group_ws)"""
+# operands of forward_features in the order the ops take them (DQDecoderLayer._operands)
+LayerOperands = collections.namedtuple("LayerOperands", "sampler self_attn chain_a o_masked pose masked_rows chain_b")
 
 
 class DecoderContext:
@@ -286,21 +302,34 @@ class DQDecoderLayer(MvPDecoderLayer):
     def _w(self, key, params, dtype, build=None):
         return self._wc.get(key, params, dtype, build)
 
-    # cached operands of the fused chains (csrc/chain.hip), in the order the ops take them
-    def _chain_a_weights(self, dt):
-        f32 = torch.float32
-        pose_layers = self.pose_embed.MLP.layers
-        sw = lambda w: ops.swizzle_weight(w.to(dt))
-        wts = (self._w("Wp_sw", (self.proj_attn.output_proj.weight,), dt, sw),
-               self._w("bp", (self.proj_attn.output_proj.bias,), f32),
-               self._w("Wpe0_sw", (pose_layers[0].weight,), dt, sw), self._w("bpe0", (pose_layers[0].bias,), f32),
-               self._w("Wpe1_sw", (pose_layers[1].weight,), dt, sw), self._w("bpe1", (pose_layers[1].bias,), f32),
-               self._w("Wpe_last", (pose_layers[2].weight,), f32), self._w("bpe_last", (pose_layers[2].bias,), f32))
-        pose_params = tuple(p for lin in pose_layers for p in (lin.weight, lin.bias))
+    def _mfma_operand(self, path, dt):
+        """(key, weight) -> the cached operand of one MFMA weight as `path`'s kernels take it, as a tuple to splice into an argument
+        list: "bf16" (fragments,); "f32h" (two fp16 planes, their power-of-two scale); None (the weight in dt,)"""
+        if path == "f32h":
+            return lambda key, w: self._w(key + "_f32h", (w,), torch.float16, ops.split_swizzle_weight_h2)
+        if path == "bf16":
+            return lambda key, w: (self._w(key + "_sw", (w,), dt, lambda t: ops.swizzle_weight(t.to(dt))),)
+        return lambda key, w: (self._w(key, (w,), dt),)
+
+    def _pose_operands(self, path, dt):
+        """(W0, b0, W1, b1, ..., W_last, b_last) of the pose MLP, the hidden layers' weights as `path` takes them (_mfma_operand)"""
+        f32, mm = torch.float32, self._mfma_operand(path, dt)
+        layers = list(self.pose_embed.MLP.layers)       # (a slice of a ModuleList would be a new module)
+        hidden = sum((mm("Wpe%d" % i, lin.weight) + (self._w("bpe%d" % i, (lin.bias,), f32),) for i, lin in enumerate(layers[:-1])), ())
+        return hidden + (self._w("Wpe_last", (layers[-1].weight,), f32), self._w("bpe_last", (layers[-1].bias,), f32))
+
+    def _chain_a_operands(self, path, dt):
+        """operands of ops.chain_attn_pose ("bf16") / ops.chain_attn_pose_f32h ("f32h") and that kernel's masked-row constant"""
+        out_proj = self.proj_attn.output_proj
+        wts = (self._mfma_operand(path, dt)("Wp", out_proj.weight) + (self._w("bp", (out_proj.bias,), torch.float32),)
+               + self._pose_operands(path, dt))
+        params = tuple(p for lin in self.pose_embed.MLP.layers for p in (lin.weight, lin.bias))
+        key, build = "o_masked", ops.chain_masked_row_output
+        if path == "f32h":
+            key, build, params = "o_masked_f32h", ops.chain_masked_row_output_f32h, params + (out_proj.bias,)
         # o of a masked row, computed by the kernel that is going to use it (the variants reduce the last pose layer in
         # different orders; a masked row inside a mixed tile and one in an all-masked tile must agree bit for bit)
-        o_masked = self._w("o_masked", pose_params, f32, lambda *_: ops.chain_masked_row_output(*wts))
-        return wts, o_masked
+        return wts, self._w(key, params, torch.float32, lambda *_: build(*wts))
 
     def _pose_masked_rows(self, dt):
         """what the hidden pose-MLP layers give for a pair outside its image (attn row = 0): layer i's output row, computed by the
@@ -320,81 +349,73 @@ class DQDecoderLayer(MvPDecoderLayer):
         from . import _lib
         return self._w("pose_masked_rows/f32_split=%d" % _lib.TUNING.get("f32_split", 1), params, f32, build)
 
-    def _chain_b_weights(self, dt):
-        f32 = torch.float32
-        sw = lambda w: ops.swizzle_weight(w.to(dt))
-        ffn = self.open_forward_ffn
-        return (self._w("Wu_sw", (self.feature_update_mlp.weight,), dt, sw), self._w("bu", (self.feature_update_mlp.bias,), f32),
-                self._w("g2", (self.norm2.weight,), f32), self._w("b2", (self.norm2.bias,), f32),
-                self._w("W1_sw", (self.linear1.weight,), dt, sw) if ffn else None,
-                self._w("b1", (self.linear1.bias,), f32) if ffn else None,
-                self._w("W2_sw", (self.linear2.weight,), dt, sw) if ffn else None,
-                self._w("bb2", (self.linear2.bias,), f32) if ffn else None,
-                self._w("g3", (self.norm3.weight,), f32) if ffn else None,
-                self._w("b3", (self.norm3.bias,), f32) if ffn else None,
-                self._w("Wc", (self.class_embed.weight,), f32), self._w("bc", (self.class_embed.bias,), f32))
+    def _chain_b_operands(self, path, dt):
+        """(Wu, bu, g2, b2, W1, b1, W2, bb2, g3, b3, Wc, bc): feature update, FFN (None without open_forward_ffn) and class head, the
+        three MFMA weights as `path` takes them (_mfma_operand) -- the argument order of ops.chain_update_ffn_class ("bf16") and,
+        each of the three followed by its scale, of ops.chain_update_ffn_class_f32h ("f32h"); None: the unfused ops' operands"""
+        f32, mm, ffn = torch.float32, self._mfma_operand(path, dt), self.open_forward_ffn
+        none = (None, 0) if path == "f32h" else (None,)
+        vec = lambda key, p, on=True: self._w(key, (p,), f32) if on else None
+        return (mm("Wu", self.feature_update_mlp.weight)
+                + (vec("bu", self.feature_update_mlp.bias), vec("g2", self.norm2.weight), vec("b2", self.norm2.bias))
+                + (mm("W1", self.linear1.weight) if ffn else none) + (vec("b1", self.linear1.bias, ffn),)
+                + (mm("W2", self.linear2.weight) if ffn else none)
+                + (vec("bb2", self.linear2.bias, ffn), vec("g3", self.norm3.weight, ffn), vec("b3", self.norm3.bias, ffn),
+                   vec("Wc", self.class_embed.weight), vec("bc", self.class_embed.bias)))
 
-    def _chain_a_weights_f32h(self):
-        """operands of ops.chain_attn_pose_f32h (two-part fp16 planes + their scales) and the masked-row constant of that kernel"""
-        f32, f16 = torch.float32, torch.float16
-        pose_layers = self.pose_embed.MLP.layers
-        sp = ops.split_swizzle_weight_h2
-        Wp, swp = self._w("Wp_f32h", (self.proj_attn.output_proj.weight,), f16, sp)
-        W0, sw0 = self._w("Wpe0_f32h", (pose_layers[0].weight,), f16, sp)
-        W1, sw1 = self._w("Wpe1_f32h", (pose_layers[1].weight,), f16, sp)
-        wts = (Wp, swp, self._w("bp", (self.proj_attn.output_proj.bias,), f32), W0, sw0, self._w("bpe0", (pose_layers[0].bias,), f32),
-               W1, sw1, self._w("bpe1", (pose_layers[1].bias,), f32),
-               self._w("Wpe_last", (pose_layers[2].weight,), f32), self._w("bpe_last", (pose_layers[2].bias,), f32))
-        pose_params = tuple(p for lin in pose_layers for p in (lin.weight, lin.bias)) + (self.proj_attn.output_proj.bias,)
-        o_masked = self._w("o_masked_f32h", pose_params, f32, lambda *_: ops.chain_masked_row_output_f32h(*wts))
-        return wts, o_masked
+    def plan(self, dt, Lq=None, levels=None, sampler=None):
+        """The LayerPlan of a forward_features call in compute dtype dt on Lq queries per batch element and the pyramid `levels`:
+        the ONLY place the kernel paths are decided.  Not cached: a handful of comparisons on switches that may change between
+        calls.  Lq None: any query count (inside every window).  levels: an ops.Levels or its (L, S); read, with Lq, by the fp32
+        sampler choice alone, which raises without them where the shape decides (ProjAttn.f32_g_form) -- bf16 needs neither.
+        sampler: plan for this form instead of the one the shape selects (prepare_caches without a shape)."""
+        pa, f32 = self.proj_attn, dt == torch.float32
+        if sampler is None:
+            L, S = (None, None) if levels is None else (levels.L, levels.S) if hasattr(levels, "L") else levels
+            sampler = pa.sampler_form(dt, Lq, L, S)
+        d256 = self.d_model == 256      # (the width of the pose MLP's hidden layers and of the FFN's input as well)
+        pose_ok = d256 and self.pose_embed.MLP.num_layers == 3
+        ffn_ok = d256 and (not self.open_forward_ffn or self.linear1.out_features == 1024)
+        if f32:
+            # (the library's f32_split knob selects the reference-arithmetic GEMMs: the fused kernels, whose products are split by
+            # construction, stand down with it; chain A reads the G-sampler's output in processing order)
+            fused = bool(self.use_fused_chains_f32) and f32_split_on()
+            chain_a = "f32h" if (fused and pose_ok and sampler == "gfused_f32h") else None
+            chain_b = "f32h" if (fused and ffn_ok and self.num_joints <= 32) else None
+        else:
+            fused = dt == torch.bfloat16 and bool(self.use_fused_chains)
+            chain_a = "bf16" if (fused and pose_ok) else None
+            chain_b = "bf16" if (fused and ffn_ok and self.num_joints <= 64) else None
+        sort = pa.sort_pairs if (Lq is None or Lq <= 65536) else False
+        # Skipping is worth 1.7 % at cfg-2 (41 % of the tiles skipped at layer 0, but the GEMM is power-limited: tiles of zero rows
+        # were cheap already); below 8192 tokens per image (cfg-4) the extra binning launch costs more than it saves.
+        skip_masked = bool(f32 and chain_a is None and self.skip_masked_f32 and d256 and sort
+                           and (Lq is None or Lq >= 8192))
+        if not sort or (sampler == "gather" and chain_a is None and not skip_masked):
+            binning = None      # (nothing reads an order)
+        else:
+            binning = "first" if (sort == "first" and chain_a == "bf16") else "layer"
+        ahead = sampler != "gather" and (f32 or bool(self.use_fused_chains))
+        # a layer that attends first projects attend_queries(tgt') + query_pos: tgt' + query_pos is not its query
+        query_term = None if self.init_self_attention else chain_a if f32 else "bf16" if ahead else None
+        return LayerPlan(dt, sampler, chain_a, chain_b, binning, skip_masked, query_term, ahead, sampler == "gsamp")
 
-    def _chain_b_weights_f32h(self):
-        """operands of ops.chain_update_ffn_class_f32h, in its argument order"""
-        f32, f16 = torch.float32, torch.float16
-        sp = ops.split_swizzle_weight_h2
-        ffn = self.open_forward_ffn
-        Wu, su = self._w("Wu_f32h", (self.feature_update_mlp.weight,), f16, sp)
-        W1, s1 = self._w("W1_f32h", (self.linear1.weight,), f16, sp) if ffn else (None, 0)
-        W2, s2 = self._w("W2_f32h", (self.linear2.weight,), f16, sp) if ffn else (None, 0)
-        return (Wu, su, self._w("bu", (self.feature_update_mlp.bias,), f32),
-                self._w("g2", (self.norm2.weight,), f32), self._w("b2", (self.norm2.bias,), f32),
-                W1, s1, self._w("b1", (self.linear1.bias,), f32) if ffn else None,
-                W2, s2, self._w("bb2", (self.linear2.bias,), f32) if ffn else None,
-                self._w("g3", (self.norm3.weight,), f32) if ffn else None,
-                self._w("b3", (self.norm3.bias,), f32) if ffn else None,
-                self._w("Wc", (self.class_embed.weight,), f32), self._w("bc", (self.class_embed.bias,), f32))
-
-    def _fuses_chains_f32(self, dt, Lq=None, levels=None):
-        """(chain A, chain B) of the fp32 path run as the fused f32s kernels (csrc/f32s.hip)"""
-        pose_layers = self.pose_embed.MLP.layers
-        from . import _lib
-        # the library's f32_split knob (bench.py --f32-gemm exact) selects the reference-arithmetic GEMMs: the fused kernels, whose
-        # products are split by construction, stand down with it
-        ok = (dt == torch.float32 and self.use_fused_chains_f32 and self.d_model == 256 and _lib.TUNING.get("f32_split", 1) != 0)
-        fuse_a = (ok and len(pose_layers) == 3 and pose_layers[0].out_features == 256 and pose_layers[1].out_features == 256
-                  and pose_layers[0].in_features == 256 and self.proj_attn.f32_fused_active()
-                  and (levels is None or self.proj_attn.f32_g_form(Lq, levels.L, levels.S)))
-        fuse_b = (ok and self.num_joints <= 32 and (not self.open_forward_ffn or (self.linear1.out_features == 1024 and
-                                                                                   self.linear1.in_features == 256)))
-        return fuse_a, fuse_b
-
-    def _fuses_chains(self, dt):
-        """(chain A, chain B) run as the fused LDS-resident kernels for this configuration."""
-        pose_layers = self.pose_embed.MLP.layers
-        fuse_a = (dt == torch.bfloat16 and self.use_fused_chains and len(pose_layers) == 3 and
-                  pose_layers[0].out_features == 256 and pose_layers[1].out_features == 256)
-        fuse_b = (dt == torch.bfloat16 and self.use_fused_chains and self.d_model == 256 and self.num_joints <= 64 and
-                  (not self.open_forward_ffn or self.linear1.out_features == 1024))
-        return fuse_a, fuse_b
-
-    def _kernel_path(self, dt, C, J, Lq, levels):
-        """(chain A, chain B) of one forward_features call, each "bf16" (fused LDS-resident chains, csrc/chain.hip), "f32h" (fp32 on
-        pre-split two-part fp16 operands, csrc/f32s.hip) or None (one launch per GEMM / row op).  The two can differ."""
-        a16, b16 = self._fuses_chains(dt)
-        a32, b32 = self._fuses_chains_f32(dt, Lq, levels)
-        return ("bf16" if a16 else "f32h" if (a32 and C == 256) else None,
-                "bf16" if (b16 and C == 256 and J <= 64) else "f32h" if (b32 and C == 256) else None)
+    def _operands(self, plan):
+        """Every cached operand a forward_features call with this plan reads, built on first use: forward_features takes its
+        operands from here, prepare_caches builds them by calling this.  The output projection's and the query term's (read by
+        the previous layer's chain B: _next_query_term) are fetched inside ProjAttn through the methods called here."""
+        dt, pa = plan.dt, self.proj_attn
+        if plan.query_term is not None:
+            pa.query_term_weights(dt, plan.query_term)
+        if plan.chain_a is not None:
+            chain_a, o_masked = self._chain_a_operands(plan.chain_a, dt)
+            pose = None
+        else:
+            pa.output_operands(dt, plan.skip_masked)
+            chain_a, o_masked, pose = None, None, self._pose_operands(None, dt)
+        return LayerOperands(pa.sampler_operands(plan.sampler, dt), self._self_attn_weights(dt) if self.init_self_attention else None,
+                             chain_a, o_masked, pose, self._pose_masked_rows(dt) if plan.skip_masked else None,
+                             self._chain_b_operands(plan.chain_b, dt))
 
     def _self_attn_weights(self, dt):
         """cached operands of attend_queries: ([Wq; Wk] (512, C), its bias, Wv, its bias, out_proj weight, bias, norm2 weight, bias)"""
@@ -408,7 +429,7 @@ class DQDecoderLayer(MvPDecoderLayer):
                 self._w("sa_Wo", (sa.out_proj.weight,), dt), self._w("sa_bo", (sa.out_proj.bias,), f32),
                 self._w("g2", (self.norm2.weight,), f32), self._w("b2", (self.norm2.bias,), f32))
 
-    def attend_queries(self, tgt, query_pos):
+    def attend_queries(self, tgt, query_pos, weights=None):
         """The block init_self_attention puts at the head of the layer (dq_decoder.py:532-539), eval mode, on the native kernels:
             norm2(tgt + out_proj(attention(Wq x, Wk x, Wv tgt))),  x = tgt + query_pos
         over the Lq = NQ * J tokens of each batch element -- (B, Lq, C) fp32.  In-projection ([Wq; Wk] as one 512-wide product with
@@ -419,7 +440,7 @@ class DQDecoderLayer(MvPDecoderLayer):
             raise RuntimeError("Not implemented on the CPU")
         B, Lq, C = tgt.shape
         dt = self.compute_dtype
-        Wqk, bqk, Wv, bv, Wo, bo, g2, b2 = self._self_attn_weights(dt)
+        Wqk, bqk, Wv, bv, Wo, bo, g2, b2 = weights or self._self_attn_weights(dt)
         t32 = tgt.float().reshape(B * Lq, C).contiguous()
         if query_pos is None:
             qk = ops.linear(t32, Wqk, bqk, out_dtype=dt)
@@ -439,55 +460,36 @@ class DQDecoderLayer(MvPDecoderLayer):
         dt = self.compute_dtype
         if nxt is None or nxt.compute_dtype != dt or not (query_pos is None or query_pos.shape == tgt.shape):
             return None
-        if nxt.init_self_attention:
-            return None         # its query is attend_queries(tgt') + query_pos: tgt' + query_pos is not what it projects
-        if not (nxt._fuses_chains_f32(dt, tgt.shape[1], levels)[0] if path_b == "f32h" else
-                nxt.use_fused_chains and nxt.proj_attn.uses_fast_path(dt)):
+        if nxt.plan(dt, tgt.shape[1], levels).query_term != path_b:
             return None
         qp = None if query_pos is None else query_pos.float().reshape(-1, tgt.shape[2]).contiguous()
-        if path_b == "f32h":
-            (Wn, sn), bn, n_next = nxt.proj_attn.query_term_weights_f32h()
-            return qp, Wn, sn, bn, n_next
-        return (qp,) + tuple(nxt.proj_attn.query_term_weights(dt))
+        return (qp,) + nxt.proj_attn.query_term_weights(dt, path_b)
 
-    def prepare_caches(self, dtype=None):
-        """Build every cached operand of the inference path on the CURRENT stream, outside any graph capture (one of
-        them, o_masked, launches a kernel).  An entry created inside a capture would live in the graph's private pool
-        and stay unwritten until the first replay -- WeightCache.get refuses to do that.  DQDecoder calls this before
-        it forks its side stream, the sharded runners (mvgformer_amd.dist) before they capture."""
+    def prepare_caches(self, dtype=None, Lq=None, levels=None):
+        """Build every cached operand of the inference path on the CURRENT stream, outside any graph capture (some launch a
+        kernel: o_masked, the masked rows).  An entry created inside a capture would live in the graph's private pool and stay
+        unwritten until the first replay -- WeightCache.get refuses to do that.  DQDecoder calls this before it forks its side
+        stream, the sharded runners (mvgformer_amd.dist) before they capture.  With the shape of the forward (Lq, levels): the
+        operands of its plan; without: of every plan some shape can select under the current switches."""
         dt = dtype or self.compute_dtype
-        if self.init_self_attention:
-            self._self_attn_weights(dt)
-        if self.proj_attn.uses_fast_path(dt):
-            self.proj_attn.prepare_fast_path(dt)
-        else:
-            self.proj_attn.weights(dt)
-            if dt == torch.float32 and self.skip_masked_f32:
-                self._pose_masked_rows(dt)
-                self.proj_attn._wc.get("zero_row", (self.proj_attn.output_proj.bias,), torch.float32, lambda b: torch.zeros_like(b))
-            if dt == torch.float32 and self.proj_attn.g_sampling_f32 is not False and \
-                    self.proj_attn.sampling_offsets.out_features + self.proj_attn.attention_weights.out_features == 192:
-                self.proj_attn._fast_query_weights(dt)      # the fp32 G-sampling branch of native_sample (Woa_perm / boa_perm)
-                if self.proj_attn.f32_fused_active() and self.proj_attn.rayconv.weight.shape == (256, 256):
-                    self.proj_attn.query_term_weights_f32h()
-                    self.proj_attn.pyramid_planes_f32h()
-            fa32, fb32 = self._fuses_chains_f32(dt)
-            if fa32:
-                self._chain_a_weights_f32h()
-            if fb32:
-                # (the query-term operand indexes rows 0..191 of [offsets; logits]: only with the G form's geometry, like every
-                # other operand of that form)
-                g_geometry = (self.proj_attn.sampling_offsets.out_features + self.proj_attn.attention_weights.out_features == 192
-                              and self.proj_attn.rayconv.weight.shape == (256, 256))
-                self._chain_b_weights_f32h()
-                if g_geometry:
-                    self.proj_attn.query_term_weights_f32h()
-        fuse_a, fuse_b = self._fuses_chains(dt)
-        if fuse_a:
-            self._chain_a_weights(dt)
-        if fuse_b:
-            self._chain_b_weights(dt)
+        for form in ((None,) if levels is not None else self.proj_attn.sampler_forms(dt)):
+            self._operands(self.plan(dt, Lq, levels, sampler=form))
         return self
+
+    def _forced_queries(self, indices, B, NQ, device, dtype=torch.uint8):
+        """(B, NQ) mask of the queries the filter is told to keep -- all of them (filter_query off, query_filter_method "all"),
+        the matcher's mask (indices as a tensor) or the listed ones (indices as a list of per-element index tensors); None: the
+        class head decides"""
+        if not self.filter_query or self.query_filter_method == "all":
+            return torch.ones((B, NQ), dtype=dtype, device=device)
+        if torch.is_tensor(indices):
+            return _mask_indices(indices, B, NQ, device).to(dtype)
+        if indices is None:
+            return None
+        forced = torch.zeros((B, NQ), dtype=dtype, device=device)
+        for b, q in enumerate(indices):
+            forced[b, torch.as_tensor(q, dtype=torch.long, device=device)] = 1
+        return forced
 
     # ----------------------------------------------------------------------------- forward
     def forward(self, tgt, query_pos, reference_points, src_views, src_spatial_shapes, level_start_index, meta,
@@ -619,15 +621,8 @@ class DQDecoderLayer(MvPDecoderLayer):
                 h1 = self.activation(h1)
             tgt_update = self.norm3(tgt_update + self.dropout4(lin(self.dropout3(h1), self.linear2.weight, self.linear2.bias)))
         prob = lin(tgt_update, self.class_embed.weight, self.class_embed.bias).view(B, NQ, J, 2).sigmoid().mean(2)
-        if not self.filter_query or self.query_filter_method == "all":
-            valid = torch.ones((B, NQ), dtype=torch.bool, device=dev)
-        elif torch.is_tensor(indices):      # the matcher's (B, NQ) mask (criterion.KNNMatcher.match): the filter as it is
-            valid = _mask_indices(indices, B, NQ, dev).bool()
-        elif indices is not None:
-            valid = torch.zeros((B, NQ), dtype=torch.bool, device=dev)
-            for b, q in enumerate(indices):
-                valid[b, torch.as_tensor(q, dtype=torch.long, device=dev)] = True
-        else:
+        valid = self._forced_queries(indices, B, NQ, dev, torch.bool)    # (a tensor: the matcher's mask, criterion.KNNMatcher.match)
+        if valid is None:
             valid = prob[..., 1] > threshold
         # no query kept -> the first one is (dq_decoder.py:620-623), decided on the device (no host sync in the step)
         valid[0, 0] |= ~valid.any()
@@ -672,15 +667,16 @@ class DQDecoderLayer(MvPDecoderLayer):
         query_tgt: what stands in for tgt in the projective attention's query x = tgt + query_pos; with init_self_attention the
         layer computes it itself (attend_queries).  As in the reference, where the attended tgt is a local of generate_features
         (dq_decoder.py:532-540), the feature update still adds its residual to the layer's own tgt (dq_decoder.py:882)."""
-        if query_tgt is None and self.init_self_attention:
-            query_tgt = self.attend_queries(tgt, query_pos)
         B, Lq, C = tgt.shape
         J = self.num_joints
         NQ = Lq // J
         dt = self.compute_dtype
         V = ctx.V
         run = self._run or _NO_RUN
-        path_a, path_b = self._kernel_path(dt, C, J, Lq, ctx.levels)
+        plan = self.plan(dt, Lq, ctx.levels)
+        w = self._operands(plan)
+        if query_tgt is None and self.init_self_attention:
+            query_tgt = self.attend_queries(tgt, query_pos, w.self_attn)
 
         # 1. projective attention features of every view (generate_features, dq_decoder.py:516-593)
         X = reference_points.detach().reshape(B, Lq, 3).float().contiguous()
@@ -697,104 +693,68 @@ class DQDecoderLayer(MvPDecoderLayer):
         xw_in = run.xw_in.pop(run.i, None)     # query term computed by the previous layer's chain B (or None)
         if xw_in is not None and (tuple(xw_in.shape) != (B * Lq, 192) or query_tgt is not None):
             xw_in = None                        # (computed from tgt + query_pos: not this layer's query)
-        f32 = torch.float32
-        pose_layers = self.pose_embed.MLP.layers
-        o = None
         if self.proj_attn._vp_event is None and getattr(ctx, "_packed_event", None) is not None:
             # this layer's pyramid products run inline on THIS stream (no side-stream launch reached it) while the pyramid was packed
             # on the side stream (DQDecoder.pack_pyramid): order the read behind the pack and keep the allocator informed
             torch.cuda.current_stream().wait_event(ctx._packed_event)
             ctx.feat.record_stream(torch.cuda.current_stream())
-        if path_a == "bf16":
-            # processing order of the (image, query) pairs: image-space (Morton) order, pairs outside the image last
-            # (mvg_bin_pairs); shared by the sampler (L1 locality, masked pairs skipped) and chain A (all-masked
-            # tiles skipped).  "first": binned once per forward from the first layer's projections.
-            order = None
-            mode = self.proj_attn.sort_pairs if Lq <= 65536 else False
-            if mode == "first":
+        # processing order of the pairs, shared by the sampler (L1 locality, masked pairs skipped or zero-filled) and what reads its
+        # output (all-masked tiles skipped); a G-sampler on its own bins for itself (ProjAttn.native_sample)
+        order = None
+        if plan.chain_a is not None or plan.skip_masked:
+            if plan.binning == "first":
                 if getattr(ctx, "order", None) is None or ctx.order.numel() != V * B * Lq:
                     ctx.order = ops.bin_pairs(ref_lvl, None, ctx.levels)
                 order = ctx.order
-            elif mode:
+            elif plan.binning:
                 order = ops.bin_pairs(ref_lvl, inside.view(-1), ctx.levels)
-            samp = self.proj_attn.native_sample(x, ref_lvl, ctx.feat, ctx.levels, V, B, pair_mask=inside.view(-1),
-                                                order=order, xw=xw_in)
-            wts, o_masked = self._chain_a_weights(dt)
-            attn, o = ops.chain_attn_pose(samp, inside.view(-1), *wts, order=order, o_masked=o_masked)
-        elif path_a == "f32h":
-            # fp32, fused: G-sampling kernel + chain A on pre-split operands (csrc/f32s.hip); pairs in processing order, masked
-            # pairs last (zero-filled by the sampler, all-masked tiles skipped by the chain)
-            order = ops.bin_pairs(ref_lvl, inside.view(-1), ctx.levels) if (self.proj_attn.sort_pairs and Lq <= 65536) else None
+        if plan.chain_a is not None:
             samp = self.proj_attn.native_sample(x, ref_lvl, ctx.feat, ctx.levels, V, B, pair_mask=inside.view(-1), order=order,
-                                                xw=xw_in)
-            wts, o_masked = self._chain_a_weights_f32h()
-            attn, o = ops.chain_attn_pose_f32h(samp, inside.view(-1), *wts, order=order, o_masked=o_masked)
+                                                xw=xw_in, operands=(plan.sampler, w.sampler))
+            chain_a = ops.chain_attn_pose_f32h if plan.chain_a == "f32h" else ops.chain_attn_pose
+            attn, o = chain_a(samp, inside.view(-1), *w.chain_a, order=order, o_masked=w.o_masked)
         else:
-            # fp32 (reference arithmetic): the per-view output projection and pose MLP run over the pairs in processing order and
-            # skip the tiles whose pairs are all outside their image (their rows are zero / a cached constant either way).
-            # Worth 1.7 % at cfg-2 (41 % of the tiles skipped at layer 0, but the GEMM is power-limited: tiles of zero rows were
-            # cheap already); below 8192 tokens per image (cfg-4) the extra binning launch costs more than it saves.
-            order32 = None
-            if (dt == torch.float32 and self.skip_masked_f32 and C == 256 and 8192 <= Lq <= 65536
-                    and self.proj_attn.sort_pairs):
-                order32 = ops.bin_pairs(ref_lvl, inside.view(-1), ctx.levels)
-            attn = self.proj_attn.native_forward(x(), ref_lvl, ctx.feat, ctx.levels, V, B, rowmask=inside.view(-1), order=order32)
+            # reference arithmetic: the per-view output projection and pose MLP; with plan.skip_masked over the pairs in processing
+            # order, without the tiles whose pairs are all outside their image (their rows are zero / a cached constant either way)
+            attn = self.proj_attn.native_forward(x(), ref_lvl, ctx.feat, ctx.levels, V, B, rowmask=inside.view(-1), order=order)
 
         # 2.+3. update the query features (update_feature 'MLP', dq_decoder.py:763-778 + forward_ffn),
         #       class head + filter (dq_decoder.py:889-908)
-        forced = None
-        if not self.filter_query or self.query_filter_method == "all":
-            forced = torch.ones((B, NQ), dtype=torch.uint8, device=tgt.device)
-        elif torch.is_tensor(indices):
-            forced = _mask_indices(indices, B, NQ, tgt.device)
-        elif indices is not None:
-            forced = torch.zeros((B, NQ), dtype=torch.uint8, device=tgt.device)
-            for b, q in enumerate(indices):
-                forced[b, torch.as_tensor(q, dtype=torch.long, device=tgt.device)] = 1
+        forced = self._forced_queries(indices, B, NQ, tgt.device)
         tgt32 = tgt.float().reshape(B * Lq, C).contiguous()
-        if path_b is not None:
+        if plan.chain_b is not None:
             tgt_out, flag, _ = run.outputs()
-            next_proj = self._next_query_term(run.next_layer(), path_b, tgt, query_pos, ctx.levels)
-            if path_b == "f32h":
+            next_proj = self._next_query_term(run.next_layer(), plan.chain_b, tgt, query_pos, ctx.levels)
+            if plan.chain_b == "f32h":
                 res = ops.chain_update_ffn_class_f32h(
-                    attn, V, tgt32, *self._chain_b_weights_f32h(), threshold, B, NQ, J, forced, self.open_forward_ffn,
+                    attn, V, tgt32, *w.chain_b, threshold, B, NQ, J, forced, self.open_forward_ffn,
                     tgt_out=tgt_out, any_valid=flag, next_query_proj=next_proj)
             else:
                 res = ops.chain_update_ffn_class(
-                    attn, V, tgt32, *self._chain_b_weights(dt), threshold, B, NQ, J, forced, self.open_forward_ffn,
+                    attn, V, tgt32, *w.chain_b, threshold, B, NQ, J, forced, self.open_forward_ffn,
                     tgt_out=tgt_out, any_valid=flag, next_query_proj=next_proj,
-                    attn_inside=inside.view(-1) if path_a == "bf16" else None)   # chain A wrote zeros for the pairs outside their image
+                    attn_inside=inside.view(-1) if plan.chain_a == "bf16" else None)   # chain A wrote zeros for the pairs outside their image
             tgt_update, prob, valid, any_valid = res[:4]
             if next_proj is not None:
                 run.xw_in[run.i + 1] = res[4]
         else:
-            mean = ops.mean_views(attn, V)
-            u = ops.linear(mean, self._w("Wu", (self.feature_update_mlp.weight,), dt),
-                           self._w("bu", (self.feature_update_mlp.bias,), f32), out_dtype=dt)
-            t1 = ops.add_layernorm(tgt32, u, self._w("g2", (self.norm2.weight,), f32), self._w("b2", (self.norm2.bias,), f32))
+            Wu, bu, g2, b2, W1, b1, W2, bb2, g3, b3, Wc, bc = w.chain_b
+            u = ops.linear(ops.mean_views(attn, V), Wu, bu, out_dtype=dt)
+            tgt_update = ops.add_layernorm(tgt32, u, g2, b2)
             if self.open_forward_ffn:
-                h = ops.linear(t1, self._w("W1", (self.linear1.weight,), dt), self._w("b1", (self.linear1.bias,), f32),
-                               out_dtype=dt, relu=True)
-                f = ops.linear(h, self._w("W2", (self.linear2.weight,), dt), self._w("bb2", (self.linear2.bias,), f32),
-                               out_dtype=dt)
-                tgt_update = ops.add_layernorm(t1, f, self._w("g3", (self.norm3.weight,), f32),
-                                               self._w("b3", (self.norm3.bias,), f32))
-            else:
-                tgt_update = t1
-            prob, valid, any_valid = ops.class_head(tgt_update, self._w("Wc", (self.class_embed.weight,), f32),
-                                                    self._w("bc", (self.class_embed.bias,), f32), threshold, B, NQ, J, forced)
+                h = ops.linear(tgt_update, W1, b1, out_dtype=dt, relu=True)
+                tgt_update = ops.add_layernorm(tgt_update, ops.linear(h, W2, bb2, out_dtype=dt), g3, b3)
+            prob, valid, any_valid = ops.class_head(tgt_update, Wc, bc, threshold, B, NQ, J, forced)
         # 4. 2D offsets from the per-view attention features (calculate_2d_offsets, dq_decoder.py:659-717)
-        if o is None:
+        if plan.chain_a is None:
             hcur = attn
-            masked = self._pose_masked_rows(dt) if order32 is not None else None
-            for i, lin in enumerate(pose_layers[:-1]):
-                Wi, bi = self._w("Wpe%d" % i, (lin.weight,), dt), self._w("bpe%d" % i, (lin.bias,), f32)
-                if masked is not None:
-                    hcur = ops.linear_ordered(hcur, Wi, bi, order32, inside.view(-1), masked[i], relu=True)
+            for i in range(len(w.pose) // 2 - 1):
+                Wi, bi = w.pose[2 * i:2 * i + 2]
+                if plan.skip_masked:
+                    hcur = ops.linear_ordered(hcur, Wi, bi, order, inside.view(-1), w.masked_rows[i], relu=True)
                 else:
                     hcur = ops.linear(hcur, Wi, bi, out_dtype=dt, relu=True)
-            o = ops.rowdot3(hcur, self._w("Wpe_last", (pose_layers[-1].weight,), f32),
-                            self._w("bpe_last", (pose_layers[-1].bias,), f32))
+            o = ops.rowdot3(hcur, *w.pose[-2:])
 
         hook = run.after_chain_b.pop(run.i, None)
         if hook is not None:
@@ -906,14 +866,15 @@ class DQDecoder(MvPDecoder):
         """The side stream of the forward, forked from the current stream -- or None when the query-independent work
         runs inline (generic path, share_layer_weights -- one buffer for all layers --, training, CPU,
         MVG_OVERLAP_PYRAMID=0).  f32_shape = (Lq, L, S): needed for the fp32 path, whose pyramid products exist only in its
-        G-sampling form (ProjAttn.f32_g_form)."""
+        G-sampling forms (ProjAttn.sampler_form)."""
         distinct = len({id(l.proj_attn) for l in self.layers}) == len(self.layers)
+        shape = f32_shape or (None, None, None)
 
         def ahead(l):
-            if l.compute_dtype == torch.float32:
-                return (self.overlap_pyramid_f32 and f32_shape is not None and l.proj_attn.rayconv.weight.shape[0] == 256
-                        and l.proj_attn.f32_g_form(*f32_shape))
-            return l.proj_attn.uses_fast_path(l.compute_dtype) and l.use_fused_chains
+            dt = l.compute_dtype
+            if dt == torch.float32 and not (self.overlap_pyramid_f32 and f32_shape is not None):
+                return False
+            return l.plan(dt, shape[0], shape[1:]).products_ahead
         if not (self.overlap_pyramid and distinct and device.type == "cuda" and not torch.is_grad_enabled()
                 and all(ahead(l) for l in self.layers)):
             return None
@@ -939,8 +900,8 @@ class DQDecoder(MvPDecoder):
             side.wait_stream(torch.cuda.current_stream())       # the packed pyramid
         ctx.feat.record_stream(side)
         with torch.cuda.stream(side):
-            groups = self._pyramid_groups(ctx)
-            if groups is None:
+            launches = self.pyramid_launches(ctx, jit)
+            if launches is None:
                 for layer in self.layers:
                     layer.proj_attn.project_pyramid(ctx.feat, record_event=True)
             else:
@@ -952,7 +913,6 @@ class DQDecoder(MvPDecoder):
                 # measured slower (profiles/r05_experiments.txt section 2).  What does pay (section 10): one launch per layer with ONE
                 # workgroup per CU, issued behind the previous layer's chain B (use_jit below).
                 use_jit = self._pyramid_jit(ctx, jit)
-                launches = self.pyramid_launches(ctx, jit)
                 for gi, (group, slots) in enumerate(launches):
                     def issue(group=group, slots=slots):
                         jobs = []
@@ -1010,7 +970,7 @@ class DQDecoder(MvPDecoder):
         """layers whose pyramid products share one launch (bf16 fast path), or None for one launch pair per layer"""
         if self.pyramid_group <= 0 or ctx.feat.dtype != torch.bfloat16 or ctx.feat.shape[2] != 256:
             return None
-        if not all(l.proj_attn.uses_fast_path(torch.bfloat16) and l.proj_attn.rayconv.weight.shape == (256, 256) for l in self.layers):
+        if not all(l.plan(torch.bfloat16).grouped for l in self.layers):
             return None
         layers = list(self.layers)
         groups = [layers[:1]]

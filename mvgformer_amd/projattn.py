@@ -30,6 +30,13 @@ def ops_host_levels_pair(spatial_shapes, level_start_index):
     return [[sc[2 * i], sc[2 * i + 1]] for i in range(len(st))], list(st)
 
 
+def f32_split_on():
+    """the library's f32_split knob selects the split fp32 GEMMs (default); 0 (bench.py --f32-gemm exact): reference arithmetic"""
+    from . import _lib
+    _lib.load()         # applies MVG_TUNE: before that TUNING reads as the library's defaults
+    return _lib.TUNING.get("f32_split", 1) != 0
+
+
 def _is_power_of_2(n):
     if (not isinstance(n, int)) or (n < 0):
         raise ValueError("invalid input for _is_power_of_2: {} (type: {})".format(n, type(n)))
@@ -202,6 +209,49 @@ class ProjAttn(nn.Module):
         return (self.projattn_posembed_mode == "ablation_not_use_rayconv" and self.d_model == 256 and
                 self.n_heads == 8 and self.n_points == 8 and self.n_levels == 1 and 1 <= feat_lvls <= 4)
 
+    @property
+    def g_geometry(self):
+        """what every G-sampling kernel and every operand of that form is built for: 192 [offsets; logits] rows on 256 channels"""
+        return (3 * self.n_heads * self.n_levels * self.n_points == 192 and self.d_model == 256
+                and self.projattn_posembed_mode == "ablation_not_use_rayconv")      # (rayconv is 256 -> 256 in that mode alone)
+
+    def uses_fast_path(self, dt):
+        return dt == torch.bfloat16 and bool(self.use_fast_path) and self.g_geometry
+
+    def f32_fused_active(self):
+        """the fused fp32 kernels on split operands (csrc/f32s.hip) are in use: MVG_F32_FUSED and the library's f32_split knob
+        (bench.py --f32-gemm exact, mvg_set_tuning("f32_split", 0)) both select them; with either off the fp32 path is the
+        reference-arithmetic decomposition (fmaf-chain GEMMs, one launch each)"""
+        return self.g_geometry and bool(self.f32_fused) and f32_split_on()
+
+    def f32_g_form(self, Lq, L, S):
+        """fp32 path: G-sampling (the offsets / logits Linear applied to the pyramid) rather than gather-then-Linear -- by
+        MVG_G_SAMPLING_F32, else whenever the gathered rows (Lq * L per image) outnumber the pyramid's (S)"""
+        if self.g_sampling_f32 != "auto":
+            return bool(self.g_sampling_f32) and self.g_geometry
+        # with the one-pass pyramid kernel (mvg_pyramid_f32h) the G form moves fewer bytes at every shipped shape: the gather
+        # form re-fetched 2.6 x its algorithmic bytes at cfg-4 (profiles/r03_bench_cfg4_fp32.json)
+        if not self.g_geometry or self.f32_fused_active():
+            return self.g_geometry
+        if Lq is None or L is None or S is None:
+            raise ValueError("ProjAttn.f32_g_form: g_sampling_f32='auto' without the fused fp32 kernels decides by the shape (Lq, L, S)")
+        return Lq * L >= S
+
+    def sampler_form(self, dt, Lq, L, S):
+        """which sampler native_sample runs: "gsamp" (bf16 G-sampling, msda_gsamp), "gfused_f32h" / "gfused_f32" (fp32 G-sampling,
+        msda_gfused_f32, on the products of mvg_pyramid_f32h / of two plain linears) or "gather" (gather + linear + msda_fused)"""
+        if self.uses_fast_path(dt):
+            return "gsamp"
+        if dt == torch.float32 and self.f32_g_form(Lq, L, S):
+            return "gfused_f32h" if self.f32_fused_active() else "gfused_f32"
+        return "gather"
+
+    def sampler_forms(self, dt):
+        """every form some shape can select under the current switches"""
+        if dt == torch.float32 and self.g_geometry and self.g_sampling_f32 == "auto" and not self.f32_fused_active():
+            return ("gfused_f32", "gather")     # the only case in which the shape decides (f32_g_form)
+        return (self.sampler_form(dt, None, None, None),)
+
     def weights(self, dtype):
         """(Wv, bv, W_oa, b_oa, Wp, bp): value / [offsets|logits] / output projections."""
         wc = self._wc
@@ -209,9 +259,30 @@ class ProjAttn(nn.Module):
         return (wc.get("Wv", (self.rayconv.weight,), dtype),
                 wc.get("bv", (self.rayconv.bias,), torch.float32),
                 wc.get("Woa", (self.sampling_offsets.weight, self.attention_weights.weight), dtype, cat),
-                wc.get("boa", (self.sampling_offsets.bias, self.attention_weights.bias), torch.float32, cat),
-                wc.get("Wp", (self.output_proj.weight,), dtype),
-                wc.get("bp", (self.output_proj.bias,), torch.float32))
+                wc.get("boa", (self.sampling_offsets.bias, self.attention_weights.bias), torch.float32, cat)) + self.output_operands(dtype)[:2]
+
+    def sampler_operands(self, form, dt, query=True):
+        """every cached operand one sampler form reads (native_sample and the pyramid products in front of it):
+        ([offsets; logits] weight and bias of the query side -- None with query=False --, the pyramid side's operands)"""
+        wc = self._wc
+        if form == "gather":
+            w = self.weights(dt)
+            return w[2:4], w[:2]
+        bv = wc.get("bv", (self.rayconv.bias,), torch.float32)
+        if form == "gsamp":     # value fragments, bias, G fragments (ops.value_proj_planes_ws / feat_linear_ws / pyramid_group_ws)
+            Wv_f = wc.get("Wv_frag", (self.rayconv.weight,), dt, lambda w: ops.swizzle_weight(w.to(dt)))
+            pyramid = (Wv_f, bv, self.query_term_weights(dt)[0])
+        elif form == "gfused_f32h":     # bias + ((value planes, scale), (G planes, scale)) of mvg_pyramid_f32h
+            pyramid = (bv,) + self.pyramid_planes_f32h()
+        else:                           # two plain linears (the second on the query side's weight)
+            pyramid = (wc.get("Wv", (self.rayconv.weight,), dt), bv)
+        return (self._fast_query_weights(dt) if query else None), pyramid
+
+    def output_operands(self, dt, skip_masked=False):
+        """(Wp, bp, zero row): output projection of native_forward; the row of a skipped tile only where tiles are skipped"""
+        wc, bias = self._wc, self.output_proj.bias
+        return (wc.get("Wp", (self.output_proj.weight,), dt), wc.get("bp", (bias,), torch.float32),
+                wc.get("zero_row", (bias,), torch.float32, lambda b: torch.zeros_like(b)) if skip_masked else None)
 
     def _plane_buffer(self, n_img, S, device):
         """value planes buffer (every line is fully rewritten by each projection); kept across calls."""
@@ -219,34 +290,6 @@ class ProjAttn(nn.Module):
         if self._vp is None or self._vp.dtype != torch.bfloat16 or tuple(self._vp.shape) != shape or self._vp.device != device:
             self._vp = torch.empty(shape, dtype=torch.bfloat16, device=device)
         return self._vp
-
-    def prepare_fast_path(self, dtype):
-        """Fill every cached operand of the bf16 fast path on the CURRENT stream (called before work is forked onto
-        a side stream, so that no cache entry is ever produced on one stream and first read on another)."""
-        self.weights(dtype)
-        self._wc.get("bv", (self.rayconv.bias,), torch.float32)
-        self._wc.get("Wv_frag", (self.rayconv.weight,), dtype, lambda w: ops.swizzle_weight(w.to(dtype)))
-        self.query_term_weights(dtype)
-        self._fast_query_weights(dtype)
-
-    def f32_fused_active(self):
-        """the fused fp32 kernels on split operands (csrc/f32s.hip) are in use: MVG_F32_FUSED and the library's f32_split knob
-        (bench.py --f32-gemm exact, mvg_set_tuning("f32_split", 0)) both select them; with either off the fp32 path is the
-        reference-arithmetic decomposition (fmaf-chain GEMMs, one launch each)"""
-        from . import _lib
-        _lib.load()         # applies MVG_TUNE: before that TUNING reads as the library's defaults
-        return bool(self.f32_fused) and _lib.TUNING.get("f32_split", 1) != 0
-
-    def f32_g_form(self, Lq, L, S):
-        """fp32 path: G-sampling (the offsets / logits Linear applied to the pyramid) rather than gather-then-Linear -- by
-        MVG_G_SAMPLING_F32, else whenever the gathered rows (Lq * L per image) outnumber the pyramid's (S)"""
-        geometry = self.sampling_offsets.out_features + self.attention_weights.out_features == 192 and self.rayconv.weight.shape == (256, 256)
-        if self.g_sampling_f32 == "auto" and self.f32_fused_active() and geometry:
-            # with the one-pass pyramid kernel (mvg_pyramid_f32h) the G form moves fewer bytes at every shipped shape: the gather
-            # form re-fetched 2.6 x its algorithmic bytes at cfg-4 (profiles/r03_bench_cfg4_fp32.json)
-            return True
-        use_g = self.g_sampling_f32 if self.g_sampling_f32 != "auto" else Lq * L >= S
-        return bool(use_g) and geometry
 
     def _wait_pyramid(self):
         """both pyramid projections were produced ahead of time on a side stream (DQDecoder.launch_pyramid_projections)."""
@@ -263,8 +306,8 @@ class ProjAttn(nn.Module):
         dt = feat.dtype
         n_img, S, Cc = feat.shape
         if dt == torch.float32:      # fp32 G-sampling form: plain (rows, 256) / (rows, 192) fp32 products, kept across calls
-            Wv, bv = self.weights(dt)[:2]
-            Wq, _ = self._fast_query_weights(dt)
+            f32h = self.f32_fused_active()
+            (Wq, _), pyramid = self.sampler_operands("gfused_f32h" if f32h else "gfused_f32", dt)
             if record_event:
                 # side-stream schedule: every layer's products exist at the same time -> one pair of buffers per layer
                 if (self._vp is None or self._vp.dtype != dt or tuple(self._vp.shape) != (n_img, S, Cc) or self._vp.device != feat.device
@@ -281,12 +324,12 @@ class ProjAttn(nn.Module):
                     cur = self._f32_pool[slot] = (torch.empty((n_img, S, Cc), dtype=dt, device=feat.device),
                                                torch.empty((n_img * S, 192), dtype=dt, device=feat.device))
                 self._vp, self._G = cur
-            if self.f32_fused_active() and Cc == 256 and feat.is_contiguous():
+            if f32h:
                 # two-part fp16 operands, three products (csrc/f32s.hip: pyramid_ws_f32h_kernel)
-                (Wv_pl, sv), (Wg_pl, sg) = self.pyramid_planes_f32h()
+                bv, (Wv_pl, sv), (Wg_pl, sg) = pyramid
                 ops.pyramid_f32h(feat, Wv_pl, sv, bv, Wg_pl, sg, 192, value=self._vp, G=self._G)   # projattn.py:169 + 180-181
             else:
-                ops.linear(feat.view(n_img * S, Cc), Wv, bv, out=self._vp.view(n_img * S, Cc))       # projattn.py:169
+                ops.linear(feat.view(n_img * S, Cc), *pyramid, out=self._vp.view(n_img * S, Cc))     # projattn.py:169
                 ops.linear(feat.view(n_img * S, Cc), Wq, None, out=self._G)
             if record_event:
                 self._vp_event = torch.cuda.Event()
@@ -295,33 +338,29 @@ class ProjAttn(nn.Module):
         # the 103-MB value write first, G (gathered at random by the sampler) last: G is then the fresher
         # resident of the 256-MB Infinity Cache when the sampler starts
         vp = self.project_values(feat)
-        shape = (n_img * S, 192)
-        if self._G is None or self._G.dtype != torch.bfloat16 or tuple(self._G.shape) != shape or self._G.device != feat.device:
-            self._G = torch.empty(shape, dtype=torch.bfloat16, device=feat.device)
-        ops.feat_linear_ws(feat, self.query_term_weights(dt)[0], 192, out=self._G)
+        ops.feat_linear_ws(feat, self.sampler_operands("gsamp", dt, query=False)[1][2], 192, out=self._g_buffer(n_img, S, feat.device))
         if record_event:
             self._vp_event = torch.cuda.Event()
             self._vp_event.record()
         return vp, self._G
 
+    def _g_buffer(self, n_img, S, device):
+        """G of the bf16 form, kept across calls like the value planes"""
+        shape = (n_img * S, 192)
+        if self._G is None or self._G.dtype != torch.bfloat16 or tuple(self._G.shape) != shape or self._G.device != device:
+            self._G = torch.empty(shape, dtype=torch.bfloat16, device=device)
+        return self._G
+
     def pyramid_jobs(self, feat):
         """this layer's two products as jobs of ops.pyramid_group_ws (value planes, G), into the buffers project_pyramid uses"""
-        dt = feat.dtype
         n_img, S, _ = feat.shape
-        bv = self._wc.get("bv", (self.rayconv.bias,), torch.float32)
-        Wv_f = self._wc.get("Wv_frag", (self.rayconv.weight,), dt, lambda w: ops.swizzle_weight(w.to(dt)))
-        vp = self._plane_buffer(n_img, S, feat.device)
-        shape = (n_img * S, 192)
-        if self._G is None or self._G.dtype != torch.bfloat16 or tuple(self._G.shape) != shape or self._G.device != feat.device:
-            self._G = torch.empty(shape, dtype=torch.bfloat16, device=feat.device)
-        return [(Wv_f, bv, vp, True), (self.query_term_weights(dt)[0], None, self._G, False)]
+        Wv_f, bv, Wg_f = self.sampler_operands("gsamp", feat.dtype, query=False)[1]
+        return [(Wv_f, bv, self._plane_buffer(n_img, S, feat.device), True), (Wg_f, None, self._g_buffer(n_img, S, feat.device), False)]
 
     def project_values(self, feat):
         """value = rayconv(input_flatten) (projattn.py:169) as bf16 head planes vh[img][head][s][32]."""
-        dt = feat.dtype
         n_img, S, _ = feat.shape
-        bv = self._wc.get("bv", (self.rayconv.bias,), torch.float32)
-        Wv_f = self._wc.get("Wv_frag", (self.rayconv.weight,), dt, lambda w: ops.swizzle_weight(w.to(dt)))
+        Wv_f, bv, _ = self.sampler_operands("gsamp", feat.dtype, query=False)[1]
         vp = self._plane_buffer(n_img, S, feat.device)
         ops.value_proj_planes_ws(feat, Wv_f, bv, vp)
         return vp
@@ -332,25 +371,24 @@ class ProjAttn(nn.Module):
         Returns (V*B*Lq, C).  order (with rowmask, fp32): the pairs' processing order (ops.bin_pairs: masked pairs last) --
         tiles of the output projection without an unmasked row are not computed (their rows are zero either way)."""
         samp = self.native_sample(x, r, feat, levels, V, B, pair_mask=rowmask, order=order)
-        _, _, _, _, Wp, bp = self.weights(feat.dtype)
-        if order is not None and rowmask is not None and feat.dtype == torch.float32:
-            zero = self._wc.get("zero_row", (self.output_proj.bias,), torch.float32, lambda b: torch.zeros_like(b))
+        Wp, bp, zero = self.output_operands(feat.dtype, order is not None and rowmask is not None and feat.dtype == torch.float32)
+        if zero is not None:
             return ops.linear_ordered(samp, Wp, bp, order, rowmask, zero, rowmask=rowmask)
         return ops.linear(samp, Wp, bp, out_dtype=feat.dtype, rowmask=rowmask)   # projattn.py:203 (+ dq_decoder.py:585)
 
-    def uses_fast_path(self, dt):
-        return (dt == torch.bfloat16 and self.use_fast_path and
-                self.sampling_offsets.out_features + self.attention_weights.out_features == 192)
-
-    def query_term_weights(self, dt):
-        """operands of xw = (tgt + query_pos) @ [Woff; Wattn]^T + b as the fused chain B of the PREVIOUS layer takes
-        them: (weight fragments (256,256) bf16 zero-padded, bias (256,) f32 zero-padded, n = 192)."""
+    def query_term_weights(self, dt, path="bf16"):
+        """operands of xw = (tgt + query_pos) @ [Woff; Wattn]^T + b as the fused chain B of the PREVIOUS layer takes them, rows in
+        gsamp_column_order and zero-padded to 256: (weight fragments (256,256) bf16, bias (256,) f32, n = 192) for the "bf16" chain,
+        (two-part fp16 planes, their scale, bias, n) for the "f32h" one."""
         perm = lambda a, b: torch.cat([a, b], 0)[ops.gsamp_column_order(a.device)]
-        pad = lambda a, b: ops.swizzle_weight(torch.cat([perm(a, b), a.new_zeros(64, a.shape[1])], 0).to(dt))
-        Wf = self._wc.get("Woa_frag", (self.sampling_offsets.weight, self.attention_weights.weight), dt, pad)
+        if path == "f32h":
+            W = self.pyramid_planes_f32h()[1]       # the G operand of mvg_pyramid_f32h is the same weight
+        else:
+            pad = lambda a, b: ops.swizzle_weight(torch.cat([perm(a, b), a.new_zeros(64, a.shape[1])], 0).to(dt))
+            W = (self._wc.get("Woa_frag", (self.sampling_offsets.weight, self.attention_weights.weight), dt, pad),)
         bpad = lambda a, b: torch.cat([perm(a, b), a.new_zeros(64)], 0)
         bn = self._wc.get("boa_pad", (self.sampling_offsets.bias, self.attention_weights.bias), torch.float32, bpad)
-        return Wf, bn, 192
+        return W + (bn, 192)
 
     def pyramid_planes_f32h(self):
         """operands of mvg_pyramid_f32h: ((value planes, scale), (G planes, scale)) -- two fp16 parts of each weight times a power of two"""
@@ -359,15 +397,6 @@ class ProjAttn(nn.Module):
         return (self._wc.get("Wv_f32h", (self.rayconv.weight,), f16, ops.split_swizzle_weight_h2),
                 self._wc.get("Woa_f32h", (self.sampling_offsets.weight, self.attention_weights.weight), f16, perm))
 
-    def query_term_weights_f32h(self):
-        """operands of the next layer's query term as the two-part fp16 chain B of the PREVIOUS layer takes them: ((planes, scale) of the
-        (192 -> 256, 256) weight in gsamp_column_order, bias (256,) f32 zero-padded, n = 192)"""
-        Wpl = self.pyramid_planes_f32h()[1]
-        perm = lambda a, b: torch.cat([a, b], 0)[ops.gsamp_column_order(a.device)]
-        bpad = lambda a, b: torch.cat([perm(a, b), a.new_zeros(64)], 0)
-        bn = self._wc.get("boa_pad", (self.sampling_offsets.bias, self.attention_weights.bias), torch.float32, bpad)
-        return Wpl, bn, 192
-
     def _fast_query_weights(self, dt):
         """[offsets; logits] Linear in the column order of the G-sampling kernel (ops.gsamp_column_order)."""
         perm = lambda a, b: torch.cat([a, b], 0)[ops.gsamp_column_order(a.device)]
@@ -375,52 +404,46 @@ class ProjAttn(nn.Module):
         b = self._wc.get("boa_perm", (self.sampling_offsets.bias, self.attention_weights.bias), torch.float32, perm)
         return W, b
 
-    def native_sample(self, x, r, feat, levels, V, B, pair_mask=None, order=None, xw=None):
+    def native_sample(self, x, r, feat, levels, V, B, pair_mask=None, order=None, xw=None, operands=None):
         """everything of native_forward up to (not including) output_proj: (V*B*Lq, C) sampled values.
         x (B,Lq,C) f32 = tgt + query_pos, or a callable returning it (only evaluated when needed: with xw given --
         the query term (B*Lq,192) precomputed by the previous layer -- the bf16 fast path never touches x).
         pair_mask (V*B*Lq) u8: rows the caller is going to multiply by 0 (reference point outside the image,
-        dq_decoder.py:585-586); the bf16 fast path returns zeros for them instead of sampling."""
+        dq_decoder.py:585-586); the bf16 fast path returns zeros for them instead of sampling.
+        operands: (sampler_form, sampler_operands of it) when the caller holds them already (DQDecoderLayer's plan)."""
         dt = feat.dtype
-        Wv, bv, Woa, boa, Wp, bp = self.weights(dt)
         n_img, S, Cc = feat.shape
+        if operands is None:
+            form = self.sampler_form(dt, r.shape[1], levels.L, S)
+            operands = form, self.sampler_operands(form, dt)
+        form, ((Wq, bq), pyramid) = operands
         parts = getattr(x, "parts", None)        # (tgt, query_pos) when the caller has not formed tgt + query_pos yet
-        f32_g = dt == torch.float32 and Cc == 256 and self.f32_g_form(r.shape[1], levels.L, S)
-        if callable(x) and not (self.uses_fast_path(dt) and (xw is not None or parts is not None)) and not (f32_g and xw is not None):
+        g16 = form == "gsamp"
+        if callable(x) and (form == "gather" or (xw is None and not (g16 and parts is not None))):
             x = x()
-        if self.uses_fast_path(dt):
-            # Linear(bilinear(feat) + x) = bilinear(Linear(feat)) + Linear(x): project the pyramid once (G), compute
-            # the query term once per layer (xw), gather offsets/logits inside the sampler (csrc/msda.hip)
-            # processing order of the pairs: given by the caller (DQDecoderLayer shares it with chain A) or binned here
-            if order is None and self.sort_pairs and r.shape[1] <= 65536:
-                order = ops.bin_pairs(r, pair_mask, levels)
-            if xw is None:      # else: already computed by the previous layer's fused chain B
-                Wq, bq = self._fast_query_weights(dt)
-                if parts is not None:   # first layer: tgt + query_pos formed inside the GEMM's loader (mvg_linear_sum)
-                    xw = ops.linear(parts[0].reshape(-1, Cc), Wq, bq, out_dtype=torch.float32, add=parts[1].reshape(-1, Cc))
-                else:
-                    xw = ops.linear(x.reshape(-1, Cc), Wq, bq, out_dtype=torch.float32)
-            vp, G = self.project_pyramid(feat) if self._vp_event is None else self._wait_pyramid()
-            return ops.msda_gsamp(vp, G, xw, r, levels, B, pair_mask=pair_mask, order=order)   # projattn.py:148-200
-        if f32_g:
-            # fp32, reference arithmetic, same re-association as the bf16 fast path: the offsets / logits Linear applied to
-            # the pyramid once (G) instead of to V*Lq*L gathered rows -- no `ain` (236 MB) / `oa` (177 MB) per layer
-            if xw is not None:      # computed by the previous layer's fp32 chain B
-                xw32 = xw
+        if form == "gather":
+            ain = ops.gather_ref(feat, r, x, levels, V, B)                       # projattn.py:148-153,180 (+query)
+            oa = ops.linear(ain, Wq, bq, out_dtype=torch.float32)                # projattn.py:180-181
+            value = ops.linear(feat.view(n_img * S, Cc), *pyramid, out_dtype=dt)    # projattn.py:169
+            return ops.msda_fused(value.view(n_img, S, Cc), oa, r, levels)       # projattn.py:184-200
+        # Linear(bilinear(feat) + x) = bilinear(Linear(feat)) + Linear(x): project the pyramid once (G) instead of V*Lq*L gathered
+        # rows (fp32: no `ain` (236 MB) / `oa` (177 MB) per layer), compute the query term once per layer (xw), gather offsets /
+        # logits inside the sampler (csrc/msda.hip).  Processing order of the pairs: given by the caller (DQDecoderLayer shares
+        # it with chain A) or binned here -- in front of the query term in bf16, behind it in fp32.
+        binned = order is None and self.sort_pairs and r.shape[1] <= 65536
+        if binned and g16:
+            order = ops.bin_pairs(r, pair_mask, levels)
+        if xw is None:      # else: already computed by the previous layer's fused chain B
+            if g16 and parts is not None:   # first layer: tgt + query_pos formed inside the GEMM's loader (mvg_linear_sum)
+                xw = ops.linear(parts[0].reshape(-1, Cc), Wq, bq, out_dtype=torch.float32, add=parts[1].reshape(-1, Cc))
             else:
-                Wq, bq = self._fast_query_weights(dt)
-                if callable(x):
-                    x = x()
-                xw32 = ops.linear(x.reshape(-1, Cc), Wq, bq, out_dtype=dt)
-            if order is None and self.sort_pairs and r.shape[1] <= 65536:
-                order = ops.bin_pairs(r, pair_mask, levels)
-            # the two pyramid products: computed here, or ahead of time on the side stream (DQDecoder.launch_pyramid_projections)
-            value, G32 = self.project_pyramid(feat) if self._vp_event is None else self._wait_pyramid()
-            return ops.msda_gfused_f32(value, G32, xw32, r, levels, B, pair_mask=pair_mask, order=order)
-        ain = ops.gather_ref(feat, r, x, levels, V, B)                       # projattn.py:148-153,180 (+query)
-        oa = ops.linear(ain, Woa, boa, out_dtype=torch.float32)              # projattn.py:180-181
-        value = ops.linear(feat.view(n_img * S, Cc), Wv, bv, out_dtype=dt)   # projattn.py:169
-        return ops.msda_fused(value.view(n_img, S, Cc), oa, r, levels)       # projattn.py:184-200
+                xw = ops.linear(x.reshape(-1, Cc), Wq, bq, out_dtype=torch.float32)
+        if binned and not g16:
+            order = ops.bin_pairs(r, pair_mask, levels)
+        # the two pyramid products: computed here, or ahead of time on the side stream (DQDecoder.launch_pyramid_projections)
+        vp, G = self.project_pyramid(feat) if self._vp_event is None else self._wait_pyramid()
+        sample = ops.msda_gsamp if g16 else ops.msda_gfused_f32
+        return sample(vp, G, xw, r, levels, B, pair_mask=pair_mask, order=order)   # projattn.py:148-200
 
     # ------------------------------------------------------------------------------- forward
     def _step(self, n):

@@ -408,36 +408,70 @@ def test_prepared_context_is_repacked_for_every_frame():
             assert torch.equal(c2[0], a2[0])
 
 
-def test_weight_cache_refuses_to_build_inside_a_graph_capture():
+def _layers_set(**attrs):
+    """set attributes on every layer ("proj_attn.x": on its ProjAttn)"""
+    def apply(dec):
+        for layer in dec.layers:
+            for name, value in attrs.items():
+                obj, _, attr = name.rpartition(".")
+                setattr(getattr(layer, obj) if obj else layer, attr, value)
+    return apply
+
+
+@pytest.mark.parametrize("dt, knob, configure", [
+    (torch.bfloat16, None, _layers_set()),
+    (torch.bfloat16, None, _layers_set(use_fused_chains=False)),
+    (torch.float32, None, _layers_set()),
+    (torch.float32, None, _layers_set(use_fused_chains_f32=False)),
+    (torch.float32, 0, _layers_set()),
+    (torch.float32, None, _layers_set(**{"proj_attn.g_sampling_f32": False})),
+    (torch.bfloat16, None, _layers_set(open_forward_ffn=True)),
+    (torch.bfloat16, None, _layers_set(init_self_attention=True)),
+], ids=["bf16", "bf16-chains-off", "fp32", "fp32-chains-off", "fp32-split-0", "fp32-g-sampling-off", "bf16-ffn", "bf16-selfattn"])
+def test_weight_cache_refuses_to_build_inside_a_graph_capture(dt, knob, configure):
     """An operand cache entry created during HIP-graph capture would stay unwritten until the first replay; the cache
-    raises instead, and DQDecoderLayer.prepare_caches() is the way to fill it ahead of a capture."""
+    raises instead, and DQDecoderLayer.prepare_caches() is the way to fill it ahead of a capture -- for every kernel path a
+    layer can plan (DQDecoderLayer.plan), not only the default one: no eager forward runs on the captured decoder."""
+    from mvgformer_amd import _lib
     from mvgformer_amd.decoder import DecoderContext
     from mvgformer_amd.factory import build_decoder_for_case, case_to_device
     case = build_case("mini5", seed=3, layers=2)
     g = case_to_device(case, DEV)
-    ctx = DecoderContext.prepare(g.spatial_shapes, g.level_start_index, g.meta, case.img_size, torch.bfloat16, 1, DEV)
+    ctx = DecoderContext.prepare(g.spatial_shapes, g.level_start_index, g.meta, case.img_size, dt, 1, DEV)
     fwd = lambda dec: dec(g.tgt, g.reference_points, g.src_views, g.meta, g.spatial_shapes, g.level_start_index, None,
                           query_pos=g.query_pos, threshold=0.1, context=ctx)
-    cold = build_decoder_for_case(case, DEV, dtype=torch.bfloat16)
-    cold.overlap_pyramid = False        # the side-stream fork prepares the caches itself; here nothing does
-    graph = torch.cuda.CUDAGraph()
-    with torch.no_grad():
-        with pytest.raises(RuntimeError, match="prepare_caches"):
-            with torch.cuda.graph(graph):
-                fwd(cold)
-    torch.cuda.synchronize()
-    warm = build_decoder_for_case(case, DEV, dtype=torch.bfloat16)
-    warm.overlap_pyramid = False
-    for layer in warm.layers:
-        layer.prepare_caches()
-    with torch.no_grad():
-        want = fwd(build_decoder_for_case(case, DEV, dtype=torch.bfloat16))
+
+    def build():
+        dec = build_decoder_for_case(case, DEV, dtype=dt)
+        dec.overlap_pyramid = False     # the side-stream fork prepares the caches itself; here nothing does (and the graph has no parallel branches)
+        configure(dec)
+        return dec
+    lib = _lib.load()
+    before = _lib.TUNING.get("f32_split", 1)
+    try:
+        if knob is not None:
+            assert lib.mvg_set_tuning(b"f32_split", knob) == 0
+        cold = build()
         graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            got = fwd(warm)
-        graph.replay()
+        with torch.no_grad():
+            with pytest.raises(RuntimeError, match="prepare_caches"):
+                with torch.cuda.graph(graph):
+                    fwd(cold)
         torch.cuda.synchronize()
-    assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1])
+        warm = build()
+        for layer in warm.layers:
+            layer.prepare_caches()
+        with torch.no_grad():
+            want = fwd(build())
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                got = fwd(warm)
+            graph.replay()
+            torch.cuda.synchronize()
+    finally:
+        assert lib.mvg_set_tuning(b"f32_split", before) == 0
+    for a, b in zip(got[:4] + (torch.stack(got[4]),), want[:4] + (torch.stack(want[4]),)):
+        assert torch.equal(a, b)
 
 
 def test_train_mode_without_autograd_applies_dropout():
