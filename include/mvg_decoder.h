@@ -555,6 +555,46 @@ int mvg_refresh_operands(const void* record_table, int n_records, const void* ti
 int mvg_self_attention(const void* q, const void* k, const void* v, void* out, int ldq, int ldk, int ldv, int B, int Lq, int C, int M,
                        int dtype, void* stream);
 
+/* mvg_self_attention for training: the same kernel and, with p_drop == 0, the same bits in `out`, plus
+ *   lse (B, 8, Lq) fp32:  lse[b,h,i] = ln sum_j exp(q[b,i,h] . k[b,j,h] / sqrt(32)) -- what the backward recomputes P from; finite
+ *       for finite inputs (the row sum is >= 1);
+ *   attention dropout:    out = (Z o P) v with Z = keep / (1 - p_q); the row sum and lse come from the undropped P, as in
+ *       F.multi_head_attention_forward.  p_drop is quantised to p_q = round(256 p_drop) / 256 (at most 255 / 256): 8 bits per
+ *       decision, the scale is that of the quantised value.  keep is a stateless function of (*seed, b, head, query, key) and of
+ *       nothing else -- mvg_self_attention_dropout_mask writes it out.  seed points to DEVICE memory (8-byte aligned) and is read
+ *       by the kernel when it runs: a captured graph sees the value of each replay.  It may be NULL when p_drop == 0.
+ * MVG_E_BADARG, nothing launched: everything mvg_self_attention refuses, a NULL lse, p_drop outside [0, 1) or NaN, p_drop > 0
+ * with a NULL or misaligned seed. */
+int mvg_self_attention_train(const void* q, const void* k, const void* v, void* out, float* lse, int ldq, int ldk, int ldv, int B, int Lq,
+                             int C, int M, int dtype, float p_drop, const uint64_t* seed, void* stream);
+
+/* bytes of mvg_self_attention_backward's workspace (delta, (B, 8, Lq) fp32); 0 for a B or Lq it refuses */
+size_t mvg_self_attention_backward_workspace(int B, int Lq);
+
+/* Gradients of mvg_self_attention_train's `out` with respect to q, k, v, flash-style: P is recomputed from q, k and lse, no
+ * Lq x Lq matrix in memory.  q, k, v, lse, p_drop, seed: what the forward was given / wrote; out, dout (B, Lq, C) `dtype`,
+ * contiguous (out as the forward stored it: in bf16 the rounded one).  dq, dk, dv (B, Lq, C) `dtype` with row strides lddq,
+ * lddk, lddv >= C (element strides (Lq * ld, ld, 1)): d[q; k] can be written as the column blocks of one (B * Lq, 512) tensor.
+ *   delta = rowsum(dout o out);  dv = (Z o P)^T dout;  dP = dout v^T;  dS = P o (Z o dP - delta) / sqrt(32);  dq = dS k;
+ *   dk = dS^T q
+ * in three launches (delta; dq with the query on the lane; dk and dv with the key on the lane), each of the two large ones
+ * recomputing S and dP.  Every output element has one writer, the reduction order is fixed, there are no atomics and no
+ * hand-off between workgroups: bit-identical from run to run, independent of the other batch elements, capturable.
+ *   MVG_BF16: q, k, v, out, dout bf16; Z o P and dS rounded to bf16 only as MFMA operands; lse, delta, P, dP, dS fp32; dq, dk,
+ *             dv rounded once on store.          MVG_F32: fp32 MFMA chains, the forward's arithmetic class.
+ * workspace: at least mvg_self_attention_backward_workspace(B, Lq) bytes, 4-byte aligned.  MVG_E_BADARG, nothing launched:
+ * everything mvg_self_attention_train refuses, for dq / dk / dv and their strides what it refuses for q / k / v, a NULL or
+ * misaligned out / dout / lse, a NULL or too small workspace. */
+int mvg_self_attention_backward(const void* q, const void* k, const void* v, const void* out, const void* dout, const float* lse, void* dq,
+                                void* dk, void* dv, int ldq, int ldk, int ldv, int lddq, int lddk, int lddv, int B, int Lq, int C, int M,
+                                int dtype, float p_drop, const uint64_t* seed, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The keep mask of the attention dropout as bytes, mask (B, 8, Lq, Lq) uint8 (1 = kept), from the device function the three
+ * training kernels call: a test and debugging aid.  p_drop == 0 writes ones.  MVG_E_BADARG: Lq > MVG_MHA_MASK_MAX_LQ, B or
+ * Lq < 1, B > 65535, a NULL mask, p_drop / seed as in mvg_self_attention_train. */
+#define MVG_MHA_MASK_MAX_LQ 1024
+int mvg_self_attention_dropout_mask(unsigned char* mask, int B, int Lq, float p_drop, const uint64_t* seed, void* stream);
+
 /* ---- serving post-processing (csrc/nms.hip) -------------------------------------------------------------------------------- */
 #define MVG_NMS_MAX_N 2048            /* candidates rows per batch element                                                    */
 #define MVG_NMS_MAX_J 32

@@ -75,6 +75,10 @@ SIGNATURES = {
     "mvg_refresh_operands": [_vp, _i, _vp, _i, _vp],
     "mvg_pose_nms_workspace": [_i] * 3,
     "mvg_self_attention": [_vp] * 4 + [_i] * 8 + [_vp],
+    "mvg_self_attention_train": [_vp] * 5 + [_i] * 8 + [_f, _vp, _vp],
+    "mvg_self_attention_backward_workspace": [_i, _i],
+    "mvg_self_attention_backward": [_vp] * 9 + [_i] * 11 + [_f, _vp, _vp, C.c_size_t, _vp],
+    "mvg_self_attention_dropout_mask": [_vp, _i, _i, _f, _vp, _vp],
     "mvg_pose_nms": [_vp, _i, _i, _i, C.c_double, _i, _i, _vp, C.c_size_t, _vp, _vp, _vp, _i, _vp],
 }
 
@@ -108,6 +112,7 @@ def load():
     lib.mvg_criterion_workspace.restype = C.c_size_t
     lib.mvg_optim_workspace.restype = C.c_size_t
     lib.mvg_pose_nms_workspace.restype = C.c_size_t
+    lib.mvg_self_attention_backward_workspace.restype = C.c_size_t
     lib.mvg_version.argtypes = []
     # every knob change goes through this wrapper, so that host-side caches that depend on a knob (DQDecoderLayer's rows of
     # all-masked tiles: computed by the GEMM form that is active) can key on its value: TUNING[key] = last value set

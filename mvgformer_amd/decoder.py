@@ -26,6 +26,11 @@ from torch import nn
 from . import ops
 from .projattn import ProjAttn, WeightCache, f32_split_on
 
+# backend of the init_self_attention block under autograd, read once: "torch" | "native" (DQDecoderLayer.set_self_attention_training)
+SELF_ATTN_TRAIN = os.environ.get("MVG_SELF_ATTN_TRAIN", "torch")
+if SELF_ATTN_TRAIN not in ("torch", "native"):
+    raise ValueError("MVG_SELF_ATTN_TRAIN must be 'torch' or 'native', got %r" % SELF_ATTN_TRAIN)
+
 
 class MLP(nn.Module):
     """multi_view_pose_transformer.py:81-102"""
@@ -237,6 +242,7 @@ class DQDecoderLayer(MvPDecoderLayer):
         self.d_model = d_model
         self.compute_dtype = torch.float32
         self.training_dtype = torch.float32     # set_training_dtype
+        self.self_attention_training = SELF_ATTN_TRAIN      # set_self_attention_training
         self.use_fused_chains = True    # bf16 inference: LDS-resident Linear chains (csrc/chain.hip)
         # fp32 inference: the same two chains on pre-split operands (csrc/f32s.hip); MVG_F32_FUSED=0: one launch per GEMM / row op
         self.use_fused_chains_f32 = os.environ.get("MVG_F32_FUSED", "1") != "0"
@@ -265,11 +271,22 @@ class DQDecoderLayer(MvPDecoderLayer):
         fp32 gradients, a bf16 value for the sampling op (rounding points: forward_autograd).  LayerNorm, softmax, dropout, sigmoid
         and all geometry stay fp32 / fp64.  The native inference path, compute_dtype, GraphedDecoder and the query-sharded
         runners do not read it.  torch.autocast is NOT consulted: this switch alone selects the bf16 path.  The self-attention block
-        of init_self_attention stays fp32 either way (_attend_queries_autograd): its bf16 training is not built."""
+        of init_self_attention follows it only on the native backend (set_self_attention_training("native"): bf16 q, k, v and the
+        bf16 attention kernels, fp32 projections); through torch's module it stays fp32 either way."""
         if dtype not in (torch.float32, torch.bfloat16):
             raise ValueError("training dtype must be float32 or bfloat16")
         self.training_dtype = dtype
         self.proj_attn.training_dtype = dtype
+        return self
+
+    def set_self_attention_training(self, backend):
+        """Backend of the init_self_attention block on the autograd path (_attend_queries_autograd).  "torch" (default, or the
+        environment variable MVG_SELF_ATTN_TRAIN): nn.MultiheadAttention, fp32.  "native": the HIP training kernels of
+        csrc/mha.hip -- forward with lse, deterministic backward, attention dropout inside the kernels -- in training_dtype
+        (_attend_queries_native).  The inference path does not read it."""
+        if backend not in ("torch", "native"):
+            raise ValueError("self-attention training backend must be 'torch' or 'native'")
+        self.self_attention_training = backend
         return self
 
     def _check_supported(self):
@@ -650,13 +667,38 @@ class DQDecoderLayer(MvPDecoderLayer):
     def _attend_queries_autograd(self, tgt, query_pos):
         """attend_queries as differentiable torch ops through the layer's own self_attn module (dq_decoder.py:532-539): torch's
         attention op with need_weights=False (no Lq x Lq probabilities are returned or kept for the caller), attention dropout
-        and dropout2 as in the reference.  fp32 whatever training_dtype says: bf16 mixed-precision training of this block and
-        a HIP attention backward are not built."""
+        and dropout2 as in the reference.  fp32 whatever training_dtype says.  With set_self_attention_training("native") the
+        block runs on the HIP training kernels instead (_attend_queries_native), in training_dtype."""
+        if self.self_attention_training == "native":
+            return self._attend_queries_native(tgt, query_pos)
         f32 = torch.float32
         t = tgt.to(f32)
         qk = self.with_pos_embed(t, None if query_pos is None else query_pos.to(f32)).transpose(0, 1)
         with torch.autocast(device_type=tgt.device.type, enabled=False):
             tgt2 = self.self_attn(qk, qk, t.transpose(0, 1), need_weights=False)[0].transpose(0, 1)
+        return self.norm2(t + self.dropout2(tgt2))
+
+    def _attend_queries_native(self, tgt, query_pos):
+        """_attend_queries_autograd on the project's own kernels: [Wq; Wk] on tgt + query_pos and Wv on tgt as fp32
+        functions.linear (LinearF32S), functions.self_attention on the column blocks where they lie (csrc/mha.hip: forward with
+        lse, deterministic backward; attention dropout inside the kernels while self.training), out_proj as functions.linear,
+        norm2(t + dropout2(.)).  training_dtype bfloat16 rounds q, k, v to bf16 and runs the bf16 kernels (P, dP, dS, lse, delta
+        fp32; the attention output and dq, dk, dv bf16); the three projections keep fp32 operands."""
+        from . import functions as Fn
+        if not tgt.is_cuda:
+            raise RuntimeError("Not implemented on the CPU")
+        sa, f32, C = self.self_attn, torch.float32, self.d_model
+        if sa.in_proj_weight is None or sa.in_proj_bias is None or sa.bias_k is not None or sa.bias_v is not None:
+            raise NotImplementedError("DQDecoderLayer: self_attn with separate projection weights, without bias or with bias_k / "
+                                      "bias_v is not built")
+        t = tgt.to(f32)
+        x = self.with_pos_embed(t, None if query_pos is None else query_pos.to(f32))
+        qk = Fn.linear(x, sa.in_proj_weight[:2 * C], sa.in_proj_bias[:2 * C])
+        v = Fn.linear(t, sa.in_proj_weight[2 * C:], sa.in_proj_bias[2 * C:])
+        if self.training_dtype == torch.bfloat16:
+            qk, v = qk.to(torch.bfloat16), v.to(torch.bfloat16)
+        a = Fn.self_attention(qk[..., :C], qk[..., C:], v, dropout_p=sa.dropout, training=self.training)
+        tgt2 = Fn.linear(a.to(f32), sa.out_proj.weight, sa.out_proj.bias)
         return self.norm2(t + self.dropout2(tgt2))
 
     # The layer in two halves, so that a query-sharded run can put its one per-layer exchange (the global
@@ -860,6 +902,15 @@ class DQDecoder(MvPDecoder):
             raise ValueError("training dtype must be float32 or bfloat16")
         for layer in self.layers:
             layer.set_training_dtype(dtype)
+        return self
+
+    def set_self_attention_training(self, backend):
+        """DQDecoderLayer.set_self_attention_training on every layer ("torch" default, or "native": the init_self_attention
+        block's training on the HIP attention kernels)"""
+        if backend not in ("torch", "native"):
+            raise ValueError("self-attention training backend must be 'torch' or 'native'")
+        for layer in self.layers:
+            layer.set_self_attention_training(backend)
         return self
 
     def fork_side_stream(self, device, f32_shape=None):

@@ -187,6 +187,43 @@ def linear(x, weight, bias=None, relu=False):
     return torch.relu(y) if relu else y
 
 
+class SelfAttentionFunction(Function):
+    """softmax(q k^T / sqrt(32)) v per (batch element, head) with both directions on csrc/mha.hip: mvg_self_attention_train keeps
+    the row statistic lse, mvg_self_attention_backward recomputes P from it (no Lq x Lq tensor is saved) and writes dq, dk, dv
+    deterministically, in the inputs' dtype.  p_drop > 0: attention dropout inside the kernels from `seed` (1-element int64
+    device tensor, saved for the backward: both directions see one mask)."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, p_drop, seed):
+        out, lse = ops.self_attention_train(q, k, v, p_drop, seed)
+        ctx.p_drop = p_drop
+        ctx.save_for_backward(q, k, v, out, lse, seed if p_drop > 0 else None)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        q, k, v, out, lse, seed = ctx.saved_tensors
+        dq, dk, dv = ops.self_attention_backward(q, k, v, out, grad_out.contiguous(), lse, ctx.p_drop, seed)
+        return dq, dk, dv, None, None
+
+
+def attention_seed(device):
+    """a fresh dropout seed for self_attention: 1-element int64 tensor drawn on the device by torch's generator on the current
+    stream -- torch.manual_seed repeats it, a captured graph draws a new one per replay, and the host never reads it"""
+    return torch.empty((1,), dtype=torch.int64, device=device).random_()
+
+
+def self_attention(q, k, v, dropout_p=0.0, training=False, seed=None):
+    """differentiable ops.self_attention (SelfAttentionFunction): q, k, v (B, Lq, 256) float32 or bfloat16, column blocks of wider
+    tensors allowed.  Attention dropout with dropout_p while `training`, as nn.MultiheadAttention applies it; seed: the tensor to
+    take the mask from (default: attention_seed, a fresh one per call)."""
+    p = float(dropout_p) if training else 0.0
+    if p > 0.0 and seed is None:
+        seed = attention_seed(q.device)
+    return SelfAttentionFunction.apply(q, k, v, p, seed)
+
+
 class RefGatherAdd(Function):
     """xin[n, q, l] = bilinear(feat[n], level l, reference point (n, q, l)) + query[n, q]  (projattn.py:134-141,180: grid_sample at the
     clamped reference points, zeros padding, align_corners=False) through mvg_gather_ref; differentiable in `query` only."""

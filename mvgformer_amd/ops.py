@@ -768,28 +768,100 @@ def self_attention(q, k, v):
     bfloat16 (all the same), 8 heads in columns 32 h .. 32 h + 31 -- what nn.MultiheadAttention computes between its in- and
     out-projection.  Each may be a column block of a wider (B, Lq, n) tensor (last stride 1, batch stride Lq * row stride): the
     in-projection's output is attended where it lies.  Returns (B, Lq, 256) in the inputs' dtype.  Finite inputs only."""
-    L.require_cuda(q, k, v)
-    if q.dim() != 3 or q.shape != k.shape or q.shape != v.shape:
-        raise RuntimeError("self_attention: q, k, v of one shape (B, Lq, C) expected, got %s %s %s"
-                           % (tuple(q.shape), tuple(k.shape), tuple(v.shape)))
-    B, Lq, Cc = q.shape
-    if Cc != 256 or Lq < 1 or B < 1:
-        raise RuntimeError("self_attention: built for d_model 256 (8 heads of 32), B >= 1, Lq >= 1; got %s" % (tuple(q.shape),))
-    if q.dtype not in (torch.float32, torch.bfloat16) or k.dtype != q.dtype or v.dtype != q.dtype:
-        raise RuntimeError("self_attention: q, k, v all float32 or all bfloat16, got %s %s %s" % (q.dtype, k.dtype, v.dtype))
-    if q.device != k.device or q.device != v.device:
-        raise RuntimeError("self_attention: q, k, v on one device expected")
-    vec = 16 // q.element_size()
-    for name, t in (("q", q), ("k", k), ("v", v)):
-        if t.stride(2) != 1 or (B > 1 and t.stride(0) != Lq * t.stride(1)) or t.stride(1) < Cc or t.stride(1) % vec \
-                or t.data_ptr() % 16:
-            raise RuntimeError("self_attention: %s must be row-major (a column block of a row-major tensor at most), 16-byte "
-                               "aligned rows; strides %s" % (name, t.stride()))
+    B, Lq, Cc = _attention_operands("self_attention", q=q, k=k, v=v)
     out = torch.empty((B, Lq, Cc), dtype=q.dtype, device=q.device)
     with _timed("self_attention"):
       L.check(L.load().mvg_self_attention(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(out), q.stride(1), k.stride(1), v.stride(1), B, Lq, Cc,
                                           8, L.dtype_code(q.dtype), L.stream_ptr()), "mvg_self_attention")
     return out
+
+
+def _attention_operands(fn, **tensors):
+    """the checks the attention kernels' (B, Lq, 256) operands share; the first one sets shape, dtype and device.  -> (B, Lq, C)"""
+    L.require_cuda(*tensors.values())
+    names, ts = ", ".join(tensors), list(tensors.values())
+    q = ts[0]
+    if q.dim() != 3 or any(t.shape != q.shape for t in ts):
+        raise RuntimeError("%s: %s of one shape (B, Lq, C) expected, got %s" % (fn, names, " ".join(str(tuple(t.shape)) for t in ts)))
+    B, Lq, Cc = q.shape
+    if Cc != 256 or Lq < 1 or B < 1:
+        raise RuntimeError("%s: built for d_model 256 (8 heads of 32), B >= 1, Lq >= 1; got %s" % (fn, tuple(q.shape)))
+    if q.dtype not in (torch.float32, torch.bfloat16) or any(t.dtype != q.dtype for t in ts):
+        raise RuntimeError("%s: %s all float32 or all bfloat16, got %s" % (fn, names, " ".join(str(t.dtype) for t in ts)))
+    if any(t.device != q.device for t in ts):
+        raise RuntimeError("%s: %s on one device expected" % (fn, names))
+    vec = 16 // q.element_size()
+    for name, t in tensors.items():
+        if t.stride(2) != 1 or (B > 1 and t.stride(0) != Lq * t.stride(1)) or t.stride(1) < Cc or t.stride(1) % vec \
+                or t.data_ptr() % 16:
+            raise RuntimeError("%s: %s must be row-major (a column block of a row-major tensor at most), 16-byte "
+                               "aligned rows; strides %s" % (fn, name, t.stride()))
+    return B, Lq, Cc
+
+
+def _attention_seed(fn, p_drop, seed, device):
+    """p_drop in [0, 1); with p_drop > 0 the seed is a 1-element int64 tensor on the device (the kernels read it there)"""
+    p_drop = float(p_drop)
+    if not 0.0 <= p_drop < 1.0:
+        raise RuntimeError("%s: p_drop in [0, 1) expected, got %r" % (fn, p_drop))
+    if p_drop > 0.0 and (seed is None or seed.dtype != torch.int64 or seed.numel() != 1 or seed.device != device):
+        raise RuntimeError("%s: dropout needs seed, a 1-element int64 tensor on %s" % (fn, device))
+    return p_drop, (seed if p_drop > 0.0 else None)
+
+
+def dropout_p_quantised(p_drop):
+    """the probability the attention kernels drop with: p_drop rounded to 8 bits (at most 255 / 256)"""
+    return min(255, int(float(p_drop) * 256.0 + 0.5)) / 256.0
+
+
+def self_attention_train(q, k, v, p_drop=0.0, seed=None):
+    """self_attention for training (mvg_self_attention_train): -> (out, lse).  out as self_attention gives it (the same bits with
+    p_drop == 0), lse (B, 8, Lq) float32 = ln sum_j exp(q_i . k_j / sqrt(32)) for self_attention_backward.  p_drop > 0: attention
+    dropout inside the kernel, out = (keep o P / (1 - p_q)) v with p_q = dropout_p_quantised(p_drop) and keep a function of
+    (seed, b, head, query, key) alone (self_attention_dropout_mask); seed: 1-element int64 device tensor, read by the kernel."""
+    B, Lq, Cc = _attention_operands("self_attention_train", q=q, k=k, v=v)
+    p_drop, seed = _attention_seed("self_attention_train", p_drop, seed, q.device)
+    out = torch.empty((B, Lq, Cc), dtype=q.dtype, device=q.device)
+    lse = torch.empty((B, 8, Lq), dtype=torch.float32, device=q.device)
+    with _timed("self_attention_train"):
+      L.check(L.load().mvg_self_attention_train(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(out), L.ptr(lse), q.stride(1), k.stride(1),
+                                                v.stride(1), B, Lq, Cc, 8, L.dtype_code(q.dtype), p_drop, L.ptr(seed), L.stream_ptr()),
+              "mvg_self_attention_train")
+    return out, lse
+
+
+def self_attention_backward(q, k, v, out, dout, lse, p_drop=0.0, seed=None):
+    """(dq, dk, dv) of self_attention_train's out (mvg_self_attention_backward: deterministic, no atomics), in the inputs' dtype,
+    contiguous.  q, k, v, lse, p_drop, seed as the forward had them; out as it returned it; dout (B, Lq, 256) contiguous."""
+    B, Lq, Cc = _attention_operands("self_attention_backward", q=q, k=k, v=v, out=out, dout=dout)
+    p_drop, seed = _attention_seed("self_attention_backward", p_drop, seed, q.device)
+    if not out.is_contiguous() or not dout.is_contiguous():
+        raise RuntimeError("self_attention_backward: out, dout must be row-major and contiguous; strides %s %s" % (out.stride(), dout.stride()))
+    if lse.shape != (B, 8, Lq) or lse.dtype != torch.float32 or not lse.is_contiguous() or lse.device != q.device:
+        raise RuntimeError("self_attention_backward: lse (B, 8, Lq) float32 contiguous expected, got %s %s" % (tuple(lse.shape), lse.dtype))
+    dq, dk, dv = (torch.empty((B, Lq, Cc), dtype=q.dtype, device=q.device) for _ in range(3))
+    lib = L.load()
+    nbytes = int(lib.mvg_self_attention_backward_workspace(B, Lq))
+    ws = torch.empty((nbytes // 4,), dtype=torch.float32, device=q.device)
+    with _timed("self_attention_backward"):
+      L.check(lib.mvg_self_attention_backward(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(out), L.ptr(dout), L.ptr(lse), L.ptr(dq), L.ptr(dk),
+                                              L.ptr(dv), q.stride(1), k.stride(1), v.stride(1), Cc, Cc, Cc, B, Lq, Cc, 8,
+                                              L.dtype_code(q.dtype), p_drop, L.ptr(seed), L.ptr(ws), nbytes, L.stream_ptr()),
+              "mvg_self_attention_backward")
+    return dq, dk, dv
+
+
+def self_attention_dropout_mask(B, Lq, p_drop, seed):
+    """(B, 8, Lq, Lq) uint8 keep mask of the attention dropout for `seed` (1 = kept), from the device function the training
+    kernels call (mvg_self_attention_dropout_mask): a test and debugging aid, Lq <= 1024."""
+    L.require_cuda(seed)
+    p_drop, seed = _attention_seed("self_attention_dropout_mask", p_drop, seed, None if seed is None else seed.device)
+    if B < 1 or not 1 <= Lq <= 1024:
+        raise RuntimeError("self_attention_dropout_mask: B >= 1, 1 <= Lq <= 1024 expected, got B %d Lq %d" % (B, Lq))
+    mask = torch.empty((B, 8, Lq, Lq), dtype=torch.uint8, device="cuda" if seed is None else seed.device)
+    L.check(L.load().mvg_self_attention_dropout_mask(L.ptr(mask), B, Lq, p_drop, L.ptr(seed), L.stream_ptr()),
+            "mvg_self_attention_dropout_mask")
+    return mask
 
 
 def class_head(tgt, Wc, bc, threshold, B, NQ, J, forced_valid=None):
