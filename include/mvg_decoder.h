@@ -631,6 +631,47 @@ size_t mvg_pose_nms_workspace(int B, int N, int J);
 int mvg_pose_nms(const float* pred, int B, int N, int J, double dist_thr, int num_nearby_joints_thr, int max_dets, void* workspace,
                  size_t workspace_bytes, int* keep, int* count, float* dets, int dets_rows, void* stream);
 
+/* ---- validation scoring behind the NMS (csrc/evalacc.hip) ------------------------------------------------------------------- */
+#define MVG_EVAL_MAX_R 2048           /* rows of dets per batch element                                                        */
+#define MVG_EVAL_MAX_J 32
+#define MVG_EVAL_MAX_G 64             /* person slots of the ground truth, actors of the PCP counters                          */
+#define MVG_EVAL_MAX_B 256
+#define MVG_EVAL_STATE_WORDS 8        /* int64 state block: n_entries, total_gt, frames, overflow, kept_rows, match_gt,
+                                       * empty_frame (1 + the first frame that has an annotated actor and no row; 0: none), 0 */
+
+/* Ground-truth matching of Panoptic.evaluate (lib/dataset/panoptic.py:497-556) on the device, accumulated over calls: TWO launches,
+ * fixed shapes, nothing read back, integer LDS atomics only, bit-reproducible; can be captured in a HIP graph behind mvg_pose_nms.
+ *   dets (B, R, J, 5) fp32 rows [x, y, z, flag, score] and count (B, 2) int32 or NULL as mvg_pose_nms leaves them: row i of element
+ *   b takes part iff dets[b, i, 0, 3] >= 0 and (count == NULL or i < count[b, 0]).
+ *   joints_3d (B, Gmax, J, 3) fp32, joints_3d_vis (B, Gmax, J) fp32 (visible iff > 0), num_person (B) int32 (clamped to [0, Gmax]).
+ *   An element with num_person == 0 appends nothing and adds nothing to total_gt.  Every other element appends, per participating
+ *   row in row order, mean_g = sum_j (dist(row_j, gt_g_j) * w_j) / sum_j w_j (w = 1 for a visible joint, else 0; fp64 from the fp32
+ *   inputs, (dx^2 + dy^2) + dz^2, correctly rounded sqrt, joints in order; 0 / 0 = NaN for a person without visible joint) for
+ *   every g < num_person, takes the FIRST minimum over g with NaN ordered as +inf, and writes mpjpe = that mean as computed,
+ *   score = the row's score, gt_id = total_gt before this element + g.  Entries go to mpjpe / score / gt_id (capacity each) at the
+ *   cursor state[0], elements in batch order; an entry at or past `capacity` is not written.  After every element has read the
+ *   state, a one-workgroup launch adds the entries to state[0] (also past the capacity), sum(num_person) to state[1], B to
+ *   state[2], the participating rows of ALL elements to state[4], and sets state[3] = 1 when state[0] > capacity.
+ * MVG_E_BADARG, and nothing launched, for B, R, J or Gmax < 1 or above their MVG_EVAL_MAX_*, capacity < 1, a NULL pointer other
+ * than count, an output or state pointer that is not 8-byte aligned. */
+int mvg_eval_match(const float* dets, const int* count, const float* joints_3d, const float* joints_3d_vis, const int* num_person, int B,
+                   int R, int J, int Gmax, double* mpjpe, double* score, int64_t* gt_id, int64_t capacity, int64_t* state,
+                   void* stream);
+
+/* PCP counters of Shelf.evaluate / Campus.evaluate (lib/dataset/shelf.py:255-330) on the device, accumulated over calls: ONE launch
+ * of one workgroup (every counter has one writer), same inputs and participation rule as mvg_eval_match, J == 14.
+ *   For every element b in order and every actor slot a < min(num_person[b], actors) with some joints_3d_vis[b, a, :] != 0: the
+ *   participating row of smallest mean joint distance over all 14 joints (first minimum, NaN ordered as +inf); state[5] += (that
+ *   mean < recall_threshold), state[1] += 1; the nine limb tests (e_start + e_end) / 2 <= alpha * length and the hip-centre / head
+ *   test -> correct[a], total[a] (+= 10), bone_correct[a, 0..9] (int64, `actors` rows).  An element with such an actor and no
+ *   participating row is not scored further and records state[6] = 1 + state[2] + b if state[6] is still 0.  state[2] += B,
+ *   state[4] += the participating rows.
+ * MVG_E_BADARG, and nothing launched, for shapes mvg_eval_match rejects, J != 14, actors < 1 or > MVG_EVAL_MAX_G, alpha < 0 or NaN,
+ * a NaN recall_threshold, a NULL pointer other than count, a counter or state pointer that is not 8-byte aligned. */
+int mvg_eval_pcp(const float* dets, const int* count, const float* joints_3d, const float* joints_3d_vis, const int* num_person, int B,
+                 int R, int J, int Gmax, int actors, double recall_threshold, double alpha, int64_t* correct, int64_t* total,
+                 int64_t* bone_correct, int64_t* state, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

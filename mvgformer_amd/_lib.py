@@ -80,6 +80,8 @@ SIGNATURES = {
     "mvg_self_attention_backward": [_vp] * 9 + [_i] * 11 + [_f, _vp, _vp, C.c_size_t, _vp],
     "mvg_self_attention_dropout_mask": [_vp, _i, _i, _f, _vp, _vp],
     "mvg_pose_nms": [_vp, _i, _i, _i, C.c_double, _i, _i, _vp, C.c_size_t, _vp, _vp, _vp, _i, _vp],
+    "mvg_eval_match": [_vp] * 5 + [_i] * 4 + [_vp] * 3 + [C.c_int64, _vp, _vp],
+    "mvg_eval_pcp": [_vp] * 5 + [_i] * 5 + [C.c_double] * 2 + [_vp] * 5,
 }
 
 _lib = None

@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 __all__ = ["nearby_joints_nms", "filter_and_nms", "filter_and_nms_device", "match_predictions", "eval_list_to_ap", "eval_list_to_mpjpe",
-           "eval_list_to_recall", "evaluate_panoptic", "evaluate_pcp", "MPJPE_THRESHOLDS", "PCP_LIMBS"]
+           "eval_list_to_recall", "evaluate_panoptic", "evaluate_pcp", "MPJPE_THRESHOLDS", "PCP_LIMBS", "DeviceEvaluator"]
 
 MPJPE_THRESHOLDS = tuple(range(25, 155, 25))            # panoptic.py:559
 PCP_LIMBS = ((0, 1), (1, 2), (3, 4), (4, 5), (6, 7), (7, 8), (9, 10), (10, 11), (12, 13))   # shelf.py:270-271
@@ -245,8 +245,7 @@ def evaluate_pcp(preds, actor_gts, recall_threshold=500, alpha=0.5):
             if gt is None or len(gt) == 0:
                 continue
             if len(p) == 0:
-                raise ValueError("frame %d has ground truth but no prediction passed the classification filter "
-                                 "(the reference fails in np.stack here, shelf.py:284)" % f)
+                raise ValueError(_NO_PREDICTION % f)
             g = _as_tensor(gt, p.device)
             mp = torch.sqrt(((g[None] - p) ** 2).sum(-1)).mean(-1)                    # shelf.py:292-294
             n = int(torch.argmin(mp))
@@ -267,8 +266,103 @@ def evaluate_pcp(preds, actor_gts, recall_threshold=500, alpha=0.5):
                     alpha * float(torch.linalg.norm(g_hip - g[12])):
                 correct[person] += 1
                 bone_correct[person, 9] += 1
+    return _pcp_from_counters(correct, total, bone_correct, match_gt, total_gt)
+
+
+_NO_PREDICTION = ("frame %d has ground truth but no prediction passed the classification filter "
+                  "(the reference fails in np.stack here, shelf.py:284)")
+
+
+def _pcp_from_counters(correct, total, bone_correct, match_gt, total_gt):
+    """shelf.py:316-330: the counters -> (actor_pcp, avg_pcp, bone_person_pcp, recall)"""
     actor_pcp = correct / (total + 1e-8)
     avg_pcp = float(np.mean(actor_pcp[:3]))
     bone_person_pcp = OrderedDict((k, np.sum(bone_correct[:, v], axis=-1) / (total / 10 * len(v) + 1e-8))
                                   for k, v in PCP_BONE_GROUPS.items())
     return actor_pcp, avg_pcp, bone_person_pcp, match_gt / (total_gt + 1e-8)
+
+
+# --------------------------------------------------------------------------------------- scoring on the device
+class DeviceEvaluator:
+    """``match_predictions`` (kind "panoptic") or the counters of ``evaluate_pcp`` (kind "pcp") accumulated in device memory by
+    ``ops.eval_match`` / ``ops.eval_pcp``: ``update`` only launches (two launches / one, nothing read back, fixed shapes, so it can
+    be captured in a HIP graph behind ``ops.pose_nms``), the metrics are read back once, by ``eval_list`` / ``panoptic`` / ``pcp``.
+
+    update(dets, count, joints_3d, joints_3d_vis, num_person): ``dets`` (B, R, J, 5) fp32 and ``count`` (B, 2) int32 or None as
+    ``ops.pose_nms`` leaves them (row i of element b takes part when its flag is >= 0 and i < count[b, 0]); the ground truth in the
+    criterion's layout, (B, Gmax, J, 3) fp32, (B, Gmax, J) fp32 and (B) int32 with Gmax <= ``max_persons``.  Elements are frames,
+    in call order.  ``capacity`` bounds the Panoptic entry list (one entry per kept pose of a frame with ground truth): entries
+    past it are counted, not stored, and ``eval_list`` then raises with the capacity the run needs.  ``actors`` is the number of
+    actor slots of the PCP counters.  ``method="mpjpe_sort"`` (per-frame de-duplication of the list) stays on the host path."""
+
+    def __init__(self, kind="panoptic", capacity=65536, max_persons=10, actors=4, device="cuda", recall_threshold=500, alpha=0.5):
+        if kind not in ("panoptic", "pcp"):
+            raise ValueError("DeviceEvaluator: kind must be 'panoptic' or 'pcp' (got %r)" % (kind,))
+        from . import ops
+        if not 1 <= int(max_persons) <= ops.EVAL_MAX_G:
+            raise ValueError("DeviceEvaluator: 1 <= max_persons <= %d expected (got %r)" % (ops.EVAL_MAX_G, max_persons))
+        self.kind, self.capacity, self.max_persons, self.actors = kind, int(capacity), int(max_persons), int(actors)
+        self.recall_threshold, self.alpha = float(recall_threshold), float(alpha)
+        self.device = torch.device(device)
+        self.buffers = ops.eval_buffers(self.capacity, self.actors, self.device)
+
+    def ground_truth_buffers(self, batch, num_joints):
+        """zeroed static inputs (joints_3d, joints_3d_vis, num_person) for ``max_persons`` person slots (graph capture)"""
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=self.device)
+        return (z((batch, self.max_persons, num_joints, 3), torch.float32), z((batch, self.max_persons, num_joints), torch.float32),
+                z((batch,), torch.int32))
+
+    def update(self, dets, count, joints_3d, joints_3d_vis, num_person):
+        from . import ops
+        if joints_3d.dim() == 4 and joints_3d.shape[1] > self.max_persons:
+            raise ValueError("DeviceEvaluator: %d person slots, built for max_persons = %d" % (joints_3d.shape[1], self.max_persons))
+        with torch.cuda.device(dets.device) if dets.is_cuda else contextlib.nullcontext():
+            if self.kind == "panoptic":
+                ops.eval_match(dets, count, joints_3d, joints_3d_vis, num_person, self.buffers)
+            else:
+                ops.eval_pcp(dets, count, joints_3d, joints_3d_vis, num_person, self.buffers, self.recall_threshold, self.alpha)
+        return self
+
+    def reset(self):
+        for t in self.buffers.values():
+            t.zero_()
+        return self
+
+    def state(self):
+        """the state block as a dict of ints (a read-back)"""
+        from . import ops
+        return dict(zip(ops.EVAL_STATE, self.buffers["state"].cpu().tolist()))
+
+    def eval_list(self):
+        """-> (dict(mpjpe, score, gt_id), total_gt) as numpy, like ``match_predictions``: the one read-back of a Panoptic run"""
+        if self.kind != "panoptic":
+            raise ValueError("DeviceEvaluator: eval_list belongs to kind 'panoptic'")
+        st = self.state()
+        if st["overflow"]:
+            raise RuntimeError("DeviceEvaluator: %d entries do not fit capacity %d; build it with capacity >= %d"
+                               % (st["n_entries"], self.capacity, st["n_entries"]))
+        n = st["n_entries"]
+        return {k: self.buffers[k][:n].cpu().numpy() for k in ("mpjpe", "score", "gt_id")}, st["total_gt"]
+
+    def panoptic(self, method="score_sort"):
+        """the tuple of ``evaluate_panoptic`` from the device's list"""
+        if method == "mpjpe_sort":
+            raise ValueError("DeviceEvaluator: mpjpe_sort de-duplicates per frame on the host; use evaluate_panoptic")
+        ev, total_gt = self.eval_list()
+        aps, recs = [], []
+        for t in MPJPE_THRESHOLDS:
+            ap, rec = eval_list_to_ap(ev, total_gt, t, method)
+            aps.append(ap)
+            recs.append(rec)
+        return aps, recs, eval_list_to_mpjpe(ev, method=method), eval_list_to_recall(ev, total_gt)
+
+    def pcp(self):
+        """the tuple of ``evaluate_pcp`` from the device's counters; raises its ValueError for a frame that has an annotated actor
+        and no prediction"""
+        if self.kind != "pcp":
+            raise ValueError("DeviceEvaluator: pcp belongs to kind 'pcp'")
+        st = self.state()
+        if st["empty_frame"]:
+            raise ValueError(_NO_PREDICTION % (st["empty_frame"] - 1))
+        f64 = lambda k: self.buffers[k].cpu().numpy().astype(np.float64)
+        return _pcp_from_counters(f64("correct"), f64("total"), f64("bone_correct"), st["match_gt"], st["total_gt"])

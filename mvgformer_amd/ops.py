@@ -1264,3 +1264,74 @@ def pose_nms(pred, dist_thr=0.3, num_nearby_joints_thr=7, max_dets=-1, dets_rows
                                  ws.numel() * ws.element_size(), L.ptr(keep), L.ptr(count), L.ptr(dets), dets.shape[1],
                                  L.stream_ptr()), "mvg_pose_nms")
     return keep, count, dets
+
+
+EVAL_MAX_R, EVAL_MAX_J, EVAL_MAX_G, EVAL_MAX_B = 2048, 32, 64, 256      # MVG_EVAL_MAX_*
+EVAL_STATE = ("n_entries", "total_gt", "frames", "overflow", "kept_rows", "match_gt", "empty_frame", "reserved")
+
+
+def eval_buffers(capacity, actors=4, device="cuda"):
+    """the zeroed accumulators of eval_match / eval_pcp: the entry list mpjpe / score (capacity) fp64 and gt_id (capacity) int64,
+    the PCP counters correct / total (actors) and bone_correct (actors, 10) int64, and the int64 state block (EVAL_STATE).
+    Allocated once and kept alive by the caller: a captured HIP graph addresses them by pointer, like pose_nms_buffers."""
+    capacity, actors = int(capacity), int(actors)
+    if capacity < 1 or not 1 <= actors <= EVAL_MAX_G:
+        raise L.MvgError("eval_buffers: capacity >= 1 and 1 <= actors <= %d expected (got %d, %d)" % (EVAL_MAX_G, capacity, actors))
+    z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=device)
+    return dict(mpjpe=z((capacity,), torch.float64), score=z((capacity,), torch.float64), gt_id=z((capacity,), torch.int64),
+                correct=z((actors,), torch.int64), total=z((actors,), torch.int64), bone_correct=z((actors, 10), torch.int64),
+                state=z((len(EVAL_STATE),), torch.int64))
+
+
+def _eval_inputs(name, dets, count, joints_3d, joints_3d_vis, num_person, buffers, keys):
+    out = [buffers[k] for k in keys]
+    L.require_cuda(dets, count, joints_3d, joints_3d_vis, num_person, *out)
+    if dets.dim() != 4 or dets.shape[-1] != 5 or dets.dtype != torch.float32:
+        raise RuntimeError("%s: dets (B, R, J, 5) float32 expected" % name)
+    B, R, J = dets.shape[:3]
+    if (joints_3d.dim() != 4 or joints_3d.dtype != torch.float32 or joints_3d.shape[0] != B or tuple(joints_3d.shape[2:]) != (J, 3)):
+        raise RuntimeError("%s: joints_3d (B, Gmax, J, 3) float32 expected for dets %s" % (name, tuple(dets.shape)))
+    G = joints_3d.shape[1]
+    if (joints_3d_vis.dtype != torch.float32 or tuple(joints_3d_vis.shape) != (B, G, J) or num_person.dtype != torch.int32
+            or tuple(num_person.shape) != (B,) or (count is not None and (count.dtype != torch.int32 or tuple(count.shape) != (B, 2)))):
+        raise RuntimeError("%s: joints_3d_vis (B, Gmax, J) float32, num_person (B) int32 and count (B, 2) int32 or None expected" % name)
+    if not all(t is None or t.is_contiguous() for t in (dets, count, joints_3d, joints_3d_vis, num_person, *out)):
+        raise RuntimeError("%s: every tensor must be contiguous" % name)
+    if any(t.dtype != (torch.int64 if k in ("gt_id", "correct", "total", "bone_correct", "state") else torch.float64)
+           for k, t in zip(keys, out)) or buffers["state"].numel() != len(EVAL_STATE):
+        raise RuntimeError("%s: buffers are not those of eval_buffers" % name)
+    return B, R, J, G
+
+
+def eval_match(dets, count, joints_3d, joints_3d_vis, num_person, buffers):
+    """Panoptic ground-truth matching on the device (mvg_eval_match: two launches, nothing read back, no synchronisation;
+    panoptic.py:497-556 as evaluate.match_predictions restates it for score_sort).  dets (B, R, J, 5) fp32 and count (B, 2) int32
+    or None as pose_nms leaves them; joints_3d (B, Gmax, J, 3) fp32, joints_3d_vis (B, Gmax, J) fp32 (visible when > 0),
+    num_person (B) int32.  Appends (mpjpe, score, gt_id) of every participating row to ``buffers`` (eval_buffers) in the
+    reference's order and advances the state block; entries past the capacity are counted, not written."""
+    keys = ("mpjpe", "score", "gt_id", "state")
+    B, R, J, G = _eval_inputs("mvg_eval_match", dets, count, joints_3d, joints_3d_vis, num_person, buffers, keys)
+    mp, sc, gid, state = (buffers[k] for k in keys)
+    if not (mp.dim() == 1 and mp.shape == sc.shape == gid.shape):
+        raise RuntimeError("mvg_eval_match: buffers are not those of eval_buffers")
+    lib = L.load()
+    with _timed("eval_match"):
+        L.check(lib.mvg_eval_match(L.ptr(dets), L.ptr(count), L.ptr(joints_3d), L.ptr(joints_3d_vis), L.ptr(num_person), B, R, J, G,
+                                   L.ptr(mp), L.ptr(sc), L.ptr(gid), mp.numel(), L.ptr(state), L.stream_ptr()), "mvg_eval_match")
+
+
+def eval_pcp(dets, count, joints_3d, joints_3d_vis, num_person, buffers, recall_threshold=500.0, alpha=0.5):
+    """PCP counters of Shelf.evaluate / Campus.evaluate on the device (mvg_eval_pcp: one launch, nothing read back; shelf.py:255-330
+    as evaluate.evaluate_pcp restates it).  Inputs as eval_match, in the 14-joint format; actor slot a of element b is annotated
+    when some joints_3d_vis[b, a] != 0.  Adds to correct / total / bone_correct and the state block of ``buffers``."""
+    keys = ("correct", "total", "bone_correct", "state")
+    B, R, J, G = _eval_inputs("mvg_eval_pcp", dets, count, joints_3d, joints_3d_vis, num_person, buffers, keys)
+    correct, total, bones, state = (buffers[k] for k in keys)
+    A = correct.numel()
+    if tuple(total.shape) != (A,) or tuple(bones.shape) != (A, 10):
+        raise RuntimeError("mvg_eval_pcp: buffers are not those of eval_buffers")
+    lib = L.load()
+    with _timed("eval_pcp"):
+        L.check(lib.mvg_eval_pcp(L.ptr(dets), L.ptr(count), L.ptr(joints_3d), L.ptr(joints_3d_vis), L.ptr(num_person), B, R, J, G, A,
+                                 float(recall_threshold), float(alpha), L.ptr(correct), L.ptr(total), L.ptr(bones), L.ptr(state),
+                                 L.stream_ptr()), "mvg_eval_pcp")

@@ -30,6 +30,12 @@ order, ``count[b] = [kept, skipped]`` and the kept row indices -- static tensors
         dets, count, keep = runner.detections
         n = int(count[0, 0])                # the frame's one read-back
         poses = dets[0, :n]                 # (n, J, 5) on the device
+
+``evaluation=dict(kind="panoptic" | "pcp", capacity=..., max_persons=10, actors=4, recall_threshold=500, alpha=0.5)`` (requires
+``postprocess``) continues behind the NMS with ``evaluate.DeviceEvaluator.update`` on static ground-truth inputs
+(``load(ground_truth=(joints_3d, joints_3d_vis, num_person))``): the kept poses of every replayed frame are scored on the device
+and accumulated in ``runner.evaluator``; nothing is read back per frame, the metrics once (``runner.evaluator.panoptic()`` /
+``.pcp()``).  The warm-up forwards of a capture leave the accumulators as they were.
 """
 from __future__ import annotations
 
@@ -40,7 +46,7 @@ from .decoder import DecoderContext
 
 class GraphedDecoder:
     def __init__(self, decoder, meta, spatial_shapes, level_start_index, batch, num_queries, threshold=0.1, device=None,
-                 producer_writes_in_place=False, channels=256, postprocess=None, convert_joint_format_indices=None):
+                 producer_writes_in_place=False, channels=256, postprocess=None, convert_joint_format_indices=None, evaluation=None):
         layer0 = decoder.layers[0]
         dev = torch.device(device) if device is not None else next(decoder.parameters()).device
         if dev.type != "cuda":
@@ -80,12 +86,39 @@ class GraphedDecoder:
             self.postprocess = dict(dist_thr=0.3, num_nearby_joints_thr=7, max_dets=-1, dets_rows=None)
             self.postprocess.update(postprocess)
             j_out = J if convert_joint_format_indices is None else len(convert_joint_format_indices)
+            if convert_joint_format_indices is not None and not torch.is_tensor(convert_joint_format_indices):
+                # a list would be copied to the device inside the captured region (caller.decoder_outputs_to_dict), which a
+                # capturing stream refuses: the Shelf / Campus joint map lives on the device from here on
+                self.convert_joint_format_indices = torch.as_tensor(list(convert_joint_format_indices), dtype=torch.long, device=dev)
             self._nms = ops.pose_nms_buffers(batch, num_queries, j_out, self.postprocess["dets_rows"], dev)
             self.detections = (self._nms["dets"], self._nms["count"], self._nms["keep"])
+        # optional scoring of the kept poses against ground truth behind the NMS, inside the same graph
+        self.evaluator, self.ground_truth = None, None
+        if evaluation is not None:
+            from .evaluate import DeviceEvaluator
+            if postprocess is None:
+                raise ValueError("GraphedDecoder: evaluation scores the rows the NMS keeps; it requires postprocess")
+            unknown = set(evaluation) - {"kind", "capacity", "max_persons", "actors", "recall_threshold", "alpha"}
+            if unknown:
+                raise TypeError("GraphedDecoder: unknown evaluation keys %s" % sorted(unknown))
+            self.evaluator = DeviceEvaluator(device=dev, **evaluation)
+            self.ground_truth = self.evaluator.ground_truth_buffers(batch, self._nms["dets"].shape[2])
 
     # ------------------------------------------------------------------ inputs (device-side copies on the current stream)
-    def load(self, src_views=None, tgt=None, query_pos=None, reference_points=None):
+    def load(self, src_views=None, tgt=None, query_pos=None, reference_points=None, ground_truth=None):
+        """ground_truth = (joints_3d (B, G, J, 3), joints_3d_vis (B, G, J), num_person (B)) with G <= max_persons, for a runner
+        built with ``evaluation``: copied into the static inputs the evaluator reads; person slots behind G are not scored."""
         with torch.no_grad():
+            if ground_truth is not None:
+                if self.evaluator is None:
+                    raise ValueError("GraphedDecoder: ground_truth needs a runner built with evaluation=dict(...)")
+                j3d, vis, num = ground_truth
+                if j3d.shape[1] > self.ground_truth[0].shape[1]:
+                    raise ValueError("GraphedDecoder: %d person slots, built for max_persons = %d"
+                                     % (j3d.shape[1], self.ground_truth[0].shape[1]))
+                self.ground_truth[0][:, :j3d.shape[1]].copy_(j3d, non_blocking=True)
+                self.ground_truth[1][:, :vis.shape[1]].copy_(vis, non_blocking=True)
+                self.ground_truth[2].copy_(num, non_blocking=True)
             if src_views is not None:
                 for dst, s in zip(self.src_views, src_views):
                     dst.copy_(s, non_blocking=True)
@@ -117,12 +150,19 @@ class GraphedDecoder:
             self.pred = caller.pack_predictions(out, self.thr)                       # function.py:386-396
             pp = self.postprocess
             ops.pose_nms(self.pred, pp["dist_thr"], pp["num_nearby_joints_thr"], pp["max_dets"], pp["dets_rows"], out=self._nms)
+            if self.evaluator is not None:
+                self.evaluator.update(self._nms["dets"], self._nms["count"], *self.ground_truth)
         return outputs
 
     def capture(self, warmup=2):
         with torch.no_grad():
+            # the warm-up forwards score whatever is loaded: the accumulators are put back, so a (re-)capture counts no frame
+            saved = None if self.evaluator is None else {k: t.clone() for k, t in self.evaluator.buffers.items()}
             for _ in range(max(1, warmup)):         # builds the weight caches, sizes the per-layer buffers
                 self._forward()
+            if saved is not None:
+                for k, t in self.evaluator.buffers.items():
+                    t.copy_(saved[k])
             torch.cuda.synchronize(self.dev)
             self.graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.graph):
@@ -141,6 +181,8 @@ class GraphedDecoder:
         keep = [self.ctx.cams, self.ctx.feat, getattr(self.ctx, "_buffer", None)]
         if self._nms is not None:
             keep += list(self._nms.values())
+        if self.evaluator is not None:
+            keep += list(self.evaluator.buffers.values()) + list(self.ground_truth)
         for l in self.dec.layers:
             keep += [l.proj_attn._vp, l.proj_attn._G]
             for wc in (l._wc, l.proj_attn._wc):
@@ -164,6 +206,7 @@ class GraphedDecoder:
 
     def eager(self):
         """the same forward without the graph (reference for tests; identical results).  With ``postprocess`` it takes the same
-        path as the capture: ``pred`` is this call's packed predictions, ``detections`` the same static buffers."""
+        path as the capture: ``pred`` is this call's packed predictions, ``detections`` the same static buffers, and with
+        ``evaluation`` the frame is scored into ``evaluator`` like a replayed one."""
         with torch.no_grad():
             return self._forward()

@@ -12,6 +12,10 @@ The backbone (PoseResNet-50) and the dataset loaders are out of scope (SURVEY.md
 camera arrays of ``meta`` and optionally ``joints_3d`` / ``joints_3d_vis``), or seeded synthetic frames of the YAML's
 geometry (``mvgformer_amd.synthetic``).  ``--cfg extract:<relative path>`` reads the values of the reference's YAML from
 ``mvgformer_amd/data/yaml_extract.json`` where the reference tree does not exist.
+
+``--device-nms 1`` runs the classification filter and the NMS on the device (inside the HIP graph with ``--graph 1``);
+``--device-eval 1`` on top of it scores the kept poses against the ground truth there as well (``evaluate.DeviceEvaluator``): the
+frame loop then reads nothing back and the metrics are fetched once per threshold.
 """
 from __future__ import annotations
 
@@ -107,11 +111,32 @@ def actor_ground_truth(gts, gts_vis):
             for a in range(n_actor)]
 
 
-def pcp_report(kept, gts, gts_vis):
-    """the PCP entry of a result row (Shelf.evaluate / Campus.evaluate through evaluate.evaluate_pcp), in percent"""
+def device_ground_truth(frames, kind, num_joints, device):
+    """--device-eval: per frame the evaluator's inputs (joints_3d (1, G, J, 3) fp32, joints_3d_vis (1, G, J) fp32, num_person (1)
+    int32) on the device, built before the frame loop; G = the largest person count.  kind None (no ground truth, or none that is
+    scored): num_person 0 everywhere, the evaluator only counts the kept poses.  Visibility is reduced the way the host scoring
+    reads it: its first component for Panoptic (match_predictions), "some component != 0" for PCP (actor_ground_truth)."""
+    scored = [f[2] for f in frames if f[2] is not None and kind is not None]
+    G = max([len(gt[0]) for gt in scored] + [1])
+    out = []
+    for _, _, gt in frames:
+        j3d, vis, n = torch.zeros((1, G, num_joints, 3)), torch.zeros((1, G, num_joints)), 0
+        if gt is not None and kind is not None and len(gt[0]):
+            g, v = np.asarray(gt[0]), np.asarray(gt[1])
+            n = len(g)
+            j3d[0, :n] = torch.from_numpy(g[..., :3].astype(np.float32))
+            seen = v[..., 0] > 0 if kind == "panoptic" else (v != 0).reshape(n, num_joints, -1).any(-1)
+            vis[0, :n] = torch.from_numpy(seen.astype(np.float32))
+        out.append((j3d.to(device), vis.to(device), torch.tensor([n], dtype=torch.int32, device=device)))
+    return G, out
+
+
+def pcp_report(kept, gts, gts_vis, evaluator=None):
+    """the PCP entry of a result row (Shelf.evaluate / Campus.evaluate through evaluate.evaluate_pcp, or the counters of a
+    DeviceEvaluator), in percent"""
     from . import evaluate as E
     try:
-        actor, avg, bones, recall = E.evaluate_pcp(kept, actor_ground_truth(gts, gts_vis))
+        actor, avg, bones, recall = evaluator.pcp() if evaluator is not None else E.evaluate_pcp(kept, actor_ground_truth(gts, gts_vis))
     except ValueError as e:            # a frame with ground truth in which no prediction passed the classification filter
         return {"error": str(e)}
     return {"actor": [round(100 * float(a), 2) for a in actor], "average": round(100 * float(avg), 2),
@@ -134,7 +159,13 @@ def main(argv=None):
     ap.add_argument("--device-nms", type=int, default=0, choices=[0, 1],
                     help="1: classification filter + NMS as one device operator (ops.pose_nms), inside the HIP graph with --graph 1 "
                          "(one count read-back per frame); 0: evaluate.filter_and_nms (host greedy loop)")
+    ap.add_argument("--device-eval", type=int, default=0, choices=[0, 1],
+                    help="1 (needs --device-nms 1): the kept poses are scored against the ground truth on the device "
+                         "(evaluate.DeviceEvaluator), inside the HIP graph with --graph 1; the frame loop reads nothing back, the "
+                         "metrics once per threshold.  Ground truth is taken as fp32.  0: evaluate.evaluate_panoptic / evaluate_pcp")
     args = ap.parse_args(argv)
+    if args.device_eval and not args.device_nms:
+        ap.error("--device-eval 1 scores the rows of the device NMS: it requires --device-nms 1")
 
     from . import evaluate as E
     cfg = load_config(args.cfg)
@@ -145,7 +176,8 @@ def main(argv=None):
     torch.manual_seed(args.seed)
     head = build_head(cfg, dev, dtype)
     report = {"cfg": args.cfg, "dtype": args.dtype, "num_instance": cfg.DECODER.num_instance,
-              "views": cfg.DATASET.CAMERA_NUM, "layers": cfg.DECODER.num_decoder_layers, "device_nms": bool(args.device_nms)}
+              "views": cfg.DATASET.CAMERA_NUM, "layers": cfg.DECODER.num_decoder_layers, "device_nms": bool(args.device_nms),
+              "device_eval": bool(args.device_eval)}
     if args.model_path:
         missing, ignored = load_checkpoint(head, args.model_path)
         report["checkpoint"] = {"path": args.model_path, "missing_keys": missing[:8], "n_missing": len(missing),
@@ -154,10 +186,24 @@ def main(argv=None):
     results = []
     from . import caller
     from .serving import GraphedDecoder
+    conv = getattr(cfg.DECODER, "convert_joint_format_indices", None)
+    evaluation, gt_dev = None, None
+    if args.device_eval:
+        # which metric the ground truth gets (the rule of the host path below), and every frame's ground truth on the device
+        from . import ops
+        with_gt = [f[2] for f in frames if f[2] is not None]
+        kind = None if not with_gt else "panoptic" if conv is None else \
+            "pcp" if np.asarray(with_gt[0][0]).shape[-2] == len(conv) else None
+        j_out = head.num_joints if conv is None else len(conv)
+        persons, gt_dev = device_ground_truth(frames, kind, j_out, dev)
+        evaluation = dict(kind=kind or "panoptic", capacity=len(frames) * head.num_instance, max_persons=persons, actors=persons)
     for thr in cfg.DECODER.inference_conf_thr:                                   # validate_3d.py:185
         preds, gts, gts_vis, t_dec, n_timed = [], [], [], 0.0, 0
         kept = []
-        runner = None
+        runner, evaluator, nms_out = None, None, None
+        if args.device_eval and not args.graph:
+            evaluator = E.DeviceEvaluator(device=dev, **evaluation)
+            nms_out = ops.pose_nms_buffers(1, head.num_instance, j_out, None, dev)
         for fi, (src, meta, gt) in enumerate(frames):
             src = [s.to(dev) for s in src]
             meta = to_device(meta, dev)
@@ -166,7 +212,8 @@ def main(argv=None):
                 shapes, starts = caller.level_tables(src)
                 runner = GraphedDecoder(head.decoder, meta, shapes, starts, 1, head.num_instance, thr,
                                         postprocess=dict(dist_thr=0.3, num_nearby_joints_thr=7) if args.device_nms else None,
-                                        convert_joint_format_indices=head.convert_joint_format_indices)
+                                        convert_joint_format_indices=head.convert_joint_format_indices, evaluation=evaluation)
+                evaluator = runner.evaluator
                 qpos, tgt = caller.person_joint_queries(head.joint_embedding.weight, head.instance_embedding.weight, 1)
                 ref0 = caller.sample_space_reference_points(head.num_instance, head.space_size, head.space_center, 1, dev,
                                                             t_pose=head.t_pose)
@@ -174,7 +221,7 @@ def main(argv=None):
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             if runner is not None:
-                runner.set_cameras(meta).load(src_views=src)
+                runner.set_cameras(meta).load(src_views=src, ground_truth=gt_dev[fi] if args.device_eval else None)
                 hs, refs, r2d, p2d, cls = runner.replay()
                 if args.device_nms:
                     pred = runner.pred.clone()                                   # static buffer: the next replay overwrites it
@@ -189,7 +236,12 @@ def main(argv=None):
                 t_dec += time.perf_counter() - t0
                 n_timed += 1
             preds.extend(p for p in pred)
-            if args.device_nms and runner is not None:
+            if args.device_eval:
+                if runner is None:                                               # with --graph 1 the replay has done both
+                    with torch.cuda.device(dev):
+                        _, count, dets = ops.pose_nms(pred.contiguous(), 0.3, 7, out=nms_out)
+                    evaluator.update(dets, count, *gt_dev[fi])                   # launches only: nothing is read back per frame
+            elif args.device_nms and runner is not None:
                 dets, count, _ = runner.detections                               # static buffers, filled by the replayed graph
                 kept.extend(dets[b, :k].clone() for b, k in enumerate(count[:, 0].tolist()))   # the frame's one read-back
             elif args.device_nms:
@@ -201,14 +253,15 @@ def main(argv=None):
             kept = [E.filter_and_nms(p) for p in preds]                          # validate_3d.py:228-234 (0.3 m, 7 joints)
         row = {"inference_conf_thr": thr, "frames": len(preds),
                "candidates_above_thr": int(sum(int((p[:, 0, 3] >= 0).sum()) for p in preds)),
-               "poses_after_nms": int(sum(len(k) for k in kept)),
+               "poses_after_nms": evaluator.state()["kept_rows"] if args.device_eval else int(sum(len(k) for k in kept)),
                "decoder_ms_per_frame": round(1e3 * t_dec / max(n_timed, 1), 3),    # host-timed, incl. the camera H2D copy
                "hip_graph": runner is not None}
-        if gts and getattr(cfg.DECODER, "convert_joint_format_indices", None) is not None:
-            if np.asarray(gts[0]).shape[-2] == len(cfg.DECODER.convert_joint_format_indices):
-                row["PCP"] = pcp_report(kept, gts, gts_vis)                       # shelf.py:255-330
+        if gts and conv is not None:
+            if np.asarray(gts[0]).shape[-2] == len(conv):
+                row["PCP"] = pcp_report(kept, gts, gts_vis, evaluator if args.device_eval else None)   # shelf.py:255-330
         elif gts:
-            aps, recs, mpjpe, recall500 = E.evaluate_panoptic(kept, gts, gts_vis)   # panoptic.py:493-574
+            aps, recs, mpjpe, recall500 = evaluator.panoptic() if args.device_eval else \
+                E.evaluate_panoptic(kept, gts, gts_vis)                          # panoptic.py:493-574
             row.update(AP={str(t): round(100 * a, 2) for t, a in zip(E.MPJPE_THRESHOLDS, aps)},
                        recall={str(t): round(100 * r, 2) for t, r in zip(E.MPJPE_THRESHOLDS, recs)},
                        MPJPE=round(float(mpjpe), 2), recall500=round(100 * float(recall500), 2))
