@@ -672,6 +672,65 @@ int mvg_eval_pcp(const float* dets, const int* count, const float* joints_3d, co
                  int R, int J, int Gmax, int actors, double recall_threshold, double alpha, int64_t* correct, int64_t* total,
                  int64_t* bone_correct, int64_t* state, void* stream);
 
+/* ---- person identities across frames behind the NMS (csrc/track.hip) --------------------------------------------------------- */
+#define MVG_LAP_MAX_N 64              /* rows and columns of one assignment problem: one wavefront, a lane per column          */
+#define MVG_LAP_BIG 1e15              /* an entry that is NaN or above this is taken as this                                   */
+#define MVG_TRACK_MAX_D 64            /* detections per stream and frame that take part                                        */
+#define MVG_TRACK_MAX_T 64            /* track slots per stream                                                                */
+#define MVG_TRACK_MAX_J 32
+#define MVG_TRACK_MAX_R 16384         /* rows of dets per batch element                                                        */
+#define MVG_TRACK_MAX_B 4096          /* batch elements (workgroups) of one call, of either function                           */
+#define MVG_TRACK_STATE_WORDS 8       /* int64 state block: frames, matches, births, deaths, overflow, dropped, active,
+                                       * reserved (the arrival counter of a call's workgroups; 0 between calls)                */
+
+/* Minimum-cost assignment of B independent problems in ONE launch, one workgroup of one wavefront per problem, no host
+ * involvement, bit-reproducible.  cost (B, N, M) fp64; n, m (B) int32 live sizes (clamped to [0, N] / [0, M]) or NULL = N, M.
+ *   s = max(n, m); S[i, j] = cost[i, j] for i < n and j < m, 0.0 elsewhere (s x s); an entry that is NaN or > MVG_LAP_BIG is taken
+ *   as MVG_LAP_BIG.  Shortest-augmenting-path Hungarian algorithm with potentials u (rows), v (columns), all 0 at the start, rows
+ *   inserted in order 0 .. s-1.  The search of row i starts at a virtual column whose row is i, with minv[j] = +inf,
+ *   way[j] = virtual, no column used; one step, with j0 the current column and i0 its row:
+ *     1. j0 is marked used;
+ *     2. for every unused column j: cur = (S[i0, j] - u[i0]) - v[j]; if cur < minv[j]: minv[j] = cur, way[j] = j0;
+ *     3. j1 = the unused column of smallest minv, the LOWEST column among equal values, a NaN minv ordered as +inf (so without a
+ *        finite minimum it is the lowest unused column); delta = minv[j1];
+ *     4. u += delta for the rows of the used columns (row i of the virtual column included), v -= delta for the used columns,
+ *        minv -= delta for the unused columns; j0 = j1.
+ *   The search ends when j0 has no row; the path is then flipped along way[] back to the virtual column.  A search is a counted
+ *   loop of at most s steps (step k uses a k-th column and at most i < s columns have a row): no input can make it spin.
+ *   fp64 throughout, every operation rounded on its own.
+ * Outputs: col_of_row (B, N) int32: the column of row r, -1 for r >= n and for a row assigned to a padding column (j >= m);
+ * total (B) fp64: the sum of cost[r, col_of_row[r]] AS GIVEN (not clamped) over the assigned rows, added in row order.
+ * MVG_E_BADARG, and nothing launched, for N or M < 1 or > MVG_LAP_MAX_N, B < 1 or > MVG_TRACK_MAX_B, a NULL cost / col_of_row /
+ * total, a cost or total pointer that is not 8-byte aligned. */
+int mvg_linear_assignment(const double* cost, const int* n, const int* m, int B, int N, int M, int* col_of_row, double* total,
+                          void* stream);
+
+/* One frame of the pose tracker for B independent streams in ONE launch (one workgroup per stream), fixed shapes, nothing read
+ * back, integer atomics on the state block only, bit-reproducible; can be captured in a HIP graph behind mvg_pose_nms.
+ *   dets (B, R, J, 5) fp32 rows [x, y, z, flag, score] and count (B, 2) int32 or NULL as mvg_pose_nms leaves them: row i of
+ *   element b is a detection iff dets[b, i, 0, 3] >= 0 and (count == NULL or i < count[b, 0]).  Detections are taken in row order
+ *   (the NMS keep order); the first MVG_TRACK_MAX_D take part, the others get id -1 and are counted in `dropped`.
+ *   Track state, owned by the caller: id (B, T) int32 (-1 = free slot), hits, misses (B, T) int32, born (B, T) int64 (the frame
+ *   number), score (B, T) fp32, pose (B, T, J, 3) fp32, next_id (B) int32, state (MVG_TRACK_STATE_WORDS) int64.
+ *   Per element: (1) the active tracks are the slots with id >= 0, in slot order.  (2) c[t, d] = (sum over joints in order of
+ *   sqrt((dx*dx + dy*dy) + dz*dz)) / J in fp64 from the fp32 inputs, correctly rounded sqrt.  (3) c'[t, d] = c[t, d] if
+ *   c[t, d] <= max_dist, else max_dist (also for NaN).  (4) the solver of mvg_linear_assignment on c', active tracks as rows,
+ *   detections as columns: every non-match pays max_dist through the zero padding, the matching is the global optimum.  (5) an
+ *   assigned pair is a match iff the ungated c[t, d] <= max_dist.  (6) a matched track takes the detection's pose (bit for bit)
+ *   and score (dets[b, row, 0, 4]), misses = 0, hits += 1.  (7) an unmatched track: misses += 1; if misses > max_misses the slot is
+ *   freed (id = -1) and `deaths` counts it.  (8) the unmatched detections, in detection order, each open a track in the lowest
+ *   free slot (slots freed in (7) included): id = next_id[b]++, hits = 1, misses = 0, born = state[0] as the call found it, pose
+ *   and score of the detection; without a free slot the detection gets no track and `overflow` counts it.
+ *   Outputs, every element written: slots (B, R) int32 = the slot of the row's track, -1 for a row that is no detection or has no
+ *   track; ids (B, R) int32 = the track's id once its hits >= min_hits, else -1.
+ *   State: matches, births, deaths, overflow, dropped += the element's counts, active += births - deaths (the live tracks, given
+ *   that state and id were reset together); frames += 1 per CALL, by the last workgroup to arrive.
+ * MVG_E_BADARG, and nothing launched, for B, R, J or T < 1 or above their MVG_TRACK_MAX_*, max_dist < 0, NaN or > MVG_LAP_BIG,
+ * max_misses or min_hits < 0, a NULL pointer other than count, a born or state pointer that is not 8-byte aligned. */
+int mvg_track_update(const float* dets, const int* count, int B, int R, int J, int T, int* id, int* hits, int* misses, int64_t* born,
+                     float* score, float* pose, int* next_id, int64_t* state, double max_dist, int max_misses, int min_hits,
+                     int* ids, int* slots, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -82,6 +82,8 @@ SIGNATURES = {
     "mvg_pose_nms": [_vp, _i, _i, _i, C.c_double, _i, _i, _vp, C.c_size_t, _vp, _vp, _vp, _i, _vp],
     "mvg_eval_match": [_vp] * 5 + [_i] * 4 + [_vp] * 3 + [C.c_int64, _vp, _vp],
     "mvg_eval_pcp": [_vp] * 5 + [_i] * 5 + [C.c_double] * 2 + [_vp] * 5,
+    "mvg_linear_assignment": [_vp] * 3 + [_i] * 3 + [_vp] * 3,
+    "mvg_track_update": [_vp] * 2 + [_i] * 4 + [_vp] * 8 + [C.c_double, _i, _i] + [_vp] * 3,
 }
 
 _lib = None

@@ -1,0 +1,367 @@
+// Person identities across frames for gfx950: a minimum-cost assignment solver on one wavefront (mvg_linear_assignment) and the
+// tracker update built on it (mvg_track_update), which associates the poses mvg_pose_nms keeps with the tracks of the frames
+// before.  Fixed shapes, nothing read back, no host synchronisation: the update sits behind the NMS in the HIP graph of the
+// decoder forward and the host reads the tracks when it wants them.
+//
+//   mvg_linear_assignment   1 launch, one workgroup of ONE wavefront per batch element: the costs go to LDS, lane j owns column j
+//                           (its potential v, minv, way, used flag and assigned row) and row j (its potential u); the only
+//                           cross-lane operation of a search step is the minimum of minv with its column (DPP moves inside the
+//                           rows of 16 lanes, v_readlane across them, a ballot for the column); wave-uniform lanes are read
+//                           with v_readlane.
+//   mvg_track_update        1 launch, one workgroup (256 threads) per batch element = stream: ordered compaction of the detection
+//                           rows (LDS scan), the active slots (one ballot), the track x detection mean joint distances by all
+//                           threads into LDS, the solve on wavefront 0, then matches / misses / deaths (a lane per track),
+//                           births (thread 0, in detection order), pose copies and the per-row outputs by all threads.
+//
+// The solver is the shortest-augmenting-path Hungarian algorithm with potentials, rows inserted in order, stated so that a host
+// restatement gives the same bits (include/mvg_decoder.h): the per-column operations of a step are independent and are executed
+// unchanged by the column's lane; the minimum is taken under a total order (value, NaN as +inf, then column), so the shape of
+// the reduction does not matter.  Every loop is counted: no input, NaN included, can make a search spin.
+//
+// Arithmetic: fp64 from the fp32 inputs, every multiply and add rounded on its own ((x^2 + y^2) + z^2, correctly rounded sqrt),
+// joints summed in joint order: this file switches contraction off like nms.hip.  The only atomics are integer adds on the state
+// block, whose sums do not depend on the order of the workgroups: two runs give the same bits.
+#include <math.h>
+
+#include "common.h"
+
+#pragma clang fp contract(off)
+
+#define LAP_N MVG_LAP_MAX_N
+#define LAP_VIRT LAP_N                // the virtual column a row's search starts from
+#define TRACK_THREADS 256
+
+static_assert(LAP_N == MVG_WAVE, "a lane per column");
+static_assert(MVG_TRACK_MAX_D == LAP_N && MVG_TRACK_MAX_T == LAP_N, "tracks and detections are the solver's rows and columns");
+
+typedef long long i64;
+typedef unsigned long long u64;
+
+enum { TS_FRAMES = 0, TS_MATCHES = 1, TS_BIRTHS = 2, TS_DEATHS = 3, TS_OVERFLOW = 4, TS_DROPPED = 5, TS_ACTIVE = 6, TS_TICKET = 7 };
+
+struct LapPlain {
+  __device__ __forceinline__ double operator()(double c) const { return c; }
+};
+// the tracker's gate: a pair further apart than max_dist, or with a NaN distance, costs what a non-match costs
+struct LapGate {
+  double max_dist;
+  __device__ __forceinline__ double operator()(double c) const { return c <= max_dist ? c : max_dist; }
+};
+
+// cross-lane moves of a double: two 32-bit halves through the DPP network (within a row of 16 lanes) / v_readlane (from a lane
+// whose index is wave-uniform)
+template <int CTRL>
+static __device__ __forceinline__ double lap_dpp(double v) {
+  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, false);
+  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, false);
+  return __hiloint2double(hi, lo);
+}
+static __device__ __forceinline__ int lap_lane(int v, int from) {
+  return __builtin_amdgcn_readlane(v, __builtin_amdgcn_readfirstlane(from));
+}
+static __device__ __forceinline__ double lap_lane(double v, int from) {
+  const int l = __builtin_amdgcn_readfirstlane(from);
+  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
+}
+static __device__ __forceinline__ double lap_min(double a, double b) { return b < a ? b : a; }
+
+// Executed by ONE whole wavefront in uniform control flow.  s_raw: LDS, row stride LAP_N, entries (i < n, j < m) valid; the square
+// matrix of the solve is S[i, j] = clamp(f(s_raw[i, j])) there and 0 elsewhere, of size s = max(n, m).  s_col[r] (LDS, LAP_N
+// entries) <- the column of row r, -1 for a row that is dead (r >= n) or assigned to a padding column; the caller puts a
+// barrier between this call and its reads of s_col.
+template <class F>
+static __device__ void lap_solve(const double* s_raw, int n, int m, F f, int* s_col, int lane) {
+  const int s = max(n, m);
+  double u = 0.0, v = 0.0;            // potentials of row `lane` and of column `lane`
+  int p = -1;                          // row assigned to column `lane`
+  for (int i = 0; i < s; ++i) {
+    double minv = (double)INFINITY;
+    int way = LAP_VIRT;
+    bool used = false, rowused = false;
+    int j0 = LAP_VIRT, i0 = i;
+    bool found = false;
+    for (int step = 0; step < s; ++step) {        // every step uses one more column and at most i are assigned: <= i + 1 steps
+      if (lane == j0) used = true;
+      if (lane == i0) rowused = true;
+      const double ui0 = lap_lane(u, i0);
+      const bool cand = lane < s && !used;
+      if (cand) {
+        double sv = 0.0;
+        if (i0 < n && lane < m) {
+          sv = f(s_raw[i0 * LAP_N + lane]);
+          if (sv != sv || sv > MVG_LAP_BIG) sv = MVG_LAP_BIG;
+        }
+        const double cur = (sv - ui0) - v;
+        if (cur < minv) {
+          minv = cur;
+          way = j0;
+        }
+      }
+      // minimum of minv over the unused columns, lowest column among equals; NaN ordered as +inf, so that without a finite
+      // minimum the lowest unused column is taken.  The value first (lane ^ 1, lane ^ 2, the mirrors of 8 and 16 lanes, then
+      // the four rows), then the lowest unused lane that holds it.
+      const double key = (cand && minv == minv) ? minv : (double)INFINITY;
+      double kmin = key;
+      kmin = lap_min(kmin, lap_dpp<0xB1>(kmin));
+      kmin = lap_min(kmin, lap_dpp<0x4E>(kmin));
+      kmin = lap_min(kmin, lap_dpp<0x141>(kmin));
+      kmin = lap_min(kmin, lap_dpp<0x140>(kmin));
+      kmin = lap_min(lap_min(lap_lane(kmin, 0), lap_lane(kmin, 16)), lap_min(lap_lane(kmin, 32), lap_lane(kmin, 48)));
+      const u64 holders = __ballot(cand && key == kmin);
+      if (holders == 0) break;                     // not reachable: an unused column exists while the search runs
+      const int j1 = __builtin_ctzll(holders);
+      const double delta = lap_lane(minv, j1);
+      if (rowused) u += delta;
+      if (lane < s) {
+        if (used) v -= delta;
+        else minv -= delta;
+      }
+      j0 = j1;
+      const int pj0 = lap_lane(p, j0);
+      if (pj0 < 0) {
+        found = true;
+        break;
+      }
+      i0 = pj0;
+    }
+    if (!found) continue;                          // not reachable: the counted loop above always ends on a free column
+    for (int k = 0; k <= s; ++k) {                 // flip the path back to the virtual column: <= i + 1 links
+      const int j1 = lap_lane(way, j0);
+      const int pj1 = j1 == LAP_VIRT ? i : lap_lane(p, j1 & (LAP_N - 1));
+      if (lane == j0) p = pj1;
+      j0 = j1;
+      if (j0 == LAP_VIRT) break;
+    }
+  }
+  s_col[lane] = -1;
+  if (p >= 0 && p < n && lane < m) s_col[p] = lane;
+}
+
+static __device__ __forceinline__ int track_clamp(int v, int hi) { return min(max(v, 0), hi); }
+
+// ------------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(LAP_N) void linear_assignment_kernel(const double* __restrict__ cost, const int* __restrict__ n_live,
+                                                                  const int* __restrict__ m_live, int N, int M,
+                                                                  int* __restrict__ col_of_row, double* __restrict__ total) {
+  __shared__ double s_raw[LAP_N * LAP_N];
+  __shared__ int s_col[LAP_N];
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int n = n_live == nullptr ? N : track_clamp(n_live[b], N);
+  const int m = m_live == nullptr ? M : track_clamp(m_live[b], M);
+  const double* c = cost + (size_t)b * N * M;
+  for (int e = lane; e < n * m; e += LAP_N) s_raw[(e / m) * LAP_N + (e % m)] = c[(size_t)(e / m) * M + (e % m)];
+  __syncthreads();
+  lap_solve(s_raw, n, m, LapPlain(), s_col, lane);
+  __syncthreads();
+  if (lane < N) col_of_row[(size_t)b * N + lane] = s_col[lane];
+  if (lane == 0) {
+    double sum = 0.0;                              // the entries of the input as given, in row order
+    for (int r = 0; r < n; ++r)
+      if (s_col[r] >= 0) sum += s_raw[r * LAP_N + s_col[r]];
+    total[b] = sum;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
+static __device__ __forceinline__ bool track_is_det(const float* dets, const int* count, int b, int i, int R, int J, int rows) {
+  return i < rows && dets[((size_t)b * R + i) * J * 5 + 3] >= 0.f;
+}
+static __device__ __forceinline__ double track_dist(const float* p, const float* g) {
+  const double dx = (double)p[0] - (double)g[0], dy = (double)p[1] - (double)g[1], dz = (double)p[2] - (double)g[2];
+  return __builtin_sqrt((dx * dx + dy * dy) + dz * dz);
+}
+
+__global__ __launch_bounds__(TRACK_THREADS) void track_update_kernel(const float* __restrict__ dets, const int* __restrict__ count,
+                                                                     int B, int R, int J, int T, int* __restrict__ id,
+                                                                     int* __restrict__ hits, int* __restrict__ misses,
+                                                                     i64* __restrict__ born, float* __restrict__ score,
+                                                                     float* pose, int* __restrict__ next_id, i64* state,
+                                                                     double max_dist, int max_misses, int min_hits,
+                                                                     int* __restrict__ ids, int* __restrict__ slots) {
+  __shared__ double s_c[LAP_N * LAP_N];        // ungated mean joint distance of (active track a, detection d)
+  __shared__ int s_scan[2][TRACK_THREADS];
+  __shared__ int s_det[LAP_N];                 // row of detection d
+  __shared__ int s_trk[LAP_N];                 // slot of active track a
+  __shared__ int s_col[LAP_N];                 // detection assigned to active track a, or -1
+  __shared__ int s_det_slot[LAP_N];            // slot of the track detection d belongs to after this frame, or -1
+  __shared__ int s_id[LAP_N], s_hits[LAP_N];   // per slot, as they stand after this frame
+  __shared__ int s_na, s_matches, s_deaths, s_births, s_overflow;
+  __shared__ i64 s_frame;
+  const int b = blockIdx.x, t = threadIdx.x;
+  if (t == 0) s_frame = __hip_atomic_load(&state[TS_FRAMES], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+
+  // detections: the rows in front of count[b, 0] whose flag is >= 0, in row order.  Every thread owns a run of consecutive rows,
+  // the run totals go through an LDS scan.
+  const int rows = count == nullptr ? R : track_clamp(count[2 * b], R);
+  const int chunk = (R + TRACK_THREADS - 1) / TRACK_THREADS;
+  const int lo = min(t * chunk, R), hi = min(lo + chunk, R);
+  int mine = 0;
+  for (int i = lo; i < hi; ++i) mine += track_is_det(dets, count, b, i, R, J, rows) ? 1 : 0;
+  s_scan[0][t] = mine;
+  __syncthreads();
+  int src = 0;
+  for (int step = 1; step < TRACK_THREADS; step <<= 1) {
+    s_scan[src ^ 1][t] = s_scan[src][t] + (t >= step ? s_scan[src][t - step] : 0);
+    src ^= 1;
+    __syncthreads();
+  }
+  const int first = s_scan[src][t] - mine;     // detections in front of this thread's run
+  const int nd_all = s_scan[src][TRACK_THREADS - 1];
+  const int nd = min(nd_all, MVG_TRACK_MAX_D);
+  {
+    int pos = first;
+    for (int i = lo; i < hi && pos < MVG_TRACK_MAX_D; ++i)
+      if (track_is_det(dets, count, b, i, R, J, rows)) s_det[pos++] = i;
+  }
+  // active tracks: the slots with id >= 0, in slot order
+  if (t < LAP_N) {
+    const int tid = t < T ? id[(size_t)b * T + t] : -1;
+    const u64 mask = __ballot(tid >= 0);
+    if (tid >= 0) s_trk[__popcll(mask & ((1ull << t) - 1ull))] = t;
+    s_id[t] = tid;
+    s_hits[t] = t < T ? hits[(size_t)b * T + t] : 0;
+    s_det_slot[t] = -1;
+    if (t == 0) s_na = __popcll(mask);
+  }
+  __syncthreads();
+  const int na = s_na;
+
+  for (int e = t; e < na * nd; e += TRACK_THREADS) {
+    const int a = e / nd, d = e % nd;
+    const float* p = pose + ((size_t)b * T + s_trk[a]) * J * 3;
+    const float* g = dets + ((size_t)b * R + s_det[d]) * J * 5;
+    double sum = 0.0;
+    for (int j = 0; j < J; ++j) sum += track_dist(p + j * 3, g + j * 5);
+    s_c[a * LAP_N + d] = sum / (double)J;
+  }
+  __syncthreads();
+  if (t < LAP_N) lap_solve(s_c, na, nd, LapGate{max_dist}, s_col, t);      // wavefront 0
+  __syncthreads();
+
+  // matched tracks take the detection; the others age and die
+  if (t < LAP_N) {
+    bool matched = false, died = false;
+    if (t < na) {
+      const int slot = s_trk[t], d = s_col[t];
+      const size_t at = (size_t)b * T + slot;
+      matched = d >= 0 && s_c[t * LAP_N + d] <= max_dist;               // the ungated cost: NaN is no match
+      if (matched) {
+        s_det_slot[d] = slot;
+        misses[at] = 0;
+        hits[at] = s_hits[slot] + 1;
+        s_hits[slot] += 1;
+      } else {
+        const int ms = misses[at] + 1;
+        misses[at] = ms;
+        died = ms > max_misses;
+        if (died) {
+          id[at] = -1;
+          s_id[slot] = -1;
+        }
+      }
+    }
+    const u64 m_mask = __ballot(matched), d_mask = __ballot(died);
+    if (t == 0) {
+      s_matches = __popcll(m_mask);
+      s_deaths = __popcll(d_mask);
+    }
+  }
+  __syncthreads();
+  // unmatched detections open tracks in detection order, each in the lowest free slot (those freed above included)
+  if (t == 0) {
+    u64 free_slots = 0;
+    for (int k = 0; k < T; ++k)
+      if (s_id[k] < 0) free_slots |= 1ull << k;
+    int nid = next_id[b], births = 0, overflow = 0;
+    for (int d = 0; d < nd; ++d) {
+      if (s_det_slot[d] >= 0) continue;
+      if (free_slots == 0) {
+        ++overflow;
+        continue;
+      }
+      const int slot = __builtin_ctzll(free_slots);
+      free_slots &= free_slots - 1;
+      const size_t at = (size_t)b * T + slot;
+      s_det_slot[d] = slot;
+      s_id[slot] = nid;
+      s_hits[slot] = 1;
+      id[at] = nid++;
+      hits[at] = 1;
+      misses[at] = 0;
+      born[at] = s_frame;
+      ++births;
+    }
+    next_id[b] = nid;
+    s_births = births;
+    s_overflow = overflow;
+  }
+  __syncthreads();
+  // the pose (bit for bit) and the score of every detection that has a track now
+  for (int e = t; e < nd * J * 3; e += TRACK_THREADS) {
+    const int d = e / (J * 3), k = e % (J * 3);
+    const int slot = s_det_slot[d];
+    if (slot >= 0) pose[((size_t)b * T + slot) * J * 3 + k] = dets[((size_t)b * R + s_det[d]) * J * 5 + (k / 3) * 5 + (k % 3)];
+  }
+  if (t < nd && s_det_slot[t] >= 0) score[(size_t)b * T + s_det_slot[t]] = dets[((size_t)b * R + s_det[t]) * J * 5 + 4];
+  // per row: the slot, and the id once the track has min_hits hits
+  {
+    int pos = first;
+    for (int i = lo; i < hi; ++i) {
+      int slot = -1, tid = -1;
+      if (track_is_det(dets, count, b, i, R, J, rows)) {
+        if (pos < MVG_TRACK_MAX_D) {
+          slot = s_det_slot[pos];
+          if (slot >= 0 && s_hits[slot] >= min_hits) tid = s_id[slot];
+        }
+        ++pos;
+      }
+      ids[(size_t)b * R + i] = tid;
+      slots[(size_t)b * R + i] = slot;
+    }
+  }
+  // the state block: integer sums over the elements, then the last element of the call to arrive advances the frame counter
+  // (every element has read it by then: thread 0 loaded it before anything else and has used it since)
+  if (t == 0) {
+    u64* st = (u64*)state;
+    if (s_matches) atomicAdd(&st[TS_MATCHES], (u64)s_matches);
+    if (s_births) atomicAdd(&st[TS_BIRTHS], (u64)s_births);
+    if (s_deaths) atomicAdd(&st[TS_DEATHS], (u64)s_deaths);
+    if (s_overflow) atomicAdd(&st[TS_OVERFLOW], (u64)s_overflow);
+    if (nd_all > nd) atomicAdd(&st[TS_DROPPED], (u64)(nd_all - nd));
+    if (s_births != s_deaths) atomicAdd(&st[TS_ACTIVE], (u64)(i64)(s_births - s_deaths));
+    __threadfence();
+    if (atomicAdd(&st[TS_TICKET], 1ull) == (u64)(B - 1)) {
+      atomicExch(&st[TS_TICKET], 0ull);
+      atomicAdd(&st[TS_FRAMES], 1ull);
+    }
+  }
+}
+
+extern "C" {
+
+int mvg_linear_assignment(const double* cost, const int* n, const int* m, int B, int N, int M, int* col_of_row, double* total,
+                          void* stream) {
+  if (B < 1 || B > MVG_TRACK_MAX_B || N < 1 || N > MVG_LAP_MAX_N || M < 1 || M > MVG_LAP_MAX_N) return MVG_E_BADARG;
+  if (cost == nullptr || col_of_row == nullptr || total == nullptr) return MVG_E_BADARG;
+  if (((uintptr_t)cost & 7) || ((uintptr_t)total & 7)) return MVG_E_BADARG;
+  hipLaunchKernelGGL(linear_assignment_kernel, dim3(B), dim3(LAP_N), 0, (hipStream_t)stream, cost, n, m, N, M, col_of_row, total);
+  MVG_LAUNCH_CHECK();
+  return 0;
+}
+
+int mvg_track_update(const float* dets, const int* count, int B, int R, int J, int T, int* id, int* hits, int* misses, int64_t* born,
+                     float* score, float* pose, int* next_id, int64_t* state, double max_dist, int max_misses, int min_hits,
+                     int* ids, int* slots, void* stream) {
+  if (B < 1 || B > MVG_TRACK_MAX_B || R < 1 || R > MVG_TRACK_MAX_R || J < 1 || J > MVG_TRACK_MAX_J || T < 1 || T > MVG_TRACK_MAX_T)
+    return MVG_E_BADARG;
+  if (!(max_dist >= 0.0) || max_dist > MVG_LAP_BIG || max_misses < 0 || min_hits < 0) return MVG_E_BADARG;
+  if (dets == nullptr || id == nullptr || hits == nullptr || misses == nullptr || born == nullptr || score == nullptr) return MVG_E_BADARG;
+  if (pose == nullptr || next_id == nullptr || state == nullptr || ids == nullptr || slots == nullptr) return MVG_E_BADARG;
+  if (((uintptr_t)born & 7) || ((uintptr_t)state & 7)) return MVG_E_BADARG;
+  hipLaunchKernelGGL(track_update_kernel, dim3(B), dim3(TRACK_THREADS), 0, (hipStream_t)stream, dets, count, B, R, J, T, id, hits,
+                     misses, (i64*)born, score, pose, next_id, (i64*)state, max_dist, max_misses, min_hits, ids, slots);
+  MVG_LAUNCH_CHECK();
+  return 0;
+}
+
+}  // extern "C"

@@ -1335,3 +1335,92 @@ def eval_pcp(dets, count, joints_3d, joints_3d_vis, num_person, buffers, recall_
         L.check(lib.mvg_eval_pcp(L.ptr(dets), L.ptr(count), L.ptr(joints_3d), L.ptr(joints_3d_vis), L.ptr(num_person), B, R, J, G, A,
                                  float(recall_threshold), float(alpha), L.ptr(correct), L.ptr(total), L.ptr(bones), L.ptr(state),
                                  L.stream_ptr()), "mvg_eval_pcp")
+
+
+LAP_MAX_N = 64                     # MVG_LAP_MAX_N
+LAP_BIG = 1e15                     # MVG_LAP_BIG
+TRACK_MAX_D, TRACK_MAX_T, TRACK_MAX_J, TRACK_MAX_R, TRACK_MAX_B = 64, 64, 32, 16384, 4096      # MVG_TRACK_MAX_*
+TRACK_STATE = ("frames", "matches", "births", "deaths", "overflow", "dropped", "active", "reserved")
+_TRACK_KEYS = (("id", torch.int32), ("hits", torch.int32), ("misses", torch.int32), ("born", torch.int64), ("score", torch.float32),
+               ("pose", torch.float32), ("next_id", torch.int32), ("state", torch.int64), ("ids", torch.int32), ("slots", torch.int32))
+
+
+def linear_assignment(cost, n=None, m=None):
+    """Minimum-cost assignment on the device (mvg_linear_assignment: one launch, one wavefront per problem, nothing read back).
+    cost (B, N, M) fp64 contiguous with N, M <= LAP_MAX_N; n, m (B) int32 live sizes or None (= N, M): the problem of element b is
+    cost[b, :n[b], :m[b]], padded with zeros to a square.  An entry that is NaN or above LAP_BIG counts as LAP_BIG.
+    -> col_of_row (B, N) int32 (-1: dead row, or a row left unassigned because n > m) and total (B) fp64, the assigned entries of
+    the input added in row order.  Shortest augmenting paths with potentials, rows in order, lowest column among equal minima:
+    the rule of include/mvg_decoder.h, which a host restatement reproduces bit for bit."""
+    L.require_cuda(cost, n, m)
+    if cost.dim() != 3 or cost.dtype != torch.float64:
+        raise RuntimeError("mvg_linear_assignment: cost (B, N, M) float64 expected")
+    B, N, M = cost.shape
+    for name, t in (("n", n), ("m", m)):
+        if t is not None and (t.dtype != torch.int32 or tuple(t.shape) != (B,)):
+            raise RuntimeError("mvg_linear_assignment: %s (B) int32 or None expected" % name)
+    if not all(t is None or t.is_contiguous() for t in (cost, n, m)):
+        raise RuntimeError("mvg_linear_assignment: every tensor must be contiguous")
+    if not (1 <= B <= TRACK_MAX_B and 1 <= N <= LAP_MAX_N and 1 <= M <= LAP_MAX_N):
+        raise L.MvgError("mvg_linear_assignment: unsupported shape B = %d (<= %d), N = %d, M = %d (<= %d)"
+                         % (B, TRACK_MAX_B, N, M, LAP_MAX_N))
+    col = torch.empty((B, N), dtype=torch.int32, device=cost.device)
+    total = torch.empty((B,), dtype=torch.float64, device=cost.device)
+    lib = L.load()
+    with _timed("linear_assignment"):
+        L.check(lib.mvg_linear_assignment(L.ptr(cost), L.ptr(n), L.ptr(m), B, N, M, L.ptr(col), L.ptr(total), L.stream_ptr()),
+                "mvg_linear_assignment")
+    return col, total
+
+
+def track_buffers(B, T, J, R, device="cuda"):
+    """the state of track_update for B streams of T slots and J joints -- id (B, T) int32 filled with -1 (free), hits, misses
+    (B, T) int32, born (B, T) int64, score (B, T) fp32, pose (B, T, J, 3) fp32, next_id (B) int32 and the int64 state block
+    (TRACK_STATE) -- plus the static outputs ids, slots (B, R) int32 (-1).  Allocated once and kept alive by the caller: a captured
+    HIP graph addresses them by pointer, like pose_nms_buffers."""
+    B, T, J, R = int(B), int(T), int(J), int(R)
+    if not (1 <= B <= TRACK_MAX_B and 1 <= T <= TRACK_MAX_T and 1 <= J <= TRACK_MAX_J and 1 <= R <= TRACK_MAX_R):
+        raise L.MvgError("track_buffers: unsupported shape B = %d (<= %d), T = %d (<= %d), J = %d (<= %d), R = %d (<= %d)"
+                         % (B, TRACK_MAX_B, T, TRACK_MAX_T, J, TRACK_MAX_J, R, TRACK_MAX_R))
+    shapes = dict(id=(B, T), hits=(B, T), misses=(B, T), born=(B, T), score=(B, T), pose=(B, T, J, 3), next_id=(B,),
+                  state=(len(TRACK_STATE),), ids=(B, R), slots=(B, R))
+    out = {k: torch.zeros(shapes[k], dtype=dt, device=device) for k, dt in _TRACK_KEYS}
+    for k in ("id", "ids", "slots"):
+        out[k].fill_(-1)
+    return out
+
+
+def track_update(dets, count, buffers, max_dist=500.0, max_misses=10, min_hits=1):
+    """One frame of the pose tracker on the device (mvg_track_update: one launch, nothing read back, no synchronisation).  dets
+    (B, R, J, 5) fp32 and count (B, 2) int32 or None as pose_nms leaves them; ``buffers`` from track_buffers.  The detections (row
+    order, the first TRACK_MAX_D) are assigned to the live tracks at the minimum total mean joint distance, a pair further apart
+    than max_dist (the unit of the poses) costing max_dist like a non-match; matched tracks take the detection, the others age and
+    are freed after more than max_misses misses, unmatched detections open tracks in the lowest free slots.  -> (ids, slots), the
+    (B, R) int32 tensors of ``buffers``: per row the track's id (once it has min_hits hits) and slot, else -1."""
+    tensors = [buffers[k] for k, _ in _TRACK_KEYS]
+    L.require_cuda(dets, count, *tensors)
+    if dets.dim() != 4 or dets.shape[-1] != 5 or dets.dtype != torch.float32:
+        raise RuntimeError("mvg_track_update: dets (B, R, J, 5) float32 expected")
+    B, R, J = dets.shape[:3]
+    if count is not None and (count.dtype != torch.int32 or tuple(count.shape) != (B, 2)):
+        raise RuntimeError("mvg_track_update: count (B, 2) int32 or None expected")
+    if not all(t is None or t.is_contiguous() for t in (dets, count, *tensors)):
+        raise RuntimeError("mvg_track_update: every tensor must be contiguous")
+    ident = buffers["id"]
+    T = ident.shape[1] if ident.dim() == 2 else 0
+    shapes = dict(id=(B, T), hits=(B, T), misses=(B, T), born=(B, T), score=(B, T), pose=(B, T, J, 3), next_id=(B,),
+                  state=(len(TRACK_STATE),), ids=(B, R), slots=(B, R))
+    if any(t.dtype != dt or tuple(t.shape) != shapes[k] for (k, dt), t in zip(_TRACK_KEYS, tensors)):
+        raise RuntimeError("mvg_track_update: buffers are not those of track_buffers for dets %s" % (tuple(dets.shape),))
+    if not (1 <= B <= TRACK_MAX_B and 1 <= T <= TRACK_MAX_T and 1 <= J <= TRACK_MAX_J and 1 <= R <= TRACK_MAX_R):
+        raise L.MvgError("mvg_track_update: unsupported shape B = %d (<= %d), T = %d (<= %d), J = %d (<= %d), R = %d (<= %d)"
+                         % (B, TRACK_MAX_B, T, TRACK_MAX_T, J, TRACK_MAX_J, R, TRACK_MAX_R))
+    if not (0.0 <= float(max_dist) <= LAP_BIG) or int(max_misses) < 0 or int(min_hits) < 0:
+        raise L.MvgError("mvg_track_update: 0 <= max_dist <= %g, max_misses >= 0 and min_hits >= 0 expected (got %r, %r, %r)"
+                         % (LAP_BIG, max_dist, max_misses, min_hits))
+    lib = L.load()
+    with _timed("track_update"):
+        L.check(lib.mvg_track_update(L.ptr(dets), L.ptr(count), B, R, J, T, *(L.ptr(t) for t in tensors[:8]), float(max_dist),
+                                     int(max_misses), int(min_hits), L.ptr(buffers["ids"]), L.ptr(buffers["slots"]),
+                                     L.stream_ptr()), "mvg_track_update")
+    return buffers["ids"], buffers["slots"]

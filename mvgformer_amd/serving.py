@@ -36,6 +36,12 @@ order, ``count[b] = [kept, skipped]`` and the kept row indices -- static tensors
 (``load(ground_truth=(joints_3d, joints_3d_vis, num_person))``): the kept poses of every replayed frame are scored on the device
 and accumulated in ``runner.evaluator``; nothing is read back per frame, the metrics once (``runner.evaluator.panoptic()`` /
 ``.pcp()``).  The warm-up forwards of a capture leave the accumulators as they were.
+
+``tracking=dict(max_tracks=32, max_dist=500.0, max_misses=10, min_hits=1)`` (requires ``postprocess``) continues behind the NMS
+(and behind the evaluator, if there is one; neither reads the other's output) with ``tracking.PoseTracker.update``, one more
+launch: every replay associates the kept poses with the tracks of the frames before.  ``runner.track_ids`` = ``(ids, slots)``,
+(B, dets_rows) int32 per row of ``runner.detections[0]``, static and overwritten by the next replay; ``runner.tracker`` holds the
+state (``.tracks()``, ``.state()``, ``.reset()``).  The warm-up forwards of a capture leave the tracks as they were.
 """
 from __future__ import annotations
 
@@ -46,7 +52,8 @@ from .decoder import DecoderContext
 
 class GraphedDecoder:
     def __init__(self, decoder, meta, spatial_shapes, level_start_index, batch, num_queries, threshold=0.1, device=None,
-                 producer_writes_in_place=False, channels=256, postprocess=None, convert_joint_format_indices=None, evaluation=None):
+                 producer_writes_in_place=False, channels=256, postprocess=None, convert_joint_format_indices=None, evaluation=None,
+                 tracking=None):
         layer0 = decoder.layers[0]
         dev = torch.device(device) if device is not None else next(decoder.parameters()).device
         if dev.type != "cuda":
@@ -103,6 +110,18 @@ class GraphedDecoder:
                 raise TypeError("GraphedDecoder: unknown evaluation keys %s" % sorted(unknown))
             self.evaluator = DeviceEvaluator(device=dev, **evaluation)
             self.ground_truth = self.evaluator.ground_truth_buffers(batch, self._nms["dets"].shape[2])
+        # optional person identities across the replayed frames behind the NMS, inside the same graph
+        self.tracker, self.track_ids = None, None
+        if tracking is not None:
+            from .tracking import PoseTracker
+            if postprocess is None:
+                raise ValueError("GraphedDecoder: tracking follows the rows the NMS keeps; it requires postprocess")
+            unknown = set(tracking) - {"max_tracks", "max_dist", "max_misses", "min_hits"}
+            if unknown:
+                raise TypeError("GraphedDecoder: unknown tracking keys %s" % sorted(unknown))
+            dets = self._nms["dets"]
+            self.tracker = PoseTracker(batch=batch, rows=dets.shape[1], num_joints=dets.shape[2], device=dev, **tracking)
+            self.track_ids = (self.tracker.buffers["ids"], self.tracker.buffers["slots"])
 
     # ------------------------------------------------------------------ inputs (device-side copies on the current stream)
     def load(self, src_views=None, tgt=None, query_pos=None, reference_points=None, ground_truth=None):
@@ -152,17 +171,22 @@ class GraphedDecoder:
             ops.pose_nms(self.pred, pp["dist_thr"], pp["num_nearby_joints_thr"], pp["max_dets"], pp["dets_rows"], out=self._nms)
             if self.evaluator is not None:
                 self.evaluator.update(self._nms["dets"], self._nms["count"], *self.ground_truth)
+            if self.tracker is not None:
+                self.tracker.update(self._nms["dets"], self._nms["count"])
         return outputs
 
     def capture(self, warmup=2):
         with torch.no_grad():
             # the warm-up forwards score whatever is loaded: the accumulators are put back, so a (re-)capture counts no frame
             saved = None if self.evaluator is None else {k: t.clone() for k, t in self.evaluator.buffers.items()}
+            tracks = None if self.tracker is None else self.tracker.snapshot()      # nor do they age or create tracks
             for _ in range(max(1, warmup)):         # builds the weight caches, sizes the per-layer buffers
                 self._forward()
             if saved is not None:
                 for k, t in self.evaluator.buffers.items():
                     t.copy_(saved[k])
+            if tracks is not None:
+                self.tracker.restore(tracks)
             torch.cuda.synchronize(self.dev)
             self.graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.graph):
@@ -183,6 +207,8 @@ class GraphedDecoder:
             keep += list(self._nms.values())
         if self.evaluator is not None:
             keep += list(self.evaluator.buffers.values()) + list(self.ground_truth)
+        if self.tracker is not None:
+            keep += list(self.tracker.buffers.values())
         for l in self.dec.layers:
             keep += [l.proj_attn._vp, l.proj_attn._G]
             for wc in (l._wc, l.proj_attn._wc):
@@ -207,6 +233,6 @@ class GraphedDecoder:
     def eager(self):
         """the same forward without the graph (reference for tests; identical results).  With ``postprocess`` it takes the same
         path as the capture: ``pred`` is this call's packed predictions, ``detections`` the same static buffers, and with
-        ``evaluation`` the frame is scored into ``evaluator`` like a replayed one."""
+        ``evaluation`` the frame is scored into ``evaluator`` like a replayed one, with ``tracking`` it updates ``tracker``."""
         with torch.no_grad():
             return self._forward()

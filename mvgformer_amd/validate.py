@@ -15,7 +15,9 @@ geometry (``mvgformer_amd.synthetic``).  ``--cfg extract:<relative path>`` reads
 
 ``--device-nms 1`` runs the classification filter and the NMS on the device (inside the HIP graph with ``--graph 1``);
 ``--device-eval 1`` on top of it scores the kept poses against the ground truth there as well (``evaluate.DeviceEvaluator``): the
-frame loop then reads nothing back and the metrics are fetched once per threshold.
+frame loop then reads nothing back and the metrics are fetched once per threshold.  ``--device-track 1``, also on top of
+``--device-nms 1``, follows the kept poses across the frames with a ``tracking.PoseTracker`` (inside the HIP graph with
+``--graph 1``) and reports the tracker's counters per threshold.
 """
 from __future__ import annotations
 
@@ -163,9 +165,15 @@ def main(argv=None):
                     help="1 (needs --device-nms 1): the kept poses are scored against the ground truth on the device "
                          "(evaluate.DeviceEvaluator), inside the HIP graph with --graph 1; the frame loop reads nothing back, the "
                          "metrics once per threshold.  Ground truth is taken as fp32.  0: evaluate.evaluate_panoptic / evaluate_pcp")
+    ap.add_argument("--device-track", type=int, default=0, choices=[0, 1],
+                    help="1 (needs --device-nms 1): the kept poses get person identities across the frames on the device "
+                         "(tracking.PoseTracker, one launch per frame, inside the HIP graph with --graph 1); a fresh tracker per "
+                         "inference_conf_thr, its counters in the report")
     args = ap.parse_args(argv)
     if args.device_eval and not args.device_nms:
         ap.error("--device-eval 1 scores the rows of the device NMS: it requires --device-nms 1")
+    if args.device_track and not args.device_nms:
+        ap.error("--device-track 1 follows the rows of the device NMS: it requires --device-nms 1")
 
     from . import evaluate as E
     cfg = load_config(args.cfg)
@@ -177,7 +185,7 @@ def main(argv=None):
     head = build_head(cfg, dev, dtype)
     report = {"cfg": args.cfg, "dtype": args.dtype, "num_instance": cfg.DECODER.num_instance,
               "views": cfg.DATASET.CAMERA_NUM, "layers": cfg.DECODER.num_decoder_layers, "device_nms": bool(args.device_nms),
-              "device_eval": bool(args.device_eval)}
+              "device_eval": bool(args.device_eval), "device_track": bool(args.device_track)}
     if args.model_path:
         missing, ignored = load_checkpoint(head, args.model_path)
         report["checkpoint"] = {"path": args.model_path, "missing_keys": missing[:8], "n_missing": len(missing),
@@ -188,22 +196,27 @@ def main(argv=None):
     from .serving import GraphedDecoder
     conv = getattr(cfg.DECODER, "convert_joint_format_indices", None)
     evaluation, gt_dev = None, None
+    from . import ops
+    j_out = head.num_joints if conv is None else len(conv)
+    tracking = dict(max_tracks=32, max_dist=500.0, max_misses=10, min_hits=1) if args.device_track else None
     if args.device_eval:
         # which metric the ground truth gets (the rule of the host path below), and every frame's ground truth on the device
-        from . import ops
         with_gt = [f[2] for f in frames if f[2] is not None]
         kind = None if not with_gt else "panoptic" if conv is None else \
             "pcp" if np.asarray(with_gt[0][0]).shape[-2] == len(conv) else None
-        j_out = head.num_joints if conv is None else len(conv)
         persons, gt_dev = device_ground_truth(frames, kind, j_out, dev)
         evaluation = dict(kind=kind or "panoptic", capacity=len(frames) * head.num_instance, max_persons=persons, actors=persons)
     for thr in cfg.DECODER.inference_conf_thr:                                   # validate_3d.py:185
         preds, gts, gts_vis, t_dec, n_timed = [], [], [], 0.0, 0
         kept = []
-        runner, evaluator, nms_out = None, None, None
-        if args.device_eval and not args.graph:
-            evaluator = E.DeviceEvaluator(device=dev, **evaluation)
+        runner, evaluator, nms_out, tracker = None, None, None, None
+        if (args.device_eval or args.device_track) and not args.graph:
             nms_out = ops.pose_nms_buffers(1, head.num_instance, j_out, None, dev)
+            if args.device_eval:
+                evaluator = E.DeviceEvaluator(device=dev, **evaluation)
+            if args.device_track:                                                # a fresh tracker per threshold pass
+                from .tracking import PoseTracker
+                tracker = PoseTracker(batch=1, rows=head.num_instance, num_joints=j_out, device=dev, **tracking)
         for fi, (src, meta, gt) in enumerate(frames):
             src = [s.to(dev) for s in src]
             meta = to_device(meta, dev)
@@ -212,8 +225,9 @@ def main(argv=None):
                 shapes, starts = caller.level_tables(src)
                 runner = GraphedDecoder(head.decoder, meta, shapes, starts, 1, head.num_instance, thr,
                                         postprocess=dict(dist_thr=0.3, num_nearby_joints_thr=7) if args.device_nms else None,
-                                        convert_joint_format_indices=head.convert_joint_format_indices, evaluation=evaluation)
-                evaluator = runner.evaluator
+                                        convert_joint_format_indices=head.convert_joint_format_indices, evaluation=evaluation,
+                                        tracking=tracking)
+                evaluator, tracker = runner.evaluator, runner.tracker
                 qpos, tgt = caller.person_joint_queries(head.joint_embedding.weight, head.instance_embedding.weight, 1)
                 ref0 = caller.sample_space_reference_points(head.num_instance, head.space_size, head.space_center, 1, dev,
                                                             t_pose=head.t_pose)
@@ -236,11 +250,15 @@ def main(argv=None):
                 t_dec += time.perf_counter() - t0
                 n_timed += 1
             preds.extend(p for p in pred)
-            if args.device_eval:
-                if runner is None:                                               # with --graph 1 the replay has done both
-                    with torch.cuda.device(dev):
-                        _, count, dets = ops.pose_nms(pred.contiguous(), 0.3, 7, out=nms_out)
+            if (args.device_eval or args.device_track) and runner is None:       # with --graph 1 the replay has done it all
+                with torch.cuda.device(dev):
+                    _, count, dets = ops.pose_nms(pred.contiguous(), 0.3, 7, out=nms_out)
+                if args.device_eval:
                     evaluator.update(dets, count, *gt_dev[fi])                   # launches only: nothing is read back per frame
+                if args.device_track:
+                    tracker.update(dets, count)
+            if args.device_eval:
+                pass
             elif args.device_nms and runner is not None:
                 dets, count, _ = runner.detections                               # static buffers, filled by the replayed graph
                 kept.extend(dets[b, :k].clone() for b, k in enumerate(count[:, 0].tolist()))   # the frame's one read-back
@@ -256,6 +274,9 @@ def main(argv=None):
                "poses_after_nms": evaluator.state()["kept_rows"] if args.device_eval else int(sum(len(k) for k in kept)),
                "decoder_ms_per_frame": round(1e3 * t_dec / max(n_timed, 1), 3),    # host-timed, incl. the camera H2D copy
                "hip_graph": runner is not None}
+        if tracker is not None:
+            st = tracker.state()
+            row["tracks"] = {k: st[k] for k in ("births", "deaths", "overflow", "dropped", "active")}
         if gts and conv is not None:
             if np.asarray(gts[0]).shape[-2] == len(conv):
                 row["PCP"] = pcp_report(kept, gts, gts_vis, evaluator if args.device_eval else None)   # shelf.py:255-330

@@ -1,0 +1,145 @@
+"""Cost of person tracking on the device (tracking.PoseTracker, csrc/track.hip) at the cfg-2 serving shapes (R = 1024, J = 15,
+max_tracks = 32).
+
+  1. PoseTracker.update with 4, 10 and 64 detections in steady state (every track is matched in every frame: two detection sets
+     20 mm apart alternate, so the solver has real costs to work on; with 64 detections and 32 slots the other 32 overflow, and
+     one more line gives 64 detections on 64 slots, the largest solve), device time between events around the call: eager, and
+     as a replay of a HIP graph that holds only the update.  ops.linear_assignment on one random 64 x 64 problem next to it.
+  2. cfg-2 decoder (bf16, ~10 % valid queries) as serving.GraphedDecoder with postprocess, with and without tracking=, alternating
+     in one process: host wall time of replay + synchronise per frame, medians after warm-up.  The runner without tracking is the
+     behaviour without this feature.
+
+    python tools/bench_track.py [--reps 200] [--warmup 20] [--out profiles/track_device.txt]
+"""
+import argparse
+import json
+import statistics
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, __import__("os").path.dirname(__import__("os").path.dirname(__import__("os").path.abspath(__file__))))
+
+DEV = "cuda:0"
+LINES = []
+R, J = 1024, 15
+
+
+def say(text):
+    print(text)
+    LINES.append(text)
+
+
+def _stats(xs):
+    return "median %8.3f ms  min %8.3f  max %8.3f" % (statistics.median(xs), min(xs), max(xs))
+
+
+def _detections(n, seed=0):
+    """two frames of n persons 2 m apart on a grid, the second moved by 20 mm and re-noised -> (dets (2, 1, R, J, 5), count)"""
+    rng = np.random.default_rng(seed)
+    skel = rng.uniform(-300.0, 300.0, size=(n, J, 3))
+    centre = np.array([[2000.0 * (k % 8), 2000.0 * (k // 8), 900.0] for k in range(n)])[:, None, :]
+    dets = np.zeros((2, 1, R, J, 5), np.float32)
+    dets[..., 3] = -1.0
+    for f in range(2):
+        dets[f, 0, :n, :, :3] = centre + 20.0 * f + skel + rng.normal(scale=5.0, size=(n, J, 3))
+        dets[f, 0, :n, :, 3] = 0.0
+        dets[f, 0, :n, :, 4] = np.linspace(0.9, 0.3, n)[:, None]
+    return torch.from_numpy(dets).to(DEV), torch.tensor([[n, 0]], dtype=torch.int32, device=DEV)
+
+
+def _timed(fn, before, reps, warm):
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    ms = []
+    for i in range(warm + reps):
+        before(i)
+        torch.cuda.synchronize()
+        ev[0].record()
+        fn()
+        ev[1].record()
+        torch.cuda.synchronize()
+        if i >= warm:
+            ms.append(ev[0].elapsed_time(ev[1]))
+    return ms
+
+
+def updates(reps, warm):
+    from mvgformer_amd import ops
+    from mvgformer_amd.tracking import PoseTracker
+    out = {}
+    for n, slots in ((4, 32), (10, 32), (64, 32), (64, 64)):
+        frames, count = _detections(n)
+        dets = frames[0].clone()
+        tracker = PoseTracker(batch=1, rows=R, num_joints=J, max_tracks=slots, device=DEV)
+        feed = lambda i: dets.copy_(frames[i % 2])                                   # noqa: E731
+        eager = _timed(lambda: tracker.update(dets, count), feed, reps, warm)
+        st = tracker.state()
+        assert st["births"] == min(n, slots) and st["deaths"] == 0 and st["matches"] == min(n, slots) * (warm + reps - 1), st
+        tracker.reset()
+        torch.cuda.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            tracker.update(dets, count)
+        replay = _timed(graph.replay, feed, reps, warm)
+        st = tracker.state()
+        assert st["births"] == min(n, slots) and st["matches"] == min(n, slots) * (warm + reps - 1), st
+        say("    PoseTracker.update (1, %d, %d), %2d slots, %2d detections  eager   %s" % (R, J, slots, n, _stats(eager)))
+        say("                                                            replay  %s  (%d reps)" % (_stats(replay), len(replay)))
+        out["update_ms_eager_%d_of_%d" % (n, slots)] = statistics.median(eager)
+        out["update_ms_replay_%d_of_%d" % (n, slots)] = statistics.median(replay)
+    cost = torch.from_numpy(np.random.default_rng(1).uniform(0.0, 1000.0, size=(1, 64, 64))).to(DEV)
+    ms = _timed(lambda: ops.linear_assignment(cost), lambda i: None, reps, warm)
+    say("    ops.linear_assignment (1, 64, 64) random costs, eager (two output allocations included)  %s" % _stats(ms))
+    out["linear_assignment_ms_64"] = statistics.median(ms)
+    return out
+
+
+def frames(reps, warm):
+    from mvgformer_amd.factory import build_decoder_for_case, case_to_device
+    from mvgformer_amd.serving import GraphedDecoder
+    from mvgformer_amd.synthetic import build_case
+    c = case_to_device(build_case("cfg2", seed=0, valid_fraction=0.1), DEV)
+    dec = build_decoder_for_case(c, DEV, dtype=torch.bfloat16)
+    pp = dict(dist_thr=0.3, num_nearby_joints_thr=7)
+    args = (dec, c.meta, c.spatial_shapes, c.level_start_index, 1, c.NQ, 0.1)
+    plain = GraphedDecoder(*args, postprocess=pp)
+    track = GraphedDecoder(*args, postprocess=pp, tracking=dict(max_tracks=32))
+    for r in (plain, track):
+        r.load(src_views=c.src_views, tgt=c.tgt, query_pos=c.query_pos, reference_points=c.reference_points).capture()
+    t_plain, t_track = [], []
+    for i in range(warm + reps):                                         # alternating in one process
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        plain.replay()
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        track.replay()
+        torch.cuda.synchronize()
+        t2 = time.perf_counter()
+        if i >= warm:
+            t_plain.append((t1 - t0) * 1e3)
+            t_track.append((t2 - t1) * 1e3)
+    assert torch.equal(plain.detections[0], track.detections[0])
+    kept = int(track.detections[1][0, 0])
+    st = track.tracker.state()
+    assert st["frames"] == warm + reps and st["births"] == min(kept, 32)
+    say("cfg2 bf16 valid10, replay + synchronise per frame, host wall (%d kept poses, %d tracks)" % (kept, st["active"]))
+    say("    GraphedDecoder(postprocess)                  %s" % _stats(t_plain))
+    say("    GraphedDecoder(postprocess, tracking)        %s  (%d reps)" % (_stats(t_track), len(t_track)))
+    return dict(frame_ms_plain=statistics.median(t_plain), frame_ms_tracking=statistics.median(t_track), kept=kept)
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--out", default=None, help="also write the printed lines to this file")
+    a = ap.parse_args()
+    res = frames(a.reps, a.warmup)
+    res.update(updates(a.reps, a.warmup))
+    say(json.dumps(res))
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write("\n".join(LINES) + "\n")
