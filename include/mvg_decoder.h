@@ -731,6 +731,37 @@ int mvg_track_update(const float* dets, const int* count, int B, int R, int J, i
                      float* score, float* pose, int* next_id, int64_t* state, double max_dist, int max_misses, int min_hits,
                      int* ids, int* slots, void* stream);
 
+/* Constant-velocity motion model of the tracker: two launches AROUND an unchanged mvg_track_update (predict, update, correct), one
+ * workgroup per stream each, fixed shapes, nothing read back, no atomics, every element with one writer: bit-reproducible, and
+ * capturable in a HIP graph with the update.  Motion state, owned by the caller: mean (B, T, J, 2, 3) fp64 = position xyz and
+ * velocity xyz per joint, var (B, T, 3) fp64 = pxx, pxv, pvv, ONE 2 x 2 covariance per track (the same noise on every joint and
+ * axis: the covariance follows the track's hit / miss history, not the data).  fp64, every operation rounded on its own, in the
+ * order written; (float) rounds to nearest even.
+ *
+ * mvg_track_predict, before the update: for every slot with id >= 0 (free slots are not touched), with dt2 = dt*dt, dt3 = dt2*dt,
+ * dt4 = dt2*dt2, qxx = (q*dt4)/4, qxv = (q*dt3)/2, qvv = q*dt2:
+ *   per joint and axis: x = x + v*dt; pose = (float) x;
+ *   pxx' = ((pxx + (2*dt)*pxv) + dt2*pvv) + qxx;  pxv' = (pxv + dt*pvv) + qxv;  pvv' = pvv + qvv   (old values on the right).
+ * The update then associates against the predicted poses; a track it does not match keeps its prediction.
+ * MVG_E_BADARG, and nothing launched, for B, T or J < 1 or above their MVG_TRACK_MAX_*, a NULL pointer, a mean or var pointer that
+ * is not 8-byte aligned, dt not finite or <= 0, q < 0, NaN or > MVG_LAP_BIG. */
+int mvg_track_predict(int B, int T, int J, const int* id, float* pose, double* mean, double* var, double dt, double q, void* stream);
+
+/* mvg_track_correct, after the update, every slot by its state as the update left it (id, hits, misses, slots are read only):
+ *   free (id < 0): mean and var of the slot = 0.
+ *   missed (id >= 0, misses > 0): nothing changes.
+ *   born in this call (id >= 0, misses == 0, hits == 1; also a slot freed and reopened by the same update):
+ *     x = (double) pose, v = 0, var = (r, 0, v0).
+ *   matched (id >= 0, misses == 0, hits > 1): pose holds the detection z.  s = pxx + r; kx = pxx/s; kv = pxv/s; per joint and axis
+ *     e = z - x; x = x + kx*e; v = v + kv*e; pose = (float) x; then pvv' = pvv - kv*pxv; pxv' = (1 - kx)*pxv; pxx' = (1 - kx)*pxx
+ *     (old values on the right).
+ *   Then for every row of slots (B, R): row_pose (B, R, J, 3) fp32 = pose of the row's slot, zeros where slots < 0: the filtered
+ *   pose of every kept detection.
+ * MVG_E_BADARG, and nothing launched, for B, R, T or J < 1 or above their MVG_TRACK_MAX_*, a NULL pointer, a mean or var pointer
+ * that is not 8-byte aligned, r <= 0, v0 < 0, or either NaN or > MVG_LAP_BIG. */
+int mvg_track_correct(int B, int R, int T, int J, const int* id, const int* hits, const int* misses, const int* slots, float* pose,
+                      double* mean, double* var, double r, double v0, float* row_pose, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

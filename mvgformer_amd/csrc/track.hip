@@ -12,6 +12,9 @@
 //                           rows (LDS scan), the active slots (one ballot), the track x detection mean joint distances by all
 //                           threads into LDS, the solve on wavefront 0, then matches / misses / deaths (a lane per track),
 //                           births (thread 0, in detection order), pose copies and the per-row outputs by all threads.
+//   mvg_track_predict,      the optional constant-velocity motion model, 1 launch each around the unchanged update, one workgroup
+//   mvg_track_correct       per stream: a Kalman filter per track (position and velocity per joint and axis, one 2 x 2 covariance
+//                           per track); the update then associates against predicted poses.  No LDS, no atomics.
 //
 // The solver is the shortest-augmenting-path Hungarian algorithm with potentials, rows inserted in order, stated so that a host
 // restatement gives the same bits (include/mvg_decoder.h): the per-column operations of a step are independent and are executed
@@ -337,7 +340,130 @@ __global__ __launch_bounds__(TRACK_THREADS) void track_update_kernel(const float
   }
 }
 
+// ------------------------------------------------------------------------------------------------------------------------------
+// The constant-velocity motion model around the update.  One workgroup per stream, threads striding over the T * J * 3 coordinates
+// of its slots; a slot's three covariance entries belong to the thread of its first coordinate.  Each operation below is one
+// rounded fp64 operation, in the order of include/mvg_decoder.h.  The library is built with -ffp-contract=fast, which fuses a
+// multiply into the add behind it whatever the pragma above says; a product that feeds an add therefore goes through track_mul,
+// whose empty asm statement the compiler cannot fuse across.
+static __device__ __forceinline__ double track_mul(double a, double b) {
+  double p = a * b;
+  asm volatile("" : "+v"(p));
+  return p;
+}
+
+__global__ __launch_bounds__(TRACK_THREADS) void track_predict_kernel(int T, int J, const int* __restrict__ id, float* __restrict__ pose,
+                                                                      double* __restrict__ mean, double* __restrict__ var, double dt,
+                                                                      double q) {
+  const int b = blockIdx.x, J3 = J * 3;
+  const double dt2 = dt * dt;
+  const double dt3 = dt2 * dt, dt4 = dt2 * dt2;
+  const double qxx = (q * dt4) / 4.0, qxv = (q * dt3) / 2.0, qvv = q * dt2;
+  for (int e = threadIdx.x; e < T * J3; e += TRACK_THREADS) {
+    const int t = e / J3, k = e % J3;
+    const size_t slot = (size_t)b * T + t;
+    if (id[slot] < 0) continue;
+    double* m = mean + (slot * J + k / 3) * 6 + k % 3;       // m[0] position, m[3] velocity of this joint and axis
+    const double x = m[0] + track_mul(m[3], dt);
+    m[0] = x;
+    pose[slot * J3 + k] = (float)x;
+    if (k == 0) {
+      double* p = var + slot * 3;
+      const double pxx = p[0], pxv = p[1], pvv = p[2];
+      p[0] = ((pxx + track_mul(2.0 * dt, pxv)) + track_mul(dt2, pvv)) + qxx;
+      p[1] = (pxv + track_mul(dt, pvv)) + qxv;
+      p[2] = pvv + qvv;
+    }
+  }
+}
+
+// var is read by every thread of a slot and written by one: the writes come behind a barrier, in a second pass.  The rows then
+// read the poses the first pass wrote, behind the same barrier (the stream's slots and rows belong to this workgroup alone).
+__global__ __launch_bounds__(TRACK_THREADS) void track_correct_kernel(int R, int T, int J, const int* __restrict__ id,
+                                                                      const int* __restrict__ hits, const int* __restrict__ misses,
+                                                                      const int* __restrict__ slots, float* pose,
+                                                                      double* __restrict__ mean, double* var, double r, double v0,
+                                                                      float* __restrict__ row_pose) {
+  const int b = blockIdx.x, J3 = J * 3;
+  for (int e = threadIdx.x; e < T * J3; e += TRACK_THREADS) {
+    const int t = e / J3, k = e % J3;
+    const size_t slot = (size_t)b * T + t;
+    double* m = mean + (slot * J + k / 3) * 6 + k % 3;
+    if (id[slot] < 0) {                                        // free
+      m[0] = 0.0;
+      m[3] = 0.0;
+    } else if (misses[slot] > 0) {                             // missed: the prediction stands
+    } else if (hits[slot] == 1) {                              // born in this call
+      m[0] = (double)pose[slot * J3 + k];
+      m[3] = 0.0;
+    } else {                                                   // matched: pose holds the detection
+      const double pxx = var[slot * 3], pxv = var[slot * 3 + 1];
+      const double s = pxx + r;
+      const double kx = pxx / s, kv = pxv / s;
+      double x = m[0], v = m[3];
+      const double d = (double)pose[slot * J3 + k] - x;
+      x = x + track_mul(kx, d);
+      v = v + track_mul(kv, d);
+      m[0] = x;
+      m[3] = v;
+      pose[slot * J3 + k] = (float)x;
+    }
+  }
+  __syncthreads();
+  for (int t = threadIdx.x; t < T; t += TRACK_THREADS) {
+    const size_t slot = (size_t)b * T + t;
+    double* p = var + slot * 3;
+    if (id[slot] < 0) {
+      p[0] = 0.0;
+      p[1] = 0.0;
+      p[2] = 0.0;
+    } else if (misses[slot] > 0) {
+    } else if (hits[slot] == 1) {
+      p[0] = r;
+      p[1] = 0.0;
+      p[2] = v0;
+    } else {
+      const double pxx = p[0], pxv = p[1], pvv = p[2];
+      const double s = pxx + r;
+      const double kx = pxx / s, kv = pxv / s;
+      p[2] = pvv - track_mul(kv, pxv);
+      p[1] = (1.0 - kx) * pxv;
+      p[0] = (1.0 - kx) * pxx;
+    }
+  }
+  for (int e = threadIdx.x; e < R * J3; e += TRACK_THREADS) {
+    const int slot = slots[(size_t)b * R + e / J3];
+    row_pose[(size_t)b * R * J3 + e] = (slot >= 0 && slot < T) ? pose[((size_t)b * T + slot) * J3 + e % J3] : 0.f;
+  }
+}
+
+static bool track_noise_ok(double v, bool zero_ok) { return (zero_ok ? v >= 0.0 : v > 0.0) && v <= MVG_LAP_BIG; }   // false for NaN
+
 extern "C" {
+
+int mvg_track_predict(int B, int T, int J, const int* id, float* pose, double* mean, double* var, double dt, double q, void* stream) {
+  if (B < 1 || B > MVG_TRACK_MAX_B || T < 1 || T > MVG_TRACK_MAX_T || J < 1 || J > MVG_TRACK_MAX_J) return MVG_E_BADARG;
+  if (id == nullptr || pose == nullptr || mean == nullptr || var == nullptr) return MVG_E_BADARG;
+  if (((uintptr_t)mean & 7) || ((uintptr_t)var & 7)) return MVG_E_BADARG;
+  if (!(dt > 0.0) || !(dt <= 1.79769313486231570815e+308) || !track_noise_ok(q, true)) return MVG_E_BADARG;
+  hipLaunchKernelGGL(track_predict_kernel, dim3(B), dim3(TRACK_THREADS), 0, (hipStream_t)stream, T, J, id, pose, mean, var, dt, q);
+  MVG_LAUNCH_CHECK();
+  return 0;
+}
+
+int mvg_track_correct(int B, int R, int T, int J, const int* id, const int* hits, const int* misses, const int* slots, float* pose,
+                      double* mean, double* var, double r, double v0, float* row_pose, void* stream) {
+  if (B < 1 || B > MVG_TRACK_MAX_B || R < 1 || R > MVG_TRACK_MAX_R || J < 1 || J > MVG_TRACK_MAX_J || T < 1 || T > MVG_TRACK_MAX_T)
+    return MVG_E_BADARG;
+  if (id == nullptr || hits == nullptr || misses == nullptr || slots == nullptr || pose == nullptr) return MVG_E_BADARG;
+  if (mean == nullptr || var == nullptr || row_pose == nullptr) return MVG_E_BADARG;
+  if (((uintptr_t)mean & 7) || ((uintptr_t)var & 7)) return MVG_E_BADARG;
+  if (!track_noise_ok(r, false) || !track_noise_ok(v0, true)) return MVG_E_BADARG;
+  hipLaunchKernelGGL(track_correct_kernel, dim3(B), dim3(TRACK_THREADS), 0, (hipStream_t)stream, R, T, J, id, hits, misses, slots, pose,
+                     mean, var, r, v0, row_pose);
+  MVG_LAUNCH_CHECK();
+  return 0;
+}
 
 int mvg_linear_assignment(const double* cost, const int* n, const int* m, int B, int N, int M, int* col_of_row, double* total,
                           void* stream) {

@@ -1424,3 +1424,75 @@ def track_update(dets, count, buffers, max_dist=500.0, max_misses=10, min_hits=1
                                      int(max_misses), int(min_hits), L.ptr(buffers["ids"]), L.ptr(buffers["slots"]),
                                      L.stream_ptr()), "mvg_track_update")
     return buffers["ids"], buffers["slots"]
+
+
+_TRACK_MOTION_KEYS = (("mean", torch.float64), ("var", torch.float64), ("row_pose", torch.float32))
+
+
+def track_motion_buffers(B, T, J, R, device="cuda"):
+    """the state of the tracker's motion model next to track_buffers(B, T, J, R) -- mean (B, T, J, 2, 3) fp64 (position and velocity
+    xyz per joint), var (B, T, 3) fp64 (pxx, pxv, pvv: one covariance per track) -- plus the static output row_pose (B, R, J, 3)
+    fp32, the filtered pose of every row.  All zeros; allocated once and kept alive by the caller like track_buffers."""
+    B, T, J, R = int(B), int(T), int(J), int(R)
+    if not (1 <= B <= TRACK_MAX_B and 1 <= T <= TRACK_MAX_T and 1 <= J <= TRACK_MAX_J and 1 <= R <= TRACK_MAX_R):
+        raise L.MvgError("track_motion_buffers: unsupported shape B = %d (<= %d), T = %d (<= %d), J = %d (<= %d), R = %d (<= %d)"
+                         % (B, TRACK_MAX_B, T, TRACK_MAX_T, J, TRACK_MAX_J, R, TRACK_MAX_R))
+    shapes = dict(mean=(B, T, J, 2, 3), var=(B, T, 3), row_pose=(B, R, J, 3))
+    return {k: torch.zeros(shapes[k], dtype=dt, device=device) for k, dt in _TRACK_MOTION_KEYS}
+
+
+def _track_motion_inputs(name, buffers, motion, keys):
+    """the checks track_predict and track_correct share -> (B, T, J, R)"""
+    tensors = [buffers[k] for k in keys] + [motion[k] for k, _ in _TRACK_MOTION_KEYS]
+    L.require_cuda(*tensors)
+    pose = buffers["pose"]
+    if pose.dim() != 4 or pose.shape[-1] != 3:
+        raise RuntimeError("%s: buffers are not those of track_buffers" % name)
+    B, T, J = pose.shape[:3]
+    R = buffers["slots"].shape[1] if buffers["slots"].dim() == 2 else 0
+    want = dict(id=(B, T), hits=(B, T), misses=(B, T), pose=(B, T, J, 3), slots=(B, R))
+    dtypes = dict(_TRACK_KEYS)
+    if any(buffers[k].dtype != dtypes[k] or tuple(buffers[k].shape) != want[k] for k in keys):
+        raise RuntimeError("%s: buffers are not those of track_buffers" % name)
+    shapes = dict(mean=(B, T, J, 2, 3), var=(B, T, 3), row_pose=(B, R, J, 3))
+    if any(motion[k].dtype != dt or tuple(motion[k].shape) != shapes[k] for k, dt in _TRACK_MOTION_KEYS):
+        raise RuntimeError("%s: motion buffers are not those of track_motion_buffers for pose %s" % (name, tuple(pose.shape)))
+    if not all(t.is_contiguous() for t in tensors):
+        raise RuntimeError("%s: every tensor must be contiguous" % name)
+    if not (1 <= B <= TRACK_MAX_B and 1 <= T <= TRACK_MAX_T and 1 <= J <= TRACK_MAX_J and 1 <= R <= TRACK_MAX_R):
+        raise L.MvgError("%s: unsupported shape B = %d (<= %d), T = %d (<= %d), J = %d (<= %d), R = %d (<= %d)"
+                         % (name, B, TRACK_MAX_B, T, TRACK_MAX_T, J, TRACK_MAX_J, R, TRACK_MAX_R))
+    return B, T, J, R
+
+
+def track_predict(buffers, motion, dt=1.0, q=25.0):
+    """The motion model's step BEFORE track_update (mvg_track_predict: one launch, nothing read back): every live slot of
+    ``buffers`` (track_buffers) moves one step of dt ahead at its velocity in ``motion`` (track_motion_buffers), its covariance
+    grows by the process noise q (the variance of a random acceleration), and ``buffers["pose"]`` becomes the predicted pose the
+    update associates against.  Free slots are not touched."""
+    B, T, J, _ = _track_motion_inputs("mvg_track_predict", buffers, motion, ("id", "pose"))
+    dt, q = float(dt), float(q)
+    if not (0.0 < dt < float("inf")) or not (0.0 <= q <= LAP_BIG):
+        raise L.MvgError("mvg_track_predict: finite dt > 0 and 0 <= q <= %g expected (got %r, %r)" % (LAP_BIG, dt, q))
+    lib = L.load()
+    with _timed("track_predict"):
+        L.check(lib.mvg_track_predict(B, T, J, L.ptr(buffers["id"]), L.ptr(buffers["pose"]), L.ptr(motion["mean"]),
+                                      L.ptr(motion["var"]), dt, q, L.stream_ptr()), "mvg_track_predict")
+
+
+def track_correct(buffers, motion, r=400.0, v0=2500.0):
+    """The motion model's step AFTER track_update (mvg_track_correct: one launch, nothing read back), every slot by the state the
+    update left: a matched track's mean moves towards the detection by the Kalman gain of its covariance and measurement noise r
+    and ``buffers["pose"]`` becomes the filtered pose; a track born in this update starts at the detection with zero velocity and
+    the covariance (r, 0, v0); a missed track keeps its prediction; a free slot's motion state is zeroed.  Then
+    ``motion["row_pose"]`` (B, R, J, 3) gets the pose of every row's slot (``buffers["slots"]``), zeros for rows without one."""
+    B, T, J, R = _track_motion_inputs("mvg_track_correct", buffers, motion, ("id", "hits", "misses", "slots", "pose"))
+    r, v0 = float(r), float(v0)
+    if not (0.0 < r <= LAP_BIG) or not (0.0 <= v0 <= LAP_BIG):
+        raise L.MvgError("mvg_track_correct: 0 < r <= %g and 0 <= v0 <= %g expected (got %r, %r)" % (LAP_BIG, LAP_BIG, r, v0))
+    lib = L.load()
+    with _timed("track_correct"):
+        L.check(lib.mvg_track_correct(B, R, T, J, *(L.ptr(buffers[k]) for k in ("id", "hits", "misses", "slots", "pose")),
+                                      L.ptr(motion["mean"]), L.ptr(motion["var"]), r, v0, L.ptr(motion["row_pose"]),
+                                      L.stream_ptr()), "mvg_track_correct")
+    return motion["row_pose"]

@@ -41,7 +41,10 @@ and accumulated in ``runner.evaluator``; nothing is read back per frame, the met
 (and behind the evaluator, if there is one; neither reads the other's output) with ``tracking.PoseTracker.update``, one more
 launch: every replay associates the kept poses with the tracks of the frames before.  ``runner.track_ids`` = ``(ids, slots)``,
 (B, dets_rows) int32 per row of ``runner.detections[0]``, static and overwritten by the next replay; ``runner.tracker`` holds the
-state (``.tracks()``, ``.state()``, ``.reset()``).  The warm-up forwards of a capture leave the tracks as they were.
+state (``.tracks()``, ``.state()``, ``.reset()``).  The warm-up forwards of a capture leave the tracks as they were.  One more
+key, ``motion=True`` or ``motion=dict(dt=1.0, q=25.0, r=400.0, v0=2500.0)``, turns on the tracker's constant-velocity motion model
+(``tracking.PoseTracker(motion=...)``: two more launches in the graph, the four values fixed at capture): ``runner.track_poses``
+(B, dets_rows, J, 3) fp32 is then the filtered pose of every row of ``runner.detections[0]``, static like ``track_ids``.
 """
 from __future__ import annotations
 
@@ -111,17 +114,18 @@ class GraphedDecoder:
             self.evaluator = DeviceEvaluator(device=dev, **evaluation)
             self.ground_truth = self.evaluator.ground_truth_buffers(batch, self._nms["dets"].shape[2])
         # optional person identities across the replayed frames behind the NMS, inside the same graph
-        self.tracker, self.track_ids = None, None
+        self.tracker, self.track_ids, self.track_poses = None, None, None
         if tracking is not None:
             from .tracking import PoseTracker
             if postprocess is None:
                 raise ValueError("GraphedDecoder: tracking follows the rows the NMS keeps; it requires postprocess")
-            unknown = set(tracking) - {"max_tracks", "max_dist", "max_misses", "min_hits"}
+            unknown = set(tracking) - {"max_tracks", "max_dist", "max_misses", "min_hits", "motion"}
             if unknown:
                 raise TypeError("GraphedDecoder: unknown tracking keys %s" % sorted(unknown))
             dets = self._nms["dets"]
             self.tracker = PoseTracker(batch=batch, rows=dets.shape[1], num_joints=dets.shape[2], device=dev, **tracking)
             self.track_ids = (self.tracker.buffers["ids"], self.tracker.buffers["slots"])
+            self.track_poses = self.tracker.row_poses       # None without tracking["motion"]
 
     # ------------------------------------------------------------------ inputs (device-side copies on the current stream)
     def load(self, src_views=None, tgt=None, query_pos=None, reference_points=None, ground_truth=None):
@@ -208,7 +212,7 @@ class GraphedDecoder:
         if self.evaluator is not None:
             keep += list(self.evaluator.buffers.values()) + list(self.ground_truth)
         if self.tracker is not None:
-            keep += list(self.tracker.buffers.values())
+            keep += list(self.tracker.buffers.values()) + list((self.tracker.motion_buffers or {}).values())
         for l in self.dec.layers:
             keep += [l.proj_attn._vp, l.proj_attn._G]
             for wc in (l._wc, l.proj_attn._wc):

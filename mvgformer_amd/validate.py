@@ -17,7 +17,8 @@ geometry (``mvgformer_amd.synthetic``).  ``--cfg extract:<relative path>`` reads
 ``--device-eval 1`` on top of it scores the kept poses against the ground truth there as well (``evaluate.DeviceEvaluator``): the
 frame loop then reads nothing back and the metrics are fetched once per threshold.  ``--device-track 1``, also on top of
 ``--device-nms 1``, follows the kept poses across the frames with a ``tracking.PoseTracker`` (inside the HIP graph with
-``--graph 1``) and reports the tracker's counters per threshold.
+``--graph 1``) and reports the tracker's counters per threshold; ``--device-track-motion 1`` on top of it turns on the tracker's
+constant-velocity motion model.
 """
 from __future__ import annotations
 
@@ -169,7 +170,13 @@ def main(argv=None):
                     help="1 (needs --device-nms 1): the kept poses get person identities across the frames on the device "
                          "(tracking.PoseTracker, one launch per frame, inside the HIP graph with --graph 1); a fresh tracker per "
                          "inference_conf_thr, its counters in the report")
+    ap.add_argument("--device-track-motion", type=int, default=0, choices=[0, 1],
+                    help="1 (needs --device-track 1): the tracker's constant-velocity motion model with its default parameters "
+                         "(tracking.PoseTracker(motion=True), two more launches per frame); the report gains the mean speed of "
+                         "the live tracks")
     args = ap.parse_args(argv)
+    if args.device_track_motion and not args.device_track:
+        ap.error("--device-track-motion 1 is an option of the device tracker: it requires --device-track 1")
     if args.device_eval and not args.device_nms:
         ap.error("--device-eval 1 scores the rows of the device NMS: it requires --device-nms 1")
     if args.device_track and not args.device_nms:
@@ -199,6 +206,9 @@ def main(argv=None):
     from . import ops
     j_out = head.num_joints if conv is None else len(conv)
     tracking = dict(max_tracks=32, max_dist=500.0, max_misses=10, min_hits=1) if args.device_track else None
+    if args.device_track_motion:
+        tracking["motion"] = True
+        report["device_track_motion"] = True
     if args.device_eval:
         # which metric the ground truth gets (the rule of the host path below), and every frame's ground truth on the device
         with_gt = [f[2] for f in frames if f[2] is not None]
@@ -277,6 +287,9 @@ def main(argv=None):
         if tracker is not None:
             st = tracker.state()
             row["tracks"] = {k: st[k] for k in ("births", "deaths", "overflow", "dropped", "active")}
+            if args.device_track_motion:                                         # mean joint speed of the live tracks, unit / frame
+                speeds = [float(np.linalg.norm(vel, axis=1).mean()) for vel, _ in tracker.motion()[0].values()]
+                row["track_motion"] = {"tracks": len(speeds), "mean_speed": round(sum(speeds) / max(len(speeds), 1), 3)}
         if gts and conv is not None:
             if np.asarray(gts[0]).shape[-2] == len(conv):
                 row["PCP"] = pcp_report(kept, gts, gts_vis, evaluator if args.device_eval else None)   # shelf.py:255-330

@@ -10,6 +10,12 @@ max_tracks = 32).
      behaviour without this feature.
 
     python tools/bench_track.py [--reps 200] [--warmup 20] [--out profiles/track_device.txt]
+
+``--motion 1`` measures the constant-velocity motion model instead (PoseTracker(motion=True): predict + update + correct), each
+time against the motion-free path in the same process: the update of 1. with 4, 10 and 64 detections, eager and replayed, and
+the cfg-2 replay of 2. with tracking= against tracking= plus motion.
+
+    python tools/bench_track.py --motion 1 [--reps 200] [--warmup 20] [--out profiles/track_motion.txt]
 """
 import argparse
 import json
@@ -131,14 +137,95 @@ def frames(reps, warm):
     return dict(frame_ms_plain=statistics.median(t_plain), frame_ms_tracking=statistics.median(t_track), kept=kept)
 
 
+def motion_updates(reps, warm):
+    """PoseTracker.update without and with the motion model (predict + update + correct), the same detections, one process"""
+    from mvgformer_amd.tracking import PoseTracker
+    out = {}
+    for n, slots in ((4, 32), (10, 32), (64, 64)):
+        frames, count = _detections(n)
+        dets = frames[0].clone()
+        feed = lambda i: dets.copy_(frames[i % 2])                                   # noqa: E731
+        med = {}
+        for motion in (None, True, None, True):                                      # each twice, interleaved
+            tracker = PoseTracker(batch=1, rows=R, num_joints=J, max_tracks=slots, device=DEV, motion=motion)
+            eager = _timed(lambda: tracker.update(dets, count), feed, reps, warm)
+            st = tracker.state()
+            assert st["births"] == n and st["deaths"] == 0 and st["matches"] == n * (warm + reps - 1), st
+            tracker.reset()
+            torch.cuda.synchronize()
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                tracker.update(dets, count)
+            replay = _timed(graph.replay, feed, reps, warm)
+            st = tracker.state()
+            assert st["births"] == n and st["matches"] == n * (warm + reps - 1), st
+            name = "motion" if motion else "plain "
+            say("    PoseTracker.update (1, %d, %d), %2d slots, %2d detections, %s  eager   %s" % (R, J, slots, n, name, _stats(eager)))
+            say("                                                                    replay  %s  (%d reps)"
+                % (_stats(replay), len(replay)))
+            med.setdefault((name.strip(), "eager"), []).append(statistics.median(eager))
+            med.setdefault((name.strip(), "replay"), []).append(statistics.median(replay))
+        for how in ("eager", "replay"):
+            plain, motion = min(med[("plain", how)]), min(med[("motion", how)])
+            say("      -> %2d of %2d %-6s  added by the motion model: %+.3f ms per frame (%.3f -> %.3f, the lower median of two passes)"
+                % (n, slots, how, motion - plain, plain, motion))
+            out["update_ms_%s_%d_of_%d" % (how, n, slots)] = plain
+            out["update_ms_%s_motion_%d_of_%d" % (how, n, slots)] = motion
+    return out
+
+
+def motion_frames(reps, warm):
+    """cfg-2 GraphedDecoder replay with tracking= against tracking= plus motion, alternating in one process"""
+    from mvgformer_amd.factory import build_decoder_for_case, case_to_device
+    from mvgformer_amd.serving import GraphedDecoder
+    from mvgformer_amd.synthetic import build_case
+    c = case_to_device(build_case("cfg2", seed=0, valid_fraction=0.1), DEV)
+    dec = build_decoder_for_case(c, DEV, dtype=torch.bfloat16)
+    pp = dict(dist_thr=0.3, num_nearby_joints_thr=7)
+    args = (dec, c.meta, c.spatial_shapes, c.level_start_index, 1, c.NQ, 0.1)
+    track = GraphedDecoder(*args, postprocess=pp, tracking=dict(max_tracks=32))
+    motion = GraphedDecoder(*args, postprocess=pp, tracking=dict(max_tracks=32, motion=True))
+    for r in (track, motion):
+        r.load(src_views=c.src_views, tgt=c.tgt, query_pos=c.query_pos, reference_points=c.reference_points).capture()
+    t_track, t_motion = [], []
+    for i in range(warm + reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        track.replay()
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        motion.replay()
+        torch.cuda.synchronize()
+        t2 = time.perf_counter()
+        if i >= warm:
+            t_track.append((t1 - t0) * 1e3)
+            t_motion.append((t2 - t1) * 1e3)
+    assert torch.equal(track.detections[0], motion.detections[0]) and torch.equal(track.track_ids[0], motion.track_ids[0])
+    kept = int(motion.detections[1][0, 0])
+    st = motion.tracker.state()
+    assert st["frames"] == warm + reps and st == track.tracker.state()
+    say("cfg2 bf16 valid10, replay + synchronise per frame, host wall (%d kept poses, %d tracks)" % (kept, st["active"]))
+    say("    GraphedDecoder(postprocess, tracking)          %s" % _stats(t_track))
+    say("    GraphedDecoder(postprocess, tracking + motion) %s  (%d reps)" % (_stats(t_motion), len(t_motion)))
+    say("      -> added by the motion model: %+.3f ms per frame" % (statistics.median(t_motion) - statistics.median(t_track)))
+    return dict(frame_ms_tracking=statistics.median(t_track), frame_ms_tracking_motion=statistics.median(t_motion), kept=kept)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--motion", type=int, default=0, choices=[0, 1],
+                    help="1: measure the constant-velocity motion model instead (PoseTracker(motion=True) against motion=None, and "
+                         "GraphedDecoder tracking= with and without motion), e.g. --out profiles/track_motion.txt")
     ap.add_argument("--out", default=None, help="also write the printed lines to this file")
     a = ap.parse_args()
-    res = frames(a.reps, a.warmup)
-    res.update(updates(a.reps, a.warmup))
+    if a.motion:
+        res = motion_frames(a.reps, a.warmup)
+        res.update(motion_updates(a.reps, a.warmup))
+    else:
+        res = frames(a.reps, a.warmup)
+        res.update(updates(a.reps, a.warmup))
     say(json.dumps(res))
     if a.out:
         with open(a.out, "w") as f:
