@@ -762,6 +762,58 @@ int mvg_track_predict(int B, int T, int J, const int* id, float* pose, double* m
 int mvg_track_correct(int B, int R, int T, int J, const int* id, const int* hits, const int* misses, const int* slots, float* pose,
                       double* mean, double* var, double r, double v0, float* row_pose, void* stream);
 
+/* ---- structural triangulation: fixed bone lengths (csrc/structural.hip) ------------------------------------------------------- */
+#define MVG_ST_MAX_J 17               /* joints of a tree: the reduced system has 3 (J - 1) <= 48 rows, a lane each             */
+#define MVG_ST_MAX_V 32
+#define MVG_ST_MAX_STEPS 8
+#define MVG_ST_LS 0                   /* the unconstrained least squares in bone coordinates                                   */
+#define MVG_ST_ST 1                   /* n_steps constrained steps towards the given bone lengths                              */
+
+/* A person's J joints from their 2D observations in V views under fixed bone lengths (lib/structural/structural_triangulation.py:
+ * Pose3D_inference with method 'ST' / 'LS'), ONE launch, one wavefront per person, fixed shapes, nothing read back, no atomics,
+ * every element with one writer: bit-reproducible, a person's result does not depend on the others, capturable in a HIP graph.
+ *   ud (B, V, NQ*J, 2) undistorted original-image px, conf (B, V, NQ*J) weights or NULL (= 1 / V, in fp64), Pm (B, V, 3, 4) =
+ *   [KR | t], all fp32, the layout of mvg_dlt_forward.  parent: J HOST ints, by value in the launch arguments: parent[0] = -1 (the
+ *   root), every other joint reaches joint 0 along parent[] (any index order).  Bone k (k = 1 .. J-1) ends at joint k; anc(i) =
+ *   the bones on the path root -> i.  bone_len fp32: (J-1) shared, or (B, P, J-1) with bone_len_per_person != 0; entry k-1 is
+ *   bone k; not read (may be NULL) for MVG_ST_LS.
+ *   Persons, P per batch element:  rows == NULL (dense; P must equal NQ): person (b, p) is query p if valid == NULL or
+ *   valid[b, p] != 0 (valid (B, NQ) uint8).  rows != NULL: rows (B, P) int32 with row stride rows_ld >= P, count (B, 2) int32 or
+ *   NULL as mvg_pose_nms writes keep and count: person (b, p) is query rows[b, p] for p < min(max(count[b, 0], 0), P) (P without
+ *   count) and 0 <= rows[b, p] < NQ; valid must be NULL.
+ * Arithmetic: fp64 from the fp32 inputs, every product and sum rounded on its own, division and sqrt correctly rounded; "sum" =
+ * an accumulation from +0.0 in ascending index order by one lane.  n = 3 (J - 1), K = J - 1.
+ *   1. Per joint i, views ascending: g0 = r0 - u r2, g1 = r1 - w r2 (r = the rows of KR), h0 = t0 - u t2, h1 = t1 - w t2,
+ *      c2 = 2 c;  D_i[a][b] += c2 (g0[a] g0[b] + g1[a] g1[b]);  m_i[a] -= c2 (g0[a] h0 + g1[a] h1)   (KR^T M KR = g0 g0^T + g1 g1^T
+ *      for the reference's M = [[1, 0, -u], [0, 1, -w], [-u, -w, u^2 + w^2]]).
+ *   2. T = sum_i D_i, mu = sum_i m_i;  C_k = sum_{i: k in anc(i)} D_i, cm_k likewise from m_i (i ascending).  Tinv = T^-1 by the
+ *      factorisation below.  W_k = Tinv C_k, tm = Tinv mu (sums over the inner index).  For c <= r, with r = 3 (k-1) + a,
+ *      c = 3 (l-1) + bb:  A[r][c] = base - sum_t C_k[a][t] W_l[t][bb],  base = C_l[a][bb] if k in anc(l), else C_k[a][bb] if l in
+ *      anc(k), else 0.  beta[r] = cm_k[a] - sum_t C_k[a][t] tm[t].
+ *   3. Inv = A^-1 by the factorisation below;  b[r] = sum_c Inv[r][c] beta[c].  MVG_ST_LS goes to 5.
+ *   4. For s = 0 .. n_steps-1:  start_k = sqrt((b0 b0 + b1 b1) + b2 b2) of bone k's three entries;
+ *      target_k = (start_k (n_steps-s-1) + L_k) / (n_steps-s);  rhs_k = (start_k start_k - target_k target_k) / 4;
+ *      S[k][l] = sum_a b_k[a] (sum_c Inv[3k+a][3l+c] b_l[c]) for l <= k;  S = L L^T as below;  y_i = (rhs_i - sum_{k<i} L[i][k] y_k)
+ *      / L[i][i] (i ascending), lambda_i = (y_i - sum_{k>i ascending} L[k][i] lambda_k) / L[i][i] (i descending);  for c <= r:
+ *      Inv'[r][c] = Inv[r][c] - sum_j (Inv[r][j] (2 lambda_{j/3})) Inv[j][c], written to both triangles;  b = Inv' beta as in 3.
+ *   5. x0[a] = sum_t Tinv[a][t] (mu[t] - sum_j Cflat[t][j] b[j]) with Cflat[t][3 (k-1) + c] = C_k[t][c];  x_i = x0 + the b_k of
+ *      k in anc(i), k ascending;  X = (float) x, round to nearest even.
+ *   Factorisation of a symmetric M (its lower triangle): Cholesky column by column, j ascending: s_i = M[i][j] -
+ *   sum_{k<j ascending} L[i][k] L[j][k] for i >= j; the pivot s_j must be > 0 (a NaN is not); L[j][j] = sqrt(s_j), L[i][j] =
+ *   s_i / L[j][j].  Inverse: Y = L^-1 by Y[i][c] = ((i == c ? 1 : 0) - sum_{k=c}^{i-1} L[i][k] Y[k][c]) / L[i][i] for i >= c, then
+ *   M^-1[r][c] = sum_{k=r}^{n-1} Y[k][r] Y[k][c] for c <= r, written to both triangles.
+ * Outputs, every element written by every call: X (B, P, J, 3) fp32 and status (B, P) int32:
+ *    0  solved;   1  a pivot of T or A was not > 0 (degenerate or non-finite input): X = 0;
+ *    2  a pivot of S was not > 0 at some step: X from the b of the last completed step (the LS solution at the first);
+ *   -1  not computed (valid == 0, a row at or behind the count, a row index outside [0, NQ)): X = 0.
+ * Every loop is counted: no input can make the kernel spin or fault.
+ * MVG_E_BADARG, and nothing launched, for J < 2 or > MVG_ST_MAX_J, V < 1 or > MVG_ST_MAX_V, n_steps < 1 or > MVG_ST_MAX_STEPS, an
+ * unknown method, B, NQ or P < 1, a parent table that is no tree rooted at joint 0, a NULL ud / Pm / X / status / parent, a NULL
+ * bone_len with MVG_ST_ST, rows with valid or rows_ld < P, no rows with count or P != NQ. */
+int mvg_structural_triangulate(const float* ud, const float* conf, const float* Pm, const uint8_t* valid, const int* rows, int rows_ld,
+                               const int* count, const int* parent, const float* bone_len, int bone_len_per_person, int method,
+                               int n_steps, float* X, int* status, int V, int B, int NQ, int P, int J, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

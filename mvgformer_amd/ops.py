@@ -1496,3 +1496,114 @@ def track_correct(buffers, motion, r=400.0, v0=2500.0):
                                       L.ptr(motion["mean"]), L.ptr(motion["var"]), r, v0, L.ptr(motion["row_pose"]),
                                       L.stream_ptr()), "mvg_track_correct")
     return motion["row_pose"]
+
+
+ST_MAX_J, ST_MAX_V, ST_MAX_STEPS = 17, 32, 8       # MVG_ST_MAX_*
+ST_METHODS = {"LS": 0, "ST": 1}                     # MVG_ST_LS, MVG_ST_ST
+
+
+def structural_check(parent, n_steps=1, method="ST"):
+    """the host-side argument checks of structural_triangulate: parent a tree rooted at joint 0 with 2 .. ST_MAX_J joints, n_steps
+    in 1 .. ST_MAX_STEPS, method "ST" or "LS" -> (parent as a ctypes int array, the method's code)"""
+    import ctypes as C
+    if torch.is_tensor(parent):
+        if parent.is_cuda:
+            raise RuntimeError("mvg_structural_triangulate: parent travels by value with the launch: host ints expected, not a device "
+                               "tensor")
+        parent = parent.tolist()
+    parent = [int(p) for p in parent]
+    J = len(parent)
+    if not 2 <= J <= ST_MAX_J:
+        raise L.MvgError("mvg_structural_triangulate: unsupported tree of %d joints (2 .. %d)" % (J, ST_MAX_J))
+    ok = parent[0] == -1 and all(0 <= p < J for p in parent[1:])
+    for i in range(1, J):
+        j = i
+        for _ in range(J):
+            if not ok or j == 0:
+                break
+            j = parent[j]
+        ok = ok and j == 0
+    if not ok:
+        raise L.MvgError("mvg_structural_triangulate: parent %s is not a tree rooted at joint 0 (parent[0] = -1)" % (parent,))
+    if method not in ST_METHODS:
+        raise L.MvgError("mvg_structural_triangulate: unknown method %r (one of %s)" % (method, sorted(ST_METHODS)))
+    if not 1 <= int(n_steps) <= ST_MAX_STEPS:
+        raise L.MvgError("mvg_structural_triangulate: n_steps = %r outside 1 .. %d" % (n_steps, ST_MAX_STEPS))
+    return (C.c_int * J)(*parent), ST_METHODS[method]
+
+
+def structural_buffers(B, P, J, device="cuda"):
+    """the static outputs of structural_triangulate(out=...): poses (B, P, J, 3) fp32 zeros and status (B, P) int32 filled with -1
+    (not computed).  A caller that captures the launch in a HIP graph allocates them once and keeps them alive with the graph."""
+    B, P, J = int(B), int(P), int(J)
+    if not (B >= 1 and P >= 1 and 2 <= J <= ST_MAX_J):
+        raise L.MvgError("structural_buffers: unsupported shape B = %d, P = %d, J = %d (2 .. %d)" % (B, P, J, ST_MAX_J))
+    return dict(poses=torch.zeros((B, P, J, 3), dtype=torch.float32, device=device),
+                status=torch.full((B, P), -1, dtype=torch.int32, device=device))
+
+
+def structural_triangulate(ud, conf, Pm, parent, bone_lengths, valid=None, rows=None, count=None, n_steps=1, method="ST", out=None):
+    """Structural triangulation on the device (mvg_structural_triangulate: one launch, one wavefront per person, fp64, nothing read
+    back): every person's J joints from their observations ud (B, V, NQ*J, 2) fp32 (undistorted original-image px) in the views
+    Pm (B, V, 3, 4) fp32 with weights conf (B, V, NQ*J) fp32 or None (= 1 / V), under the bone lengths bone_lengths, fp32 (J-1)
+    shared or (B, P, J-1) per person (entry k-1: the bone that ends at joint k; None is allowed for method "LS").  parent: the
+    tree as J host ints (a sequence or a CPU tensor), parent[0] = -1.
+    Persons: dense (rows None): every query, P = NQ, where valid (B, NQ) uint8 is None or non-zero.  Rows: rows (B, P) int32 query
+    indices (unit stride in a row; a column slice of a wider tensor is fine) and count (B, 2) int32 or None as pose_nms writes
+    keep and count: person (b, p) is query rows[b, p] for p < count[b, 0].
+    method "ST": n_steps (1 .. 8) constrained steps; "LS": the unconstrained solution in the same coordinates.
+    -> (X (B, P, J, 3) fp32, status (B, P) int32): 0 solved, 1 degenerate or non-finite input (X = 0), 2 a step's multiplier system
+    was not positive definite (X from the last completed step), -1 not computed (X = 0).  out: the dict of structural_buffers."""
+    L.require_cuda(ud, conf, Pm, bone_lengths, valid, rows, count)
+    name = "mvg_structural_triangulate"
+    parent_c, method_c = structural_check(parent, n_steps, method)
+    J = len(parent_c)
+    if ud.dim() != 4 or ud.shape[-1] != 2 or ud.dtype != torch.float32 or ud.shape[2] % J:
+        raise RuntimeError("%s: ud (B, V, NQ * %d, 2) float32 expected" % (name, J))
+    B, V, Lq = ud.shape[:3]
+    NQ = Lq // J
+    if Pm.dtype != torch.float32 or tuple(Pm.shape) != (B, V, 3, 4):
+        raise RuntimeError("%s: Pm (B, V, 3, 4) float32 expected" % name)
+    if conf is not None and (conf.dtype != torch.float32 or tuple(conf.shape) != (B, V, Lq)):
+        raise RuntimeError("%s: conf (B, V, NQ * J) float32 or None expected" % name)
+    if rows is not None:
+        if valid is not None:
+            raise RuntimeError("%s: valid selects the persons of the dense mode; it cannot be given with rows" % name)
+        if rows.dtype != torch.int32 or rows.dim() != 2 or rows.shape[0] != B or rows.shape[1] < 1:
+            raise RuntimeError("%s: rows (B, P) int32 expected" % name)
+        if rows.stride(1) != 1 or (B > 1 and rows.stride(0) < rows.shape[1]):
+            raise RuntimeError("%s: rows must have unit stride along a row" % name)
+        if count is not None and (count.dtype != torch.int32 or tuple(count.shape) != (B, 2)):
+            raise RuntimeError("%s: count (B, 2) int32 or None expected" % name)
+        P, rows_ld = rows.shape[1], (rows.stride(0) if B > 1 else rows.shape[1])
+    else:
+        if count is not None:
+            raise RuntimeError("%s: count belongs to the rows mode; it cannot be given without rows" % name)
+        if valid is not None and (valid.dtype != torch.uint8 or tuple(valid.shape) != (B, NQ)):
+            raise RuntimeError("%s: valid (B, NQ) uint8 or None expected" % name)
+        P, rows_ld = NQ, 0
+    per_person = 0
+    if bone_lengths is None:
+        if method != "LS":
+            raise RuntimeError("%s: method %r needs bone_lengths" % (name, method))
+    else:
+        if bone_lengths.dtype != torch.float32 or tuple(bone_lengths.shape) not in ((J - 1,), (B, P, J - 1)):
+            raise RuntimeError("%s: bone_lengths (J-1) or (B, P, J-1) float32 expected" % name)
+        per_person = int(bone_lengths.dim() == 3)
+    if not all(t is None or t.is_contiguous() for t in (ud, conf, Pm, bone_lengths, valid, count)):
+        raise RuntimeError("%s: every tensor must be contiguous" % name)
+    if not 1 <= V <= ST_MAX_V:
+        raise L.MvgError("%s: unsupported number of views %d (1 .. %d)" % (name, V, ST_MAX_V))
+    if out is None:
+        out = structural_buffers(B, P, J, ud.device)
+    X, status = out["poses"], out["status"]
+    L.require_cuda(X, status)
+    if (X.dtype != torch.float32 or tuple(X.shape) != (B, P, J, 3) or status.dtype != torch.int32 or tuple(status.shape) != (B, P)
+            or not (X.is_contiguous() and status.is_contiguous())):
+        raise RuntimeError("%s: out buffers do not fit (B, P, J) = (%d, %d, %d) (see structural_buffers)" % (name, B, P, J))
+    lib = L.load()
+    with _timed("structural_triangulate"):
+        L.check(lib.mvg_structural_triangulate(L.ptr(ud), L.ptr(conf), L.ptr(Pm), L.ptr(valid), L.ptr(rows), rows_ld, L.ptr(count),
+                                               parent_c, L.ptr(bone_lengths), per_person, method_c, int(n_steps), L.ptr(X),
+                                               L.ptr(status), V, B, NQ, P, J, L.stream_ptr()), name)
+    return X, status

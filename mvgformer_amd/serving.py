@@ -45,6 +45,14 @@ state (``.tracks()``, ``.state()``, ``.reset()``).  The warm-up forwards of a ca
 key, ``motion=True`` or ``motion=dict(dt=1.0, q=25.0, r=400.0, v0=2500.0)``, turns on the tracker's constant-velocity motion model
 (``tracking.PoseTracker(motion=...)``: two more launches in the graph, the four values fixed at capture): ``runner.track_poses``
 (B, dets_rows, J, 3) fp32 is then the filtered pose of every row of ``runner.detections[0]``, static like ``track_ids``.
+
+``refine=dict(bone_lengths=<J-1 values, mm>, n_steps=1, method="ST")`` (requires ``postprocess``) continues behind the NMS with
+``structural.StructuralRefiner.update``, two more launches, independent of ``evaluation`` and ``tracking`` (which keep reading
+``dets`` unchanged): the kept queries are re-solved from the last layer's 2D points in all views under the given bone lengths of
+the 15-joint tree.  ``runner.refined`` = ``(poses (B, dets_rows, J, 3) fp32, status (B, dets_rows) int32)`` per row of
+``runner.detections[0]`` (status 0: solved; rows behind the count: zeros, -1) and ``runner.bone_lengths`` (J-1) fp32 are static
+tensors: new lengths written into ``runner.bone_lengths`` take effect at the next replay, without re-capture.  The projection
+matrices come from the packed camera records and follow ``set_cameras``.
 """
 from __future__ import annotations
 
@@ -56,7 +64,7 @@ from .decoder import DecoderContext
 class GraphedDecoder:
     def __init__(self, decoder, meta, spatial_shapes, level_start_index, batch, num_queries, threshold=0.1, device=None,
                  producer_writes_in_place=False, channels=256, postprocess=None, convert_joint_format_indices=None, evaluation=None,
-                 tracking=None):
+                 tracking=None, refine=None):
         layer0 = decoder.layers[0]
         dev = torch.device(device) if device is not None else next(decoder.parameters()).device
         if dev.type != "cuda":
@@ -126,6 +134,26 @@ class GraphedDecoder:
             self.tracker = PoseTracker(batch=batch, rows=dets.shape[1], num_joints=dets.shape[2], device=dev, **tracking)
             self.track_ids = (self.tracker.buffers["ids"], self.tracker.buffers["slots"])
             self.track_poses = self.tracker.row_poses       # None without tracking["motion"]
+        # optional structural triangulation of the kept queries (fixed bone lengths) behind the NMS, inside the same graph
+        self.refiner, self.refined, self.bone_lengths, self._Pm = None, None, None, None
+        if refine is not None:
+            from .geometry_torch import proj_matrices_from_records
+            from .structural import PANOPTIC15_PARENT, StructuralRefiner
+            if postprocess is None:
+                raise ValueError("GraphedDecoder: refine re-solves the rows the NMS keeps; it requires postprocess")
+            unknown = set(refine) - {"bone_lengths", "n_steps", "method"}
+            if unknown:
+                raise TypeError("GraphedDecoder: unknown refine keys %s" % sorted(unknown))
+            if convert_joint_format_indices is not None or J != len(PANOPTIC15_PARENT):
+                raise ValueError("GraphedDecoder: refine solves on the 15-joint tree of the decoder's own joints; it cannot be "
+                                 "combined with convert_joint_format_indices")
+            rows = self._nms["dets"].shape[1]
+            if rows > num_queries:              # postprocess["dets_rows"] is the caller's: keep has num_queries columns, no more
+                raise ValueError("GraphedDecoder: refine with dets_rows = %d > num_queries = %d" % (rows, num_queries))
+            self.refiner = StructuralRefiner(batch=batch, rows=rows, parent=PANOPTIC15_PARENT, device=dev, **refine)
+            self.refined = (self.refiner.poses, self.refiner.status)
+            self.bone_lengths = self.refiner.bone_lengths
+            self._Pm = proj_matrices_from_records(self.ctx.cams, self.V, batch).contiguous()
 
     # ------------------------------------------------------------------ inputs (device-side copies on the current stream)
     def load(self, src_views=None, tgt=None, query_pos=None, reference_points=None, ground_truth=None):
@@ -159,6 +187,9 @@ class GraphedDecoder:
             raise RuntimeError("set_cameras: %s camera records, the runner was built for %s"
                                % (tuple(fresh.cams.shape), tuple(self.ctx.cams.shape)))
         self.ctx.cams.copy_(fresh.cams)
+        if self._Pm is not None:
+            from .geometry_torch import proj_matrices_from_records
+            self._Pm.copy_(proj_matrices_from_records(self.ctx.cams, self.V, self.tgt.shape[0]))
         self.meta = meta
         return self
 
@@ -177,6 +208,8 @@ class GraphedDecoder:
                 self.evaluator.update(self._nms["dets"], self._nms["count"], *self.ground_truth)
             if self.tracker is not None:
                 self.tracker.update(self._nms["dets"], self._nms["count"])
+            if self.refiner is not None:
+                self.refiner.update(outputs[2][-1], self.ctx.cams, self._Pm, self._nms["keep"], self._nms["count"])
         return outputs
 
     def capture(self, warmup=2):
@@ -213,6 +246,8 @@ class GraphedDecoder:
             keep += list(self.evaluator.buffers.values()) + list(self.ground_truth)
         if self.tracker is not None:
             keep += list(self.tracker.buffers.values()) + list((self.tracker.motion_buffers or {}).values())
+        if self.refiner is not None:
+            keep += list(self.refiner.buffers.values()) + [self.refiner.bone_lengths, self._Pm]
         for l in self.dec.layers:
             keep += [l.proj_attn._vp, l.proj_attn._G]
             for wc in (l._wc, l.proj_attn._wc):

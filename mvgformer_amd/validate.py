@@ -18,7 +18,10 @@ geometry (``mvgformer_amd.synthetic``).  ``--cfg extract:<relative path>`` reads
 frame loop then reads nothing back and the metrics are fetched once per threshold.  ``--device-track 1``, also on top of
 ``--device-nms 1``, follows the kept poses across the frames with a ``tracking.PoseTracker`` (inside the HIP graph with
 ``--graph 1``) and reports the tracker's counters per threshold; ``--device-track-motion 1`` on top of it turns on the tracker's
-constant-velocity motion model.
+constant-velocity motion model.  ``--device-refine 1 --bone-lengths FILE.npy`` (on top of ``--device-nms 1``) re-solves the kept
+poses under the J-1 bone lengths of the file (mm) by structural triangulation (``structural.StructuralRefiner``, inside the HIP
+graph with ``--graph 1``) and reports the share of kept rows it solved and their mean absolute bone-length residual
+before and after.
 """
 from __future__ import annotations
 
@@ -174,7 +177,17 @@ def main(argv=None):
                     help="1 (needs --device-track 1): the tracker's constant-velocity motion model with its default parameters "
                          "(tracking.PoseTracker(motion=True), two more launches per frame); the report gains the mean speed of "
                          "the live tracks")
+    ap.add_argument("--device-refine", type=int, default=0, choices=[0, 1],
+                    help="1 (needs --device-nms 1 and --bone-lengths): the kept poses are re-solved under fixed bone lengths on the "
+                         "device (structural.StructuralRefiner, two more launches per frame, inside the HIP graph with --graph 1)")
+    ap.add_argument("--bone-lengths", default=None, help=".npy file with the J-1 bone lengths in mm (entry k-1: the bone that ends "
+                                                         "at joint k of structural.PANOPTIC15_PARENT) for --device-refine 1")
+    ap.add_argument("--refine-steps", type=int, default=1, help="n_steps of --device-refine 1 (1 .. 8)")
     args = ap.parse_args(argv)
+    if args.device_refine and not args.device_nms:
+        ap.error("--device-refine 1 re-solves the rows of the device NMS: it requires --device-nms 1")
+    if args.device_refine and not args.bone_lengths:
+        ap.error("--device-refine 1 holds given bone lengths fixed: it requires --bone-lengths FILE.npy")
     if args.device_track_motion and not args.device_track:
         ap.error("--device-track-motion 1 is an option of the device tracker: it requires --device-track 1")
     if args.device_eval and not args.device_nms:
@@ -209,6 +222,10 @@ def main(argv=None):
     if args.device_track_motion:
         tracking["motion"] = True
         report["device_track_motion"] = True
+    refine = None
+    if args.device_refine:
+        refine = dict(bone_lengths=np.load(args.bone_lengths).astype(np.float32).reshape(-1), n_steps=args.refine_steps)
+        report["device_refine"] = True
     if args.device_eval:
         # which metric the ground truth gets (the rule of the host path below), and every frame's ground truth on the device
         with_gt = [f[2] for f in frames if f[2] is not None]
@@ -219,9 +236,16 @@ def main(argv=None):
     for thr in cfg.DECODER.inference_conf_thr:                                   # validate_3d.py:185
         preds, gts, gts_vis, t_dec, n_timed = [], [], [], 0.0, 0
         kept = []
-        runner, evaluator, nms_out, tracker = None, None, None, None
-        if (args.device_eval or args.device_track) and not args.graph:
+        runner, evaluator, nms_out, tracker, refiner = None, None, None, None, None
+        if refine is not None:
+            refine_sums = torch.zeros(4, dtype=torch.float64, device=dev)        # kept rows, solved rows, residual before, after
+        if (args.device_eval or args.device_track or args.device_refine) and not args.graph:
             nms_out = ops.pose_nms_buffers(1, head.num_instance, j_out, None, dev)
+            if args.device_refine:                                               # the eager form of GraphedDecoder(refine=...)
+                from .structural import StructuralRefiner
+                if conv is not None:
+                    raise ValueError("--device-refine 1 solves on the 15-joint tree: not with convert_joint_format_indices")
+                refiner = StructuralRefiner(batch=1, rows=head.num_instance, device=dev, **refine)
             if args.device_eval:
                 evaluator = E.DeviceEvaluator(device=dev, **evaluation)
             if args.device_track:                                                # a fresh tracker per threshold pass
@@ -236,8 +260,8 @@ def main(argv=None):
                 runner = GraphedDecoder(head.decoder, meta, shapes, starts, 1, head.num_instance, thr,
                                         postprocess=dict(dist_thr=0.3, num_nearby_joints_thr=7) if args.device_nms else None,
                                         convert_joint_format_indices=head.convert_joint_format_indices, evaluation=evaluation,
-                                        tracking=tracking)
-                evaluator, tracker = runner.evaluator, runner.tracker
+                                        tracking=tracking, refine=refine)
+                evaluator, tracker, refiner = runner.evaluator, runner.tracker, runner.refiner
                 qpos, tgt = caller.person_joint_queries(head.joint_embedding.weight, head.instance_embedding.weight, 1)
                 ref0 = caller.sample_space_reference_points(head.num_instance, head.space_size, head.space_center, 1, dev,
                                                             t_pose=head.t_pose)
@@ -254,19 +278,34 @@ def main(argv=None):
                                                          head.convert_joint_format_indices)
                     pred = caller.pack_predictions(out, thr)                     # function.py:386-396
             else:
-                _, pred = head(src, meta, threshold=thr)                         # function.py:372-396
+                out, pred = head(src, meta, threshold=thr)                       # function.py:372-396
             torch.cuda.synchronize()
             if fi > 0 or len(frames) == 1:          # the first frame builds the weight caches / captures the graph (one-time)
                 t_dec += time.perf_counter() - t0
                 n_timed += 1
             preds.extend(p for p in pred)
-            if (args.device_eval or args.device_track) and runner is None:       # with --graph 1 the replay has done it all
+            if nms_out is not None:                                              # with --graph 1 the replay has done it all
                 with torch.cuda.device(dev):
-                    _, count, dets = ops.pose_nms(pred.contiguous(), 0.3, 7, out=nms_out)
+                    keep, count, dets = ops.pose_nms(pred.contiguous(), 0.3, 7, out=nms_out)
+                    if refiner is not None:
+                        from .geometry_torch import proj_matrices_from_records
+                        cams = ops.pack_cameras(meta, head.decoder.layers[0].img_size, dev)
+                        refiner.update(out["pred_poses_2d"]["outputs_coord_2d"].contiguous(), cams,
+                                       proj_matrices_from_records(cams, len(meta), 1).contiguous(), keep, count)
                 if args.device_eval:
                     evaluator.update(dets, count, *gt_dev[fi])                   # launches only: nothing is read back per frame
                 if args.device_track:
                     tracker.update(dets, count)
+            if refine is not None:                                               # device sums, read back once per threshold
+                from .structural import PANOPTIC15_PARENT, bone_lengths
+                poses, status = refiner.poses, refiner.status
+                dets, count = (runner.detections[0], runner.detections[1]) if runner is not None else (nms_out["dets"], nms_out["count"])
+                live = torch.arange(poses.shape[1], device=dev)[None] < count[:, :1]
+                solved = live & (status == 0)
+                want = refiner.bone_lengths.double()
+                before = (bone_lengths(dets[..., :3].double(), PANOPTIC15_PARENT) - want).abs().mean(-1)
+                after = (bone_lengths(poses.double(), PANOPTIC15_PARENT) - want).abs().mean(-1)
+                refine_sums += torch.stack([live.sum(), solved.sum(), (before * solved).sum(), (after * solved).sum()])
             if args.device_eval:
                 pass
             elif args.device_nms and runner is not None:
@@ -290,6 +329,11 @@ def main(argv=None):
             if args.device_track_motion:                                         # mean joint speed of the live tracks, unit / frame
                 speeds = [float(np.linalg.norm(vel, axis=1).mean()) for vel, _ in tracker.motion()[0].values()]
                 row["track_motion"] = {"tracks": len(speeds), "mean_speed": round(sum(speeds) / max(len(speeds), 1), 3)}
+        if refine is not None:
+            n_live, n_solved, before, after = refine_sums.tolist()
+            row["refine"] = {"kept_rows": int(n_live), "solved_share": round(n_solved / max(n_live, 1.0), 4),
+                             "bone_residual_mm_before": round(before / max(n_solved, 1.0), 4),
+                             "bone_residual_mm_after": round(after / max(n_solved, 1.0), 4)}
         if gts and conv is not None:
             if np.asarray(gts[0]).shape[-2] == len(conv):
                 row["PCP"] = pcp_report(kept, gts, gts_vis, evaluator if args.device_eval else None)   # shelf.py:255-330
