@@ -442,6 +442,46 @@ int mvg_knn_match_jm(const float* poses, const float* joints_3d, const void* num
                      int Jp, int Jc, const int* joint_map, int Pmax, void* workspace, size_t workspace_bytes, int* pair_query,
                      int* pair_gt, int* pair_count, uint8_t* matched, void* stream);
 
+/* ---- one-to-one ground-truth matcher (csrc/hungarian.hip) ---------------------------------------------------------------------- */
+#define MVG_MATCH_HUNGARIAN      2   /* C = cost_pose * pose + cost_class * class  (matcher.py:175) */
+#define MVG_MATCH_HUNGARIAN_DIS  3   /* C = pose                                   (matcher.py:172) */
+#define MVG_HUNGARIAN_MAX_G   64
+#define MVG_HUNGARIAN_MAX_NQ  4096
+
+/* bytes of cost workspace mvg_hungarian_match needs (0 while the Gmax x NQ fp32 pose costs fit its 40 KB of LDS; 4-byte aligned) */
+size_t mvg_hungarian_match_workspace(int P, int NQ, int Gmax);
+
+/* The reference's default matcher (lib/models/matcher.py:80-199, methods 'hungarian' / 'hungarian-dis': scipy's
+ * linear_sum_assignment per batch element behind a .cpu()) for P = Lm * B independent problems in ONE launch, one workgroup of
+ * 256 lanes per problem, nothing read back, graph-capturable.  Problem p uses the ground truth of batch element p % B: Lm = 1 is
+ * the match on the initial poses, Lm = L matches every layer's own outputs.
+ *   logits (P, NQ, 2) fp32 or NULL (= logit 1.0 for every query, the reference's construct_output_from_origin); poses
+ *   (P, NQ*Jp, 3) fp32 absolute mm; joints_3d (B, Gmax, Jc, 3), num_person (B,), space_size, space_center and joint_map exactly as
+ *   for mvg_knn_match_jm (joint_map NULL = the identity, requires Jc == Jp).
+ * Costs.  pose[g][q]: the fp32 value mvg_knn_match(_jm) computes (same norm round trip, same summation order, same device
+ * function, csrc/match_dev.h: in the round trip n * size + center is one fused multiply-add, as these matchers have always
+ * been built; NaN and inf sums become +inf).  class[q], in fp64: p = 1 / (1 + exp(-(double)logits[q][1])),
+ *   class[q] = 0.25 (1-p)^2 (-log(p + 1e-8)) - 0.75 p^2 (-log(1 - p + 1e-8))          (matcher.py:151-162, every target class 1).
+ * MVG_MATCH_HUNGARIAN: C[g][q] = (double)cost_pose * pose + (double)cost_class * class, each product and the sum rounded on its
+ * own; MVG_MATCH_HUNGARIAN_DIS: C[g][q] = (double)pose.  An entry that is NaN or above MVG_LAP_BIG is taken as MVG_LAP_BIG.
+ * Solver: the algorithm of mvg_linear_assignment (below), stated for the rectangular problem without padding: rows are the
+ * G = clamp(num_person[p % B], 0, Gmax) persons, columns the NQ queries (NQ >= Gmax required); potentials u, v start at 0, rows
+ * are inserted in order, steps 1 to 4 as written there, the LOWEST column wins among equal minima, a NaN minimum orders as
+ * +inf; the search of row i is a counted loop of at most i + 1 steps and ends at a column without a row.  fp64 throughout, every
+ * operation rounded on its own, no atomics: two runs give the same bits.
+ * Outputs, every element written by every call: pair_query, pair_gt (P, Gmax) int32: the G pairs in ASCENDING QUERY order
+ * (scipy's order for this orientation), -1 in the unused slots; pair_count (P,) = G; matched (P, NQ) uint8; duals (P, Gmax + NQ)
+ * fp64 or NULL: the final u[0..Gmax) (0 for rows >= G) followed by v[0..NQ), for verification (u[g] + v[q] <= C[g][q], with
+ * equality on the pairs, v = 0 on unmatched columns).
+ * MVG_E_BADARG, nothing launched: Gmax > MVG_HUNGARIAN_MAX_G, NQ > MVG_HUNGARIAN_MAX_NQ, NQ < Gmax, P < 1, B < 1, P % B != 0, Jp or
+ * Jc outside [1, 64], a bad joint_map, method not 2 or 3, a NULL required pointer, duals not 8-byte aligned, a too small
+ * workspace. */
+int mvg_hungarian_match(const float* logits, const float* poses, const float* joints_3d, const void* num_person,
+                        int num_person_is64, const float* space_size, const float* space_center, int method, float cost_class,
+                        float cost_pose, int P, int B, int NQ, int Gmax, int Jp, int Jc, const int* joint_map, void* workspace,
+                        size_t workspace_bytes, int* pair_query, int* pair_gt, int* pair_count, uint8_t* matched, double* duals,
+                        void* stream);
+
 /* bytes of the (8-byte aligned) workspace of mvg_criterion: the projected ground truth and the per-(layer, batch) partial sums */
 size_t mvg_criterion_workspace(int L, int B, int Gmax, int V, int J);
 

@@ -67,6 +67,8 @@ SIGNATURES = {
     "mvg_knn_match_workspace": [_i] * 3,
     "mvg_knn_match": [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _f] + [_i] * 5 + [_vp, C.c_size_t] + [_vp] * 5,
     "mvg_knn_match_jm": [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _f] + [_i] * 5 + [_vp, _i, _vp, C.c_size_t] + [_vp] * 5,
+    "mvg_hungarian_match_workspace": [_i] * 3,
+    "mvg_hungarian_match": [_vp] * 4 + [_i, _vp, _vp, _i, _f, _f] + [_i] * 6 + [_vp, _vp, C.c_size_t] + [_vp] * 6,
     "mvg_criterion_workspace": [_i] * 5,
     "mvg_criterion": [_vp] * 10 + [_i] + [_vp] * 4 + [_f] * 3 + [_i] * 7 + [_vp, C.c_size_t] + [_vp] * 5,
     "mvg_criterion_jm": [_vp] * 10 + [_i] + [_vp] * 4 + [_f] * 3 + [_i] * 5 + [_vp] + [_i] * 3 + [_vp, C.c_size_t] + [_vp] * 5,
@@ -116,6 +118,7 @@ def load():
     lib.mvg_msda_backward_det_workspace.restype = C.c_size_t
     lib.mvg_msda_backward_bal_workspace.restype = C.c_size_t
     lib.mvg_knn_match_workspace.restype = C.c_size_t
+    lib.mvg_hungarian_match_workspace.restype = C.c_size_t
     lib.mvg_criterion_workspace.restype = C.c_size_t
     lib.mvg_optim_workspace.restype = C.c_size_t
     lib.mvg_pose_nms_workspace.restype = C.c_size_t

@@ -3,6 +3,8 @@
 per-layer sum of lib/models/dq_transformer.py:653-731) on the fused HIP kernels of csrc/criterion.hip.
 
   KNNMatcher            constructor and forward(outputs, meta) of the reference's matcher; match() is the sync-free form
+  HungarianMatcher      the reference's matcher class in full: methods hungarian / hungarian-dis on mvg_hungarian_match (one
+                        launch, no .cpu(), no scipy), KNN / multiple delegated to mvg_knn_match
   SetCriterion          forward(outputs, meta, outputs_origin=None) -> (loss_dict, indices), the reference's keys
   criterion_all_layers  all decoder layers of a step in one mvg_criterion call: summed dict + dict_losses_layers + loss_init
   total_loss            lib/core/function.py:127-128
@@ -14,8 +16,14 @@ joint_map[j] for converted joint j and write the gradients back in the 15-joint 
 index / index_put launch, the same launch counts as without a map.  SetCriterion.forward is the reference's signature: its
 callers pass already converted tensors, it takes no map.
 
-Not built (no shipped YAML uses them): Hungarian assignment, aux_loss / enc_outputs, per-bone and 3D-projection losses, views
-flagged 'padding'.  They raise; nothing falls back to torch or scipy."""
+Hungarian assignment (DECODER.match_method 'hungarian', the reference's default, and 'hungarian-dis') is built in
+HungarianMatcher / ops.hungarian_match / factory.build_matcher_from_cfg.  It is reached through those names only: KNNMatcher,
+ops.knn_match and build_criterion_from_cfg without a matcher keep refusing the Hungarian methods with NotImplementedError.
+SetCriterion.forward hands the layer's own logits to a matcher that sets `uses_logits`; criterion_all_layers(init_poses=None)
+with a HungarianMatcher matches every layer on its own outputs (gt_match: False) in one matcher launch.
+
+Not built (no shipped YAML uses them): use_ce_match, aux_loss / enc_outputs, per-bone and 3D-projection losses, views flagged
+'padding', match_coord_* other than 'abs' / 'norm'.  They raise; nothing falls back to torch or scipy."""
 from __future__ import annotations
 
 import torch
@@ -62,7 +70,8 @@ class KNNMatcher(nn.Module):
                  method="KNN", method_value=None):
         super().__init__()
         if method in ("hungarian", "hungarian-dis"):
-            raise NotImplementedError("match method %r: the Hungarian assignment is not built (no shipped YAML uses it)" % method)
+            raise NotImplementedError("match method %r: KNNMatcher does not solve the Hungarian assignment "
+                                      "(criterion.HungarianMatcher does)" % method)
         if method not in ops.MATCH_METHODS:
             raise ValueError("unknown match method %r" % (method,))
         if match_coord_est != "abs" or match_coord_gt != "norm":
@@ -89,6 +98,57 @@ class KNNMatcher(nn.Module):
         """the reference's return value: list[B] of (query_idx, gt_idx) int64 tensors, on the device.  Cutting the pair list to
         each element's length needs pair_count on the host: this form synchronises once, match() does not."""
         pq, pg, pc, _ = self.match(outputs["pred_poses"]["outputs_coord"], meta, method, value)
+        return [(pq[b, :n].long(), pg[b, :n].long()) for b, n in enumerate(pc.tolist())]
+
+
+class HungarianMatcher(nn.Module):
+    """The reference's matcher (lib/models/matcher.py HungarianMatcher: class name, constructor signature and defaults) on the
+    device.  Methods 'hungarian' (C = cost_pose * pose + cost_class * class) and 'hungarian-dis' (C = pose) run
+    mvg_hungarian_match: one launch for all batch elements -- and all layers, if the poses carry a leading layer axis --, no
+    .cpu(), no scipy, capturable in a HIP graph.  Methods 'KNN' and 'multiple' delegate to ops.knn_match.  KNNMatcher and
+    ops.knn_match keep refusing the Hungarian methods: this class is the way to them."""
+
+    uses_logits = True                                        # SetCriterion.forward passes the layer's logits to match()
+
+    def __init__(self, match_coord_est="abs", match_coord_gt="norm", cost_class: float = 1, cost_pose: float = 1,
+                 cost_giou: float = 1, method="hungarian", method_value=None):
+        super().__init__()
+        if method not in ops.HUNGARIAN_METHODS and method not in ops.MATCH_METHODS:
+            raise ValueError("unknown match method %r" % (method,))
+        if match_coord_est != "abs" or match_coord_gt != "norm":
+            raise NotImplementedError("match_coord_est %r / match_coord_gt %r (every shipped YAML: 'abs' / 'norm')"
+                                      % (match_coord_est, match_coord_gt))
+        assert cost_class != 0 or cost_pose != 0 or cost_giou != 0, "all costs cant be 0"      # matcher.py:52
+        self.cost_class, self.cost_pose, self.cost_giou = cost_class, cost_pose, cost_giou
+        self.match_coord_est, self.match_coord_gt = match_coord_est, match_coord_gt
+        self.method, self.method_value = method, method_value
+        self.grid_size = self.grid_center = None              # set by SetCriterion, as in the reference
+
+    def match(self, poses, meta, method=None, value=None, joint_map=None, num_joints=None, logits=None):
+        """poses (B, NQ*J, 3) or (Lm, B, NQ*J, 3) abs mm, logits shaped to match or None (= logit 1 for every query) ->
+        (pair_query, pair_gt, pair_count, matched) device tensors, a leading Lm kept; no host synchronisation.  The first
+        arguments and the results are KNNMatcher.match's."""
+        if self.grid_size is None:
+            raise RuntimeError("HungarianMatcher.grid_size / grid_center are not set (SetCriterion sets them)")
+        method = method or self.method
+        size, center = [float(v) for v in self.grid_size], [float(v) for v in self.grid_center]
+        gt, num_person = meta[0]["joints_3d"].float(), meta[0]["num_person"]
+        if method in ops.HUNGARIAN_METHODS:
+            return ops.hungarian_match(poses.float(), gt, num_person, size, center,
+                                       logits=None if logits is None else logits.float(), method=method,
+                                       cost_class=self.cost_class, cost_pose=self.cost_pose, joint_map=joint_map,
+                                       num_joints=num_joints)
+        if poses.dim() != 3:
+            raise ValueError("match method %r takes poses (B, NQ*J, 3)" % (method,))
+        return ops.knn_match(poses.float(), gt, num_person, size, center, method, self.method_value if value is None else value,
+                             joint_map=joint_map, num_joints=num_joints)
+
+    @torch.no_grad()
+    def forward(self, outputs, meta, method=None, value=None):
+        """the reference's return value: list[B] of (query_idx, gt_idx) int64 tensors, on the device, for the Hungarian methods
+        in scipy's order (ascending query).  Cutting the pair list to each element's length needs pair_count on the host: this
+        form synchronises once, match() does not."""
+        pq, pg, pc, _ = self.match(outputs["pred_poses"]["outputs_coord"], meta, method, value, logits=outputs.get("pred_logits"))
         return [(pq[b, :n].long(), pg[b, :n].long()) for b, n in enumerate(pc.tolist())]
 
 
@@ -151,7 +211,10 @@ class SetCriterion(nn.Module):
         if "aux_outputs" in outputs or "enc_outputs" in outputs:
             raise NotImplementedError("aux_outputs / enc_outputs are not built (unused by the reference)")
         src = outputs_origin if outputs_origin else outputs
-        pairs = self.matcher.match(src["pred_poses"]["outputs_coord"].detach(), meta)
+        if getattr(self.matcher, "uses_logits", False):
+            pairs = self.matcher.match(src["pred_poses"]["outputs_coord"].detach(), meta, logits=src["pred_logits"].detach())
+        else:
+            pairs = self.matcher.match(src["pred_poses"]["outputs_coord"].detach(), meta)
         table = self.table(outputs["pred_logits"][None], outputs["pred_poses"]["outputs_coord"][None],
                            outputs["pred_poses_2d"]["outputs_coord_2d"][None], pairs, meta)
         pq, pg, pc = pairs[:3]
@@ -164,11 +227,30 @@ def criterion_all_layers(criterion, logits, poses, poses_2d, meta, init_poses, d
     """The training step's loss dict for gt_match (dq_transformer.py:653-731, loss_for_each_layers): logits (L,B,NQ,2), poses
     (L,B,NQ*J,3), poses_2d (L,B,V,NQ*J,2) of all layers against the match of the initial poses init_poses (B,NQ*J,3) (or the
     pair list `pairs` if the caller matched already).  One matcher launch and three criterion launches, nothing read back.
-    joint_map: the unconverted outputs against a ground truth in another joint format (Shelf / Campus), see the module docstring."""
+    joint_map: the unconverted outputs against a ground truth in another joint format (Shelf / Campus), see the module docstring.
+    init_poses=None (and no pairs) with a HungarianMatcher in a Hungarian method is the reference's gt_match: False
+    (dq_transformer.py:666-678): every layer is matched on its own detached outputs, all L * B problems in ONE matcher launch, and
+    criterion.table runs once per layer with that layer's pairs; `pairs` then comes back with a leading layer axis.  Any other
+    matcher without init_poses raises ValueError."""
+    if pairs is None and init_poses is None:
+        m = criterion.matcher
+        if not (isinstance(m, HungarianMatcher) and m.method in ops.HUNGARIAN_METHODS):
+            raise ValueError("criterion_all_layers: init_poses=None (per-layer matching) needs a HungarianMatcher in a Hungarian "
+                             "method, got %s" % type(m).__name__)
+        pairs = m.match(poses.detach(), meta, joint_map=joint_map,
+                        num_joints=None if joint_map is None else poses.shape[2] // logits.shape[2], logits=logits.detach())
+        table = torch.cat([criterion.table(logits[l:l + 1], poses[l:l + 1], poses_2d[l:l + 1], tuple(t[l] for t in pairs), meta,
+                                           cams, joint_map) for l in range(logits.shape[0])])
+        return _layers_dict(table, decay_method), pairs
     if pairs is None:
         pairs = criterion.matcher.match(init_poses.detach(), meta, joint_map=joint_map,
                                         num_joints=None if joint_map is None else poses.shape[2] // logits.shape[2])
     table = criterion.table(logits, poses, poses_2d, pairs, meta, cams, joint_map)
+    return _layers_dict(table, decay_method), pairs
+
+
+def _layers_dict(table, decay_method):
+    """the step's loss dict from the (L, 8) table: weighted sums, mean metrics, the per-layer dicts, loss_init"""
     Ln = table.shape[0]
     w = layer_weights(decay_method, Ln, table.device)
     loss_dict = {}
@@ -176,4 +258,4 @@ def criterion_all_layers(criterion, logits, poses, poses_2d, meta, init_poses, d
         loss_dict[k] = table[:, i].mean() if k in METRIC_KEYS else (w * table[:, i]).sum()
     loss_dict["dict_losses_layers"] = [SetCriterion.row_to_dict(table[l]) for l in range(Ln)]
     loss_dict["loss_init"] = torch.zeros((1,), dtype=torch.float32, device=table.device)
-    return loss_dict, pairs
+    return loss_dict

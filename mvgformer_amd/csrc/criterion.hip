@@ -17,8 +17,9 @@
 #include <math.h>
 
 #include "common.h"
+#include "match_dev.h"
 
-#define CRIT_THREADS 256
+#define CRIT_THREADS MATCH_THREADS
 #define CRIT_WAVES (CRIT_THREADS / MVG_WAVE)
 #define KNN_LDS_COSTS 10240    // NQ x G fp32 costs kept in LDS up to 1024 x 10 (40 KB); a caller workspace beyond
 #define CRIT_MAX_NQ 4096       // int16 chains in LDS
@@ -26,27 +27,10 @@
 #define CRIT_MAX_B 256
 #define CRIT_PART 8            // doubles per (layer, batch element) partial record
 
-struct SpaceBox {
-  float size[3], center[3];
-};
-struct JointMap {
-  uint8_t m[64];               // m[j] = prediction joint of converted joint j, j < Jc
-};
-
-// absolute -> norm -> absolute exactly as matcher.py:65-78 rounds it in fp32 (no contraction into FMAs)
-__device__ __forceinline__ float norm_round_trip_f32(float x, float size, float center) {
-  const float half = __fdiv_rn(size, 2.0f);
-  const float n = __fdiv_rn(__fadd_rn(__fsub_rn(x, center), half), size);
-  return __fsub_rn(__fadd_rn(__fmul_rn(n, size), center), half);
-}
 // the same chain for the criterion's targets, in fp64
 __device__ __forceinline__ double norm_round_trip_f64(double x, double size, double center) {
   const double n = (x - center + size / 2.0) / size;
   return n * size + center - size / 2.0;
-}
-
-__device__ __forceinline__ long load_count(const void* p, int is64, int i) {
-  return is64 ? (long)((const int64_t*)p)[i] : (long)((const int32_t*)p)[i];
 }
 
 // lexicographic (cost, index) minimum over the 64 lanes of a wavefront; every lane gets the result
@@ -97,27 +81,7 @@ __global__ __launch_bounds__(CRIT_THREADS) void knn_match_kernel(const float* __
     pq[p] = -1;
     pg[p] = -1;
   }
-  // the round-tripped ground truth of one person at a time in LDS (3J <= 192 floats): G * 3J round trips, not NQ * G * 3J
-  for (int g = 0; g < G; ++g) {
-    __syncthreads();
-    for (int e = tid; e < J * 3; e += CRIT_THREADS)
-      gt_lds[e] = norm_round_trip_f32(gb[(long)g * J * 3 + e], box.size[e % 3], box.center[e % 3]);
-    __syncthreads();
-    for (int q = tid; q < NQ; q += CRIT_THREADS) {
-      const float* x = pb + (long)q * (MAPPED ? Jp : J) * 3;
-      float s = 0.f;
-      if (MAPPED) {
-        for (int j = 0; j < J; ++j) {
-          const float* xj = x + s_map3[j];
-          for (int c = 0; c < 3; ++c) s += fabsf(xj[c] - gt_lds[j * 3 + c]);
-        }
-      } else {
-        for (int e = 0; e < J * 3; ++e) s += fabsf(x[e] - gt_lds[e]);
-      }
-      s *= 0.01f;
-      cost[(long)g * NQ + q] = (s < INFINITY) ? s : INFINITY;    // NaN / inf poses sort last
-    }
-  }
+  match_pose_costs<MAPPED>(pb, gb, box, NQ, G, J, Jp, s_map3, gt_lds, cost);     // match_dev.h
   __syncthreads();
 
   if (method == MVG_MATCH_KNN) {
@@ -455,21 +419,6 @@ __global__ __launch_bounds__(CRIT_THREADS) void crit_final_kernel(const double* 
     t[6] = keep ? l2d : l2d * 0.0f;
     t[7] = keep ? 1.f : 0.f;
   }
-}
-
-// joint_map (Jc HOST ints, distinct, inside [0, Jp)) -> the by-value table; NULL = the identity, Jc == Jp.  0 on a bad map.
-static int pack_joint_map(int Jp, int Jc, const int* joint_map, JointMap* out) {
-  if (Jp < 1 || Jp > 64 || Jc < 1 || Jc > 64) return 0;
-  for (int j = 0; j < 64; ++j) out->m[j] = 0;
-  if (!joint_map) return Jc == Jp;
-  bool seen[64] = {};
-  for (int j = 0; j < Jc; ++j) {
-    const int m = joint_map[j];
-    if (m < 0 || m >= Jp || seen[m]) return 0;
-    seen[m] = true;
-    out->m[j] = (uint8_t)m;
-  }
-  return 1;
 }
 
 extern "C" {

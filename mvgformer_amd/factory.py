@@ -69,22 +69,37 @@ def build_weight_dict(cfg):
             "loss_pose_perprojection_2d": d.loss_pose_perprojection_2d, "loss_init": d.loss_weight_init}
 
 
-def build_criterion_from_cfg(cfg):
+def build_matcher_from_cfg(cfg):
+    """criterion.HungarianMatcher -- the reference's matcher class in full, on the device -- from the DECODER keys with the cost
+    weights of multi_view_pose_transformer.py:217-247 (cost_class 2, cost_pose 5).  Missing keys take the reference's defaults
+    (lib/core/config.py:306-318): a bare cfg gives match_method 'hungarian'.  Hand the result to build_criterion_from_cfg /
+    build_training_head as `matcher`; without one they build a KNNMatcher, which refuses the Hungarian methods."""
+    from .criterion import HungarianMatcher
+    d = getattr(cfg, "DECODER", None)
+    return HungarianMatcher(getattr(d, "match_coord_est", "abs"), getattr(d, "match_coord_gt", "norm"), cost_class=2., cost_pose=5.,
+                            method=getattr(d, "match_method", "hungarian"), method_value=getattr(d, "match_method_value", 5))
+
+
+def build_criterion_from_cfg(cfg, matcher=None):
     """matcher + criterion + weight_dict from the DECODER keys, as multi_view_pose_transformer.py:217-247 builds them
     (cost_class 2, cost_pose 5, focal alpha 0.25, losses joints / labels / cardinality).  Keys a hand-made cfg lacks take the
-    defaults of lib/core/config.py.  Returns (criterion, weight_dict, decay_method)."""
+    defaults of lib/core/config.py.  matcher: the matcher to use (build_matcher_from_cfg's HungarianMatcher for the Hungarian
+    methods); None builds a KNNMatcher from the cfg, which raises NotImplementedError for match_method 'hungarian' /
+    'hungarian-dis'.  Returns (criterion, weight_dict, decay_method)."""
     from .criterion import KNNMatcher, SetCriterion
     d = SimpleNamespace(**{**_CRITERION_DEFAULTS, **vars(cfg.DECODER)})
     full = SimpleNamespace(DECODER=d, NETWORK=cfg.NETWORK, MULTI_PERSON=cfg.MULTI_PERSON)
-    matcher = KNNMatcher(d.match_coord_est, d.match_coord_gt, cost_class=2., cost_pose=5., method=d.match_method,
-                         method_value=d.match_method_value)
+    if matcher is None:
+        matcher = KNNMatcher(d.match_coord_est, d.match_coord_gt, cost_class=2., cost_pose=5., method=d.match_method,
+                             method_value=d.match_method_value)
     weight_dict = build_weight_dict(full)
     criterion = SetCriterion(2, matcher, weight_dict, ["joints", "labels", "cardinality"], full, focal_alpha=0.25)
     return criterion, weight_dict, d.decay_method
 
 
-def build_training_head(cfg, decoder=None, t_pose=None):
+def build_training_head(cfg, decoder=None, t_pose=None, matcher=None):
     """caller.DecoderHead around the cfg's decoder with the cfg's criterion set: forward_train is ready.  Returns (head, weight_dict).
+    matcher: handed to build_criterion_from_cfg (build_matcher_from_cfg(cfg) for the Hungarian methods).
     DECODER.convert_joint_format_indices (the shelf_campus YAMLs) becomes the head's joint map: forward_train then takes ground
     truth with that many joints."""
     from .caller import DecoderHead
@@ -93,7 +108,7 @@ def build_training_head(cfg, decoder=None, t_pose=None):
     conv = getattr(d, "convert_joint_format_indices", None)
     head = DecoderHead(decoder, d.num_instance, d.num_keypoints, d.d_model, cfg.MULTI_PERSON.SPACE_SIZE, cfg.MULTI_PERSON.SPACE_CENTER,
                        convert_joint_format_indices=None if conv is None else [int(i) for i in conv], t_pose=t_pose)
-    criterion, weight_dict, decay = build_criterion_from_cfg(cfg)
+    criterion, weight_dict, decay = build_criterion_from_cfg(cfg, matcher=matcher)
     head.set_criterion(criterion, decay)
     return head, weight_dict
 

@@ -1052,7 +1052,8 @@ def knn_match(poses, joints_3d, num_person, space_size, space_center, method="KN
     joint_map[j]; poses then are (B, NQ*Jp, 3) with Jp = num_joints (poses alone do not tell NQ from Jp) and joints_3d
     (B, Gmax, Jc, 3).  Still one launch; the map is a launch argument."""
     if method in ("hungarian", "hungarian-dis"):
-        raise NotImplementedError("match method %r: the Hungarian assignment is not built (no shipped YAML uses it)" % method)
+        raise NotImplementedError("match method %r: knn_match does not solve the Hungarian assignment (ops.hungarian_match "
+                                  "does)" % method)
     if method not in MATCH_METHODS:
         raise ValueError("unknown match method %r" % (method,))
     jm = _joint_map_arg(joint_map, num_joints, joints_3d, "mvg_knn_match_jm")
@@ -1088,6 +1089,64 @@ def knn_match(poses, joints_3d, num_person, space_size, space_center, method="KN
                                          _host3(space_center), MATCH_METHODS[method], K, float(value), B, NQ, Gmax, Jp, J, jm, Pmax,
                                          L.ptr(ws), nbytes, L.ptr(pq), L.ptr(pg), L.ptr(pc), L.ptr(matched), L.stream_ptr()),
                     "mvg_knn_match_jm")
+    return pq, pg, pc, matched
+
+
+HUNGARIAN_METHODS = {"hungarian": 2, "hungarian-dis": 3}       # MVG_MATCH_HUNGARIAN, MVG_MATCH_HUNGARIAN_DIS
+HUNGARIAN_MAX_G, HUNGARIAN_MAX_NQ = 64, 4096
+
+
+def hungarian_match(poses, joints_3d, num_person, space_size, space_center, logits=None, method="hungarian", cost_class=1.0,
+                    cost_pose=1.0, joint_map=None, num_joints=None, duals=False):
+    """The reference's one-to-one matcher (methods 'hungarian' / 'hungarian-dis') on the device: mvg_hungarian_match, ONE launch
+    for all problems, nothing read back, no scipy.  poses (B, NQ*J, 3) or (Lm, B, NQ*J, 3) abs mm -- Lm sets of predictions (the
+    decoder layers) matched against the same ground truth in the same launch --, logits (B, NQ, 2) / (Lm, B, NQ, 2) or None
+    (= logit 1 everywhere), joints_3d (B, Gmax, J, 3), num_person (B,).  C = cost_pose * pose + cost_class * class for
+    'hungarian', C = pose for 'hungarian-dis' (logits ignored).
+    -> pair_query, pair_gt (B, Gmax) int32: the num_person pairs in ascending query order, -1 behind them; pair_count (B,) int32;
+    matched (B, NQ) uint8; with duals=True also the solver's potentials u (B, Gmax), v (B, NQ) fp64.  A leading Lm is kept.
+    joint_map / num_joints as for knn_match.  The methods 'KNN' and 'multiple' are ops.knn_match; ops.knn_match keeps refusing
+    the Hungarian names."""
+    if method not in HUNGARIAN_METHODS:
+        raise ValueError("unknown Hungarian match method %r (hungarian | hungarian-dis)" % (method,))
+    jm = _joint_map_arg(joint_map, num_joints, joints_3d, "mvg_hungarian_match")
+    L.require_cuda(poses, joints_3d, num_person, logits)
+    lead = poses.dim() == 4
+    if poses.dtype != torch.float32 or joints_3d.dtype != torch.float32 or joints_3d.dim() != 4 or joints_3d.shape[-1] != 3 \
+            or poses.dim() not in (3, 4) or poses.shape[-1] != 3 or poses.shape[-3] != joints_3d.shape[0]:
+        raise RuntimeError("mvg_hungarian_match: poses ([Lm,] B, NQ*J, 3) / joints_3d (B, Gmax, J, 3) float32 expected")
+    B, Gmax, J = joints_3d.shape[:3]
+    Lm = poses.shape[0] if lead else 1
+    Jp = J if jm is None else int(num_joints)
+    if poses.shape[-2] % Jp:
+        raise RuntimeError("mvg_hungarian_match: poses rows (%d) are not a multiple of J = %d" % (poses.shape[-2], Jp))
+    NQ = poses.shape[-2] // Jp
+    if logits is not None and (logits.dtype != torch.float32 or tuple(logits.shape) != tuple(poses.shape[:-2]) + (NQ, 2)):
+        raise RuntimeError("mvg_hungarian_match: logits %s float32 expected" % (tuple(poses.shape[:-2]) + (NQ, 2),))
+    if Gmax > HUNGARIAN_MAX_G or NQ > HUNGARIAN_MAX_NQ or NQ < Gmax:
+        raise RuntimeError("mvg_hungarian_match: Gmax <= %d, Gmax <= NQ <= %d expected, got Gmax = %d, NQ = %d"
+                           % (HUNGARIAN_MAX_G, HUNGARIAN_MAX_NQ, Gmax, NQ))
+    num_person, is64 = _count_tensor(num_person, B)
+    poses, joints_3d = poses.detach().contiguous(), joints_3d.contiguous()
+    logits = None if logits is None else logits.detach().contiguous()
+    P = Lm * B
+    lib = L.load()
+    dev = poses.device
+    head = (Lm, B) if lead else (B,)
+    pq = torch.empty(head + (Gmax,), dtype=torch.int32, device=dev)
+    pg = torch.empty(head + (Gmax,), dtype=torch.int32, device=dev)
+    pc = torch.empty(head, dtype=torch.int32, device=dev)
+    matched = torch.empty(head + (NQ,), dtype=torch.uint8, device=dev)
+    uv = torch.empty(head + (Gmax + NQ,), dtype=torch.float64, device=dev) if duals else None
+    nbytes = lib.mvg_hungarian_match_workspace(P, NQ, Gmax)
+    ws = torch.empty(((nbytes + 3) // 4,), dtype=torch.float32, device=dev) if nbytes else None
+    with _timed("hungarian_match"):
+        L.check(lib.mvg_hungarian_match(L.ptr(logits), L.ptr(poses), L.ptr(joints_3d), L.ptr(num_person), is64, _host3(space_size),
+                                        _host3(space_center), HUNGARIAN_METHODS[method], float(cost_class), float(cost_pose), P, B,
+                                        NQ, Gmax, Jp, J, jm, L.ptr(ws), nbytes, L.ptr(pq), L.ptr(pg), L.ptr(pc), L.ptr(matched),
+                                        L.ptr(uv), L.stream_ptr()), "mvg_hungarian_match")
+    if duals:
+        return pq, pg, pc, matched, uv[..., :Gmax], uv[..., Gmax:]
     return pq, pg, pc, matched
 
 

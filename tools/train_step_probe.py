@@ -1,13 +1,16 @@
 """Time of one training step of the decoder at cfg-2 size: forward under autograd (torch geometry +
 ProjAttn with the HIP sampling forward / backward kernels) + backward to every parameter.  GPU only.
 python tools/train_step_probe.py [config] [steps] [fp32|bf16] [--criterion] [--optimizer fused|torch] [--graph]
-                                 [--backward det|balanced] [--chunk c] [--shelf]
+                                 [--backward det|balanced] [--chunk c] [--shelf] [--match knn|hungarian]
 (bf16: DQDecoder.set_training_dtype(torch.bfloat16))
 --criterion: the real step -- DecoderHead.forward_train (ground-truth match, decoder with the matched mask, fused criterion) on
 synthetic ground truth (5 persons, K = 5) and total_loss(...).backward() -- instead of the made-up loss of the default run.
 --shelf (with --criterion): the step in the Shelf / Campus joint format -- the head carries the shelf_campus YAMLs'
 convert_joint_format_indices, the ground truth is the synthetic 15-joint persons gathered with that map (14 joints), matcher and
 criterion run through their joint-map entry points.
+--match (with --criterion): knn (default) -- KNNMatcher with K = 5 -- or hungarian -- factory.build_matcher_from_cfg's
+HungarianMatcher, the reference's default match_method: one query per person on the device (mvg_hungarian_match), so the decoder
+triangulates 5 queries per batch element, not 25.
 --optimizer: the step includes the weight update (lr 4e-4, clip 0.1, the reference's two parameter groups).  torch: `if loss > 0`
 on the host, clip_grad_norm_ and torch.optim.Adam, gradients zeroed in place; fused: optim.FusedAdam.step(loss=loss), the guard
 on the device.  Without the option the step ends at backward() and drops the gradients, as before.
@@ -41,6 +44,13 @@ if "--optimizer" in argv:
     optimizer = argv[i + 1] if i + 1 < len(argv) else ""
     if optimizer not in ("fused", "torch"):
         raise SystemExit("--optimizer fused|torch")
+    del argv[i:i + 2]
+match = "knn"
+if "--match" in argv:
+    i = argv.index("--match")
+    match = argv[i + 1] if i + 1 < len(argv) else ""
+    if match not in ("knn", "hungarian") or not with_criterion:
+        raise SystemExit("--match knn|hungarian (with --criterion)")
     del argv[i:i + 2]
 backward = chunk = None
 if "--backward" in argv:
@@ -79,14 +89,14 @@ head = weight_dict = None
 if with_criterion:
     from types import SimpleNamespace as NS
     from mvgformer_amd.caller import DecoderHead, total_loss
-    from mvgformer_amd.factory import build_criterion_from_cfg
+    from mvgformer_amd.factory import build_criterion_from_cfg, build_matcher_from_cfg
     from mvgformer_amd.synthetic import add_ground_truth, convert_ground_truth
     add_ground_truth(g, 5, Gmax=10, seed=0)
     if with_shelf:
         convert_ground_truth(g, SHELF_MAP)
-    ccfg = NS(DECODER=NS(match_method="KNN", match_method_value=5), NETWORK=NS(IMAGE_SIZE=list(case.img_size)),
+    ccfg = NS(DECODER=NS(match_method="KNN" if match == "knn" else "hungarian", match_method_value=5), NETWORK=NS(IMAGE_SIZE=list(case.img_size)),
               MULTI_PERSON=NS(SPACE_SIZE=list(case.space_size), SPACE_CENTER=list(case.space_center)))
-    criterion, weight_dict, decay = build_criterion_from_cfg(ccfg)
+    criterion, weight_dict, decay = build_criterion_from_cfg(ccfg, matcher=None if match == "knn" else build_matcher_from_cfg(ccfg))
     head = DecoderHead(dec, case.NQ, 15, 256, case.space_size, case.space_center,
                        convert_joint_format_indices=SHELF_MAP if with_shelf else None).to("cuda").set_criterion(criterion, decay)
     head.train()
@@ -178,10 +188,10 @@ def graph_run():
     reduce = [(n, t) for name, (n, t) in by_name.items() if "bw_reduce" in name]
     print("bw_reduce* kernels of that step (backward mode %s): %.3f ms in %d launches"
           % (ops.BACKWARD_MODE + ("" if ops.BACKWARD_CHUNK is None else ", chunk %d" % ops.BACKWARD_CHUNK), sum(t for _, t in reduce) / 1e3, sum(n for n, _ in reduce)))
-    print("%s training step (%s, match + criterion%s + fused optimizer): plain step %.2f ms (context per call; median of %d in a block); "
+    print(("%s training step (%s, " + match + " match + criterion%s + fused optimizer): plain step %.2f ms (context per call; median of %d in a block); "
           "runner.eager() %.2f ms (static context, operands kept by the device), graph replay %.2f ms (medians of %d, alternating; "
           "min %.2f / %.2f); %d device launches per runner.eager() step, 1 graph launch per replay; loss %.4f; peak memory %.2f GB "
-          "plain, %.2f GB with the graph's pool" % (cfg, tdt, " in the Shelf joint format" if with_shelf else "", statistics.median(tp), steps, statistics.median(te), statistics.median(tr),
+          "plain, %.2f GB with the graph's pool") % (cfg, tdt, " in the Shelf joint format" if with_shelf else "", statistics.median(tp), steps, statistics.median(te), statistics.median(tr),
                                                    steps, min(te), min(tr), launches, float(total), peak_eager, peak_all))
 
 
