@@ -802,6 +802,55 @@ int mvg_track_predict(int B, int T, int J, const int* id, float* pose, double* m
 int mvg_track_correct(int B, int R, int T, int J, const int* id, const int* hits, const int* misses, const int* slots, float* pose,
                       double* mean, double* var, double r, double v0, float* row_pose, void* stream);
 
+#define MVG_TRACK_EVAL_MAX_P 64       /* identities per stream: the rows of the remaining-pairs solve and of the overlap table  */
+#define MVG_TRACK_EVAL_MAX_K 4096     /* columns of the overlap table: track ids below this are counted                        */
+#define MVG_TRACK_EVAL_WORDS 13       /* int64 counters per stream: frames, gt, hyp, matches, misses, false_pos, switches, kept,
+                                       * dropped, unreported, bad_id, id_overflow, reserved (always 0)                          */
+
+/* CLEAR-MOT counts and the identity overlap table of one frame of the tracker's output against ground truth, for B independent
+ * streams in ONE launch (one workgroup per stream) behind mvg_track_update (or mvg_track_correct), fixed shapes, nothing read
+ * back, NO atomics: every element of the state has one writer, the stream's own workgroup, so the bits cannot depend on the order
+ * of the workgroups; capturable in a HIP graph.
+ *   dets (B, R, J, 5) fp32 and count (B, 2) int32 or NULL as mvg_pose_nms leaves them; ids (B, R) int32, the tracker's per-row
+ *   ids; row_pose (B, R, J, 3) fp32 or NULL: when given, a hypothesis' pose is taken from here (the motion model's filtered
+ *   poses) instead of dets.  Ground truth in the evaluator's layout: joints_3d (B, G, J, 3) fp32, joints_3d_vis (B, G, J) fp32
+ *   (visible when > 0), num_person (B) int32; person_id (B, G) int32 or NULL (the identity of person slot g is g).
+ *   State, owned by the caller, P identities per stream (G <= P <= MVG_TRACK_EVAL_MAX_P), K columns: last_track (B, P) int32
+ *   (-1 at the start), counters (B, MVG_TRACK_EVAL_WORDS) int64, dist_sum (B) fp64, seen, covered (B, P) int64, overlap (B, P, K)
+ *   int32, all 0 at the start.
+ * Per stream b:
+ *   1. Frame skipping.  num_person[b] < 0: the frame has no annotation, nothing is counted or changed.  num_person[b] == 0 is an
+ *      annotated empty frame (every hypothesis is a false positive).
+ *   2. Hypotheses: the rows i < count[b, 0] (clamped to [0, R]; all R rows when count is NULL) with dets[b, i, 0, 3] >= 0 AND
+ *      ids[b, i] >= 0, in row order, the first MVG_TRACK_MAX_D; later ones are counted in `dropped`.  Detection rows (flag >= 0,
+ *      in front of the count) with ids < 0 are no hypotheses and are counted in `unreported`.  The ids of a stream's hypotheses
+ *      are expected to be distinct, as mvg_track_update's are; with equal ids one of the concurrent += 1 on the same overlap
+ *      entry in 9 may be lost, nothing else is affected.
+ *   3. Persons: the slots g < min(num_person[b], G) with at least one visible joint, in slot order, identity p = person_id[b, g]
+ *      (or g).  A person whose p is outside [0, P), or equal to the p of a person in a lower slot, is counted in `bad_id` and
+ *      ignored.
+ *   4. d[person, hypothesis] = (sum over the person's VISIBLE joints in joint order of sqrt((dx*dx + dy*dy) + dz*dz)) / (the
+ *      number of visible joints), fp64 from the fp32 inputs, every operation rounded on its own, correctly rounded sqrt.  A NaN
+ *      distance is no match (d <= dist_thr is false).
+ *   5. Kept correspondences, persons in slot order: with h the first hypothesis in row order whose id is last_track[b, p]
+ *      (last_track >= 0): if no earlier person has kept h and d[person, h] <= dist_thr the pair is matched, whatever the optimum
+ *      of 6 would pair, and counted in `kept`.
+ *   6. The remaining persons (slot order) x the remaining hypotheses (row order): the solver of mvg_linear_assignment on
+ *      c' = d if d <= dist_thr else dist_thr (also for NaN); an assigned pair is a match iff its ungated d <= dist_thr.
+ *   7. For each person in slot order: seen[b, p] += 1.  Matched with the hypothesis of id t: matches += 1, dist_sum[b] =
+ *      dist_sum[b] + d (one add per match, in this order), covered[b, p] += 1; if last_track[b, p] >= 0 and != t: switches += 1;
+ *      last_track[b, p] = t.  Not matched: misses += 1, last_track stays (a person who comes back under another id is one switch).
+ *   8. false_pos += the unmatched hypotheses; gt += the persons, hyp += the hypotheses, frames += 1.
+ *   9. For every (person, hypothesis) pair with d <= dist_thr, matched or not, t the hypothesis' id: overlap[b, p, t] += 1 when
+ *      t < K, otherwise id_overflow += 1.
+ * MVG_E_BADARG, and nothing launched, for B, R or J < 1 or above their MVG_TRACK_MAX_*, G < 1, P < G or > MVG_TRACK_EVAL_MAX_P,
+ * K < 1 or > MVG_TRACK_EVAL_MAX_K, dist_thr < 0, NaN or > MVG_LAP_BIG, a NULL pointer other than count, row_pose and person_id, a
+ * counters, dist_sum, seen or covered pointer that is not 8-byte aligned. */
+int mvg_track_eval(const float* dets, const int* count, const int* ids, const float* row_pose, const float* joints_3d,
+                   const float* joints_3d_vis, const int* num_person, const int* person_id, int B, int R, int J, int G, int P, int K,
+                   double dist_thr, int* last_track, int64_t* counters, double* dist_sum, int64_t* seen, int64_t* covered,
+                   int* overlap, void* stream);
+
 /* ---- structural triangulation: fixed bone lengths (csrc/structural.hip) ------------------------------------------------------- */
 #define MVG_ST_MAX_J 17               /* joints of a tree: the reduced system has 3 (J - 1) <= 48 rows, a lane each             */
 #define MVG_ST_MAX_V 32

@@ -88,6 +88,7 @@ SIGNATURES = {
     "mvg_track_update": [_vp] * 2 + [_i] * 4 + [_vp] * 8 + [C.c_double, _i, _i] + [_vp] * 3,
     "mvg_track_predict": [_i] * 3 + [_vp] * 4 + [C.c_double] * 2 + [_vp],
     "mvg_track_correct": [_i] * 4 + [_vp] * 7 + [C.c_double] * 2 + [_vp] * 2,
+    "mvg_track_eval": [_vp] * 8 + [_i] * 6 + [C.c_double] + [_vp] * 7,
     "mvg_structural_triangulate": [_vp] * 5 + [_i] + [_vp] * 3 + [_i] * 3 + [_vp] * 2 + [_i] * 5 + [_vp],
 }
 

@@ -15,6 +15,10 @@
 //   mvg_track_predict,      the optional constant-velocity motion model, 1 launch each around the unchanged update, one workgroup
 //   mvg_track_correct       per stream: a Kalman filter per track (position and velocity per joint and axis, one 2 x 2 covariance
 //                           per track); the update then associates against predicted poses.  No LDS, no atomics.
+//   mvg_track_eval          the scoring of the ids against ground truth, 1 launch behind the tracker, one workgroup per stream: the
+//                           same compaction, the person x hypothesis distances into the same LDS tile, the kept correspondences of
+//                           CLEAR-MOT (a lane per person), the rest on the same solve, counters and the identity overlap table for
+//                           IDF1.  Every element of its state has one writer: no atomics.
 //
 // The solver is the shortest-augmenting-path Hungarian algorithm with potentials, rows inserted in order, stated so that a host
 // restatement gives the same bits (include/mvg_decoder.h): the per-column operations of a step are independent and are executed
@@ -437,6 +441,243 @@ __global__ __launch_bounds__(TRACK_THREADS) void track_correct_kernel(int R, int
   }
 }
 
+// ------------------------------------------------------------------------------------------------------------------------------
+// CLEAR-MOT counts and the identity overlap table of one frame (mvg_track_eval, the rules of include/mvg_decoder.h).  One workgroup
+// per stream; every element of the state is written by that workgroup alone, with plain loads and stores: no atomics.
+enum { TE_FRAMES = 0, TE_GT, TE_HYP, TE_MATCHES, TE_MISSES, TE_FALSE_POS, TE_SWITCHES, TE_KEPT, TE_DROPPED, TE_UNREPORTED, TE_BAD_ID,
+       TE_ID_OVERFLOW, TE_RESERVED };
+#define TE_GATHER (LAP_N * LAP_N / TRACK_THREADS)      // entries of the distance tile per thread
+
+static_assert(MVG_TRACK_EVAL_WORDS == TE_RESERVED + 1, "the counters of include/mvg_decoder.h");
+static_assert(MVG_TRACK_EVAL_MAX_P == LAP_N, "persons are the solver's rows");
+static_assert(TE_GATHER * TRACK_THREADS == LAP_N * LAP_N, "the tile is compacted through TE_GATHER registers per thread");
+
+// track_dist with every product rounded on its own (track_mul): the distances are summed into dist_sum, which is compared bit for bit
+static __device__ __forceinline__ double track_eval_dist(const float* p, const float* g) {
+  const double dx = (double)p[0] - (double)g[0], dy = (double)p[1] - (double)g[1], dz = (double)p[2] - (double)g[2];
+  return __builtin_sqrt((track_mul(dx, dx) + track_mul(dy, dy)) + track_mul(dz, dz));
+}
+
+__global__ __launch_bounds__(TRACK_THREADS) void track_eval_kernel(const float* __restrict__ dets, const int* __restrict__ count,
+                                                                   const int* __restrict__ ids, const float* __restrict__ row_pose,
+                                                                   const float* __restrict__ joints_3d, const float* __restrict__ vis,
+                                                                   const int* __restrict__ num_person,
+                                                                   const int* __restrict__ person_id, int R, int J, int G, int P,
+                                                                   int K, double thr, int* __restrict__ last_track,
+                                                                   i64* __restrict__ counters, double* __restrict__ dist_sum,
+                                                                   i64* __restrict__ seen, i64* __restrict__ covered,
+                                                                   int* __restrict__ overlap) {
+  __shared__ double s_d[LAP_N * LAP_N];        // d[person a, hypothesis h]; from step 6 on: the remaining pairs, compacted
+  __shared__ double s_pd[LAP_N];               // distance of person a's match
+  __shared__ int s_scan[2][2][TRACK_THREADS];  // [hypotheses, unreported rows]
+  __shared__ int s_row[LAP_N], s_hid[LAP_N];   // row and id of hypothesis h
+  __shared__ int s_slot[LAP_N], s_pid[LAP_N];  // slot and identity of person a
+  __shared__ int s_ph[LAP_N];                  // hypothesis matched to person a, or -1
+  __shared__ int s_taken[LAP_N];               // hypothesis h is matched
+  __shared__ int s_rp[LAP_N], s_rh[LAP_N];     // the remaining persons / hypotheses
+  __shared__ int s_col[LAP_N];
+  __shared__ int s_np, s_bad, s_nrp, s_nrh;
+  const int b = blockIdx.x, t = threadIdx.x;
+  const int annotated = num_person[b];
+  if (annotated < 0) return;                   // the whole workgroup: a frame without annotation
+
+  // hypotheses: the detection rows that carry an id, in row order (the scan of track_update_kernel, two counts at once)
+  const int rows = count == nullptr ? R : track_clamp(count[2 * b], R);
+  const int chunk = (R + TRACK_THREADS - 1) / TRACK_THREADS;
+  const int lo = min(t * chunk, R), hi = min(lo + chunk, R);
+  int mine = 0, mine_u = 0;
+  for (int i = lo; i < hi; ++i)
+    if (track_is_det(dets, count, b, i, R, J, rows)) {
+      if (ids[(size_t)b * R + i] >= 0) ++mine;
+      else ++mine_u;
+    }
+  s_scan[0][0][t] = mine;
+  s_scan[0][1][t] = mine_u;
+  __syncthreads();
+  int src = 0;
+  for (int step = 1; step < TRACK_THREADS; step <<= 1) {
+    s_scan[src ^ 1][0][t] = s_scan[src][0][t] + (t >= step ? s_scan[src][0][t - step] : 0);
+    s_scan[src ^ 1][1][t] = s_scan[src][1][t] + (t >= step ? s_scan[src][1][t - step] : 0);
+    src ^= 1;
+    __syncthreads();
+  }
+  const int nh_all = s_scan[src][0][TRACK_THREADS - 1], unreported = s_scan[src][1][TRACK_THREADS - 1];
+  const int nh = min(nh_all, MVG_TRACK_MAX_D);
+  {
+    int pos = s_scan[src][0][t] - mine;
+    for (int i = lo; i < hi && pos < MVG_TRACK_MAX_D; ++i)
+      if (track_is_det(dets, count, b, i, R, J, rows) && ids[(size_t)b * R + i] >= 0) {
+        s_row[pos] = i;
+        s_hid[pos++] = ids[(size_t)b * R + i];
+      }
+  }
+  // persons: a lane per slot; an identity out of range or already taken by a lower slot is a bad id
+  if (t < LAP_N) {
+    bool live = false;
+    int p = -1;
+    if (t < min(annotated, G)) {
+      const float* w = vis + ((size_t)b * G + t) * J;
+      for (int j = 0; j < J; ++j) live = live || w[j] > 0.f;
+      p = person_id == nullptr ? t : person_id[(size_t)b * G + t];
+    }
+    const int pin = (live && p >= 0 && p < P) ? p : -1;
+    bool twice = false;
+    for (int k = 0; k < LAP_N; ++k) {
+      const int pk = lap_lane(pin, k);
+      twice = twice || (k < t && pk >= 0 && pk == pin);
+    }
+    const bool ok = pin >= 0 && !twice;
+    const u64 ok_mask = __ballot(ok), bad_mask = __ballot(live && !ok);
+    if (ok) {
+      const int a = __popcll(ok_mask & ((1ull << t) - 1ull));
+      s_slot[a] = t;
+      s_pid[a] = pin;
+    }
+    s_ph[t] = -1;
+    s_taken[t] = 0;
+    if (t == 0) {
+      s_np = __popcll(ok_mask);
+      s_bad = __popcll(bad_mask);
+    }
+  }
+  __syncthreads();
+  const int np = s_np;
+
+  const int hs = row_pose == nullptr ? 5 : 3;                                   // floats per joint of a hypothesis' pose
+  const float* hyp = row_pose == nullptr ? dets + (size_t)b * R * J * 5 : row_pose + (size_t)b * R * J * 3;
+  for (int e = t; e < np * nh; e += TRACK_THREADS) {
+    const int a = e / nh, h = e % nh;
+    const float* x = hyp + (size_t)s_row[h] * J * hs;
+    const float* g = joints_3d + ((size_t)b * G + s_slot[a]) * J * 3;
+    const float* w = vis + ((size_t)b * G + s_slot[a]) * J;
+    double sum = 0.0;
+    int n = 0;
+    for (int j = 0; j < J; ++j)
+      if (w[j] > 0.f) {
+        sum += track_eval_dist(x + j * hs, g + j * 3);
+        ++n;
+      }
+    s_d[a * LAP_N + h] = sum / (double)n;                                       // n >= 1: a person has a visible joint
+  }
+  __syncthreads();
+
+  // step 5 on wavefront 0, a lane per person: the hypothesis that carries the person's last id; among the persons that could keep
+  // the same hypothesis the lowest slot does
+  int kept = 0;
+  if (t < LAP_N) {
+    int cand = -1;
+    double d = 0.0;
+    if (t < np) {
+      const int last = last_track[(size_t)b * P + s_pid[t]];
+      if (last >= 0)
+        for (int h = 0; h < nh; ++h)
+          if (cand < 0 && s_hid[h] == last) cand = h;
+      if (cand >= 0) {
+        d = s_d[t * LAP_N + cand];
+        if (!(d <= thr)) cand = -1;
+      }
+    }
+    bool keep = cand >= 0;
+    for (int k = 0; k < LAP_N; ++k) {
+      const int ck = lap_lane(cand, k);
+      if (k < t && ck >= 0 && ck == cand) keep = false;
+    }
+    if (keep) {
+      s_ph[t] = cand;
+      s_taken[cand] = 1;
+      s_pd[t] = d;
+    }
+    kept = __popcll(__ballot(keep));
+  }
+  // step 9 by all threads, from the full tile
+  int over = 0;
+  for (int e = t; e < np * nh; e += TRACK_THREADS) {
+    const int a = e / nh, h = e % nh;
+    if (s_d[a * LAP_N + h] <= thr) {
+      const int tid = s_hid[h];
+      if (tid < K) overlap[((size_t)b * P + s_pid[a]) * K + tid] += 1;
+      else ++over;
+    }
+  }
+  __syncthreads();
+
+  // step 6: the remaining persons x hypotheses, compacted in place through registers, then the solve on wavefront 0
+  if (t < LAP_N) {
+    const bool rp = t < np && s_ph[t] < 0, rh = t < nh && s_taken[t] == 0;
+    const u64 rp_mask = __ballot(rp), rh_mask = __ballot(rh);
+    if (rp) s_rp[__popcll(rp_mask & ((1ull << t) - 1ull))] = t;
+    if (rh) s_rh[__popcll(rh_mask & ((1ull << t) - 1ull))] = t;
+    if (t == 0) {
+      s_nrp = __popcll(rp_mask);
+      s_nrh = __popcll(rh_mask);
+    }
+  }
+  s_scan[0][0][t] = over;                        // the scan is done with: the per-thread id_overflow counts
+  __syncthreads();
+  const int nrp = s_nrp, nrh = s_nrh;
+  double moved[TE_GATHER];
+#pragma unroll
+  for (int k = 0; k < TE_GATHER; ++k) {
+    const int e = t + k * TRACK_THREADS;
+    moved[k] = e < nrp * nrh ? s_d[s_rp[e / nrh] * LAP_N + s_rh[e % nrh]] : 0.0;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < TE_GATHER; ++k) {
+    const int e = t + k * TRACK_THREADS;
+    if (e < nrp * nrh) s_d[(e / nrh) * LAP_N + e % nrh] = moved[k];
+  }
+  __syncthreads();
+  if (t < LAP_N) lap_solve(s_d, nrp, nrh, LapGate{thr}, s_col, t);
+  __syncthreads();
+  if (t < nrp) {
+    const int j = s_col[t];
+    if (j >= 0 && s_d[t * LAP_N + j] <= thr) {                                  // the ungated distance: NaN is no match
+      s_ph[s_rp[t]] = s_rh[j];
+      s_pd[s_rp[t]] = s_d[t * LAP_N + j];
+    }
+  }
+  __syncthreads();
+
+  // steps 7 and 8 on wavefront 0: a lane per person (the identities are distinct), the distance sum and the counters by lane 0
+  if (t < LAP_N) {
+    bool matched = false, switched = false;
+    if (t < np) {
+      const size_t at = (size_t)b * P + s_pid[t];
+      seen[at] += 1;
+      matched = s_ph[t] >= 0;
+      if (matched) {
+        const int tid = s_hid[s_ph[t]], last = last_track[at];
+        covered[at] += 1;
+        switched = last >= 0 && last != tid;
+        last_track[at] = tid;
+      }
+    }
+    const int matches = __popcll(__ballot(matched)), switches = __popcll(__ballot(switched));
+    int overflow = (s_scan[0][0][t] + s_scan[0][0][t + LAP_N]) + (s_scan[0][0][t + 2 * LAP_N] + s_scan[0][0][t + 3 * LAP_N]);
+    for (int off = LAP_N / 2; off > 0; off >>= 1) overflow += __shfl_xor(overflow, off);
+    if (t == 0) {
+      double sum = dist_sum[b];
+      for (int a = 0; a < np; ++a)
+        if (s_ph[a] >= 0) sum = sum + s_pd[a];
+      dist_sum[b] = sum;
+      i64* c = counters + (size_t)b * MVG_TRACK_EVAL_WORDS;
+      c[TE_FRAMES] += 1;
+      c[TE_GT] += np;
+      c[TE_HYP] += nh;
+      c[TE_MATCHES] += matches;
+      c[TE_MISSES] += np - matches;
+      c[TE_FALSE_POS] += nh - matches;
+      c[TE_SWITCHES] += switches;
+      c[TE_KEPT] += kept;
+      c[TE_DROPPED] += nh_all - nh;
+      c[TE_UNREPORTED] += unreported;
+      c[TE_BAD_ID] += s_bad;
+      c[TE_ID_OVERFLOW] += overflow;
+    }
+  }
+}
+
 static bool track_noise_ok(double v, bool zero_ok) { return (zero_ok ? v >= 0.0 : v > 0.0) && v <= MVG_LAP_BIG; }   // false for NaN
 
 extern "C" {
@@ -486,6 +727,24 @@ int mvg_track_update(const float* dets, const int* count, int B, int R, int J, i
   if (((uintptr_t)born & 7) || ((uintptr_t)state & 7)) return MVG_E_BADARG;
   hipLaunchKernelGGL(track_update_kernel, dim3(B), dim3(TRACK_THREADS), 0, (hipStream_t)stream, dets, count, B, R, J, T, id, hits,
                      misses, (i64*)born, score, pose, next_id, (i64*)state, max_dist, max_misses, min_hits, ids, slots);
+  MVG_LAUNCH_CHECK();
+  return 0;
+}
+
+int mvg_track_eval(const float* dets, const int* count, const int* ids, const float* row_pose, const float* joints_3d,
+                   const float* joints_3d_vis, const int* num_person, const int* person_id, int B, int R, int J, int G, int P, int K,
+                   double dist_thr, int* last_track, int64_t* counters, double* dist_sum, int64_t* seen, int64_t* covered,
+                   int* overlap, void* stream) {
+  if (B < 1 || B > MVG_TRACK_MAX_B || R < 1 || R > MVG_TRACK_MAX_R || J < 1 || J > MVG_TRACK_MAX_J) return MVG_E_BADARG;
+  if (G < 1 || P < G || P > MVG_TRACK_EVAL_MAX_P || K < 1 || K > MVG_TRACK_EVAL_MAX_K) return MVG_E_BADARG;
+  if (!(dist_thr >= 0.0) || dist_thr > MVG_LAP_BIG) return MVG_E_BADARG;
+  if (dets == nullptr || ids == nullptr || joints_3d == nullptr || joints_3d_vis == nullptr || num_person == nullptr) return MVG_E_BADARG;
+  if (last_track == nullptr || counters == nullptr || dist_sum == nullptr || seen == nullptr || covered == nullptr) return MVG_E_BADARG;
+  if (overlap == nullptr) return MVG_E_BADARG;
+  if (((uintptr_t)counters & 7) || ((uintptr_t)dist_sum & 7) || ((uintptr_t)seen & 7) || ((uintptr_t)covered & 7)) return MVG_E_BADARG;
+  hipLaunchKernelGGL(track_eval_kernel, dim3(B), dim3(TRACK_THREADS), 0, (hipStream_t)stream, dets, count, ids, row_pose, joints_3d,
+                     joints_3d_vis, num_person, person_id, R, J, G, P, K, dist_thr, last_track, (i64*)counters, dist_sum, (i64*)seen,
+                     (i64*)covered, overlap);
   MVG_LAUNCH_CHECK();
   return 0;
 }

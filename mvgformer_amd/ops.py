@@ -1557,6 +1557,83 @@ def track_correct(buffers, motion, r=400.0, v0=2500.0):
     return motion["row_pose"]
 
 
+TRACK_EVAL_MAX_P, TRACK_EVAL_MAX_K = 64, 4096      # MVG_TRACK_EVAL_MAX_*
+TRACK_EVAL_STATE = ("frames", "gt", "hyp", "matches", "misses", "false_pos", "switches", "kept", "dropped", "unreported", "bad_id",
+                    "id_overflow", "reserved")      # MVG_TRACK_EVAL_WORDS
+_TRACK_EVAL_KEYS = (("last_track", torch.int32), ("counters", torch.int64), ("dist_sum", torch.float64), ("seen", torch.int64),
+                    ("covered", torch.int64), ("overlap", torch.int32))
+
+
+def _track_eval_shapes(B, P, K):
+    return dict(last_track=(B, P), counters=(B, len(TRACK_EVAL_STATE)), dist_sum=(B,), seen=(B, P), covered=(B, P), overlap=(B, P, K))
+
+
+def track_eval_buffers(B, P, K, device="cuda"):
+    """the state of track_eval for B streams of P identities and K track ids -- last_track (B, P) int32 filled with -1, counters
+    (B, len(TRACK_EVAL_STATE)) int64, dist_sum (B) fp64, seen, covered (B, P) int64, overlap (B, P, K) int32, zeros.  Allocated
+    once and kept alive by the caller, like track_buffers."""
+    B, P, K = int(B), int(P), int(K)
+    if not (1 <= B <= TRACK_MAX_B and 1 <= P <= TRACK_EVAL_MAX_P and 1 <= K <= TRACK_EVAL_MAX_K):
+        raise L.MvgError("track_eval_buffers: unsupported shape B = %d (<= %d), P = %d (<= %d), K = %d (<= %d)"
+                         % (B, TRACK_MAX_B, P, TRACK_EVAL_MAX_P, K, TRACK_EVAL_MAX_K))
+    shapes = _track_eval_shapes(B, P, K)
+    out = {k: torch.zeros(shapes[k], dtype=dt, device=device) for k, dt in _TRACK_EVAL_KEYS}
+    out["last_track"].fill_(-1)
+    return out
+
+
+def track_eval(dets, count, ids, joints_3d, joints_3d_vis, num_person, buffers, dist_thr=500.0, row_pose=None, person_id=None):
+    """One frame of CLEAR-MOT / identity scoring on the device (mvg_track_eval: one launch behind track_update, nothing read back,
+    no atomics).  dets (B, R, J, 5) fp32, count (B, 2) int32 or None and ids (B, R) int32 as pose_nms and track_update leave them;
+    row_pose (B, R, J, 3) fp32 or None: the motion model's filtered poses, scored instead of dets; joints_3d (B, G, J, 3),
+    joints_3d_vis (B, G, J) fp32, num_person (B) int32 as the evaluator takes them (num_person < 0: the frame has no annotation
+    and is skipped); person_id (B, G) int32 or None (person slot g is identity g); ``buffers`` from track_eval_buffers.  The rows
+    with an id are matched to the persons by the CLEAR-MOT rules of include/mvg_decoder.h (last frame's pairs first while within
+    dist_thr, the rest by minimum-cost assignment) and misses, false positives, identity switches, the matched distance and the
+    person x track id overlap table are accumulated.  -> buffers."""
+    tensors = [buffers[k] for k, _ in _TRACK_EVAL_KEYS]
+    L.require_cuda(dets, count, ids, row_pose, joints_3d, joints_3d_vis, num_person, person_id, *tensors)
+    if dets.dim() != 4 or dets.shape[-1] != 5 or dets.dtype != torch.float32:
+        raise RuntimeError("mvg_track_eval: dets (B, R, J, 5) float32 expected")
+    B, R, J = dets.shape[:3]
+    if count is not None and (count.dtype != torch.int32 or tuple(count.shape) != (B, 2)):
+        raise RuntimeError("mvg_track_eval: count (B, 2) int32 or None expected")
+    if ids.dtype != torch.int32 or tuple(ids.shape) != (B, R):
+        raise RuntimeError("mvg_track_eval: ids (B, R) int32 expected")
+    if row_pose is not None and (row_pose.dtype != torch.float32 or tuple(row_pose.shape) != (B, R, J, 3)):
+        raise RuntimeError("mvg_track_eval: row_pose (B, R, J, 3) float32 or None expected")
+    if joints_3d.dim() != 4 or joints_3d.dtype != torch.float32 or joints_3d.shape[0] != B or tuple(joints_3d.shape[2:]) != (J, 3):
+        raise RuntimeError("mvg_track_eval: joints_3d (B, G, J, 3) float32 expected")
+    G = joints_3d.shape[1]
+    if joints_3d_vis.dtype != torch.float32 or tuple(joints_3d_vis.shape) != (B, G, J):
+        raise RuntimeError("mvg_track_eval: joints_3d_vis (B, G, J) float32 expected")
+    if num_person.dtype != torch.int32 or tuple(num_person.shape) != (B,):
+        raise RuntimeError("mvg_track_eval: num_person (B) int32 expected")
+    if person_id is not None and (person_id.dtype != torch.int32 or tuple(person_id.shape) != (B, G)):
+        raise RuntimeError("mvg_track_eval: person_id (B, G) int32 or None expected")
+    if not all(t is None or t.is_contiguous() for t in (dets, count, ids, row_pose, joints_3d, joints_3d_vis, num_person, person_id,
+                                                         *tensors)):
+        raise RuntimeError("mvg_track_eval: every tensor must be contiguous")
+    overlap = buffers["overlap"]
+    P, K = (overlap.shape[1], overlap.shape[2]) if overlap.dim() == 3 else (0, 0)
+    shapes = _track_eval_shapes(B, P, K)
+    if any(t.dtype != dt or tuple(t.shape) != shapes[k] for (k, dt), t in zip(_TRACK_EVAL_KEYS, tensors)):
+        raise RuntimeError("mvg_track_eval: buffers are not those of track_eval_buffers for dets %s" % (tuple(dets.shape),))
+    if not (1 <= B <= TRACK_MAX_B and 1 <= R <= TRACK_MAX_R and 1 <= J <= TRACK_MAX_J and 1 <= G <= P <= TRACK_EVAL_MAX_P
+            and 1 <= K <= TRACK_EVAL_MAX_K):
+        raise L.MvgError("mvg_track_eval: unsupported shape B = %d (<= %d), R = %d (<= %d), J = %d (<= %d), G = %d <= P = %d (<= %d), "
+                         "K = %d (<= %d)" % (B, TRACK_MAX_B, R, TRACK_MAX_R, J, TRACK_MAX_J, G, P, TRACK_EVAL_MAX_P, K,
+                                             TRACK_EVAL_MAX_K))
+    if not (0.0 <= float(dist_thr) <= LAP_BIG):
+        raise L.MvgError("mvg_track_eval: 0 <= dist_thr <= %g expected (got %r)" % (LAP_BIG, dist_thr))
+    lib = L.load()
+    with _timed("track_eval"):
+        L.check(lib.mvg_track_eval(L.ptr(dets), L.ptr(count), L.ptr(ids), L.ptr(row_pose), L.ptr(joints_3d), L.ptr(joints_3d_vis),
+                                   L.ptr(num_person), L.ptr(person_id), B, R, J, G, P, K, float(dist_thr),
+                                   *(L.ptr(t) for t in tensors), L.stream_ptr()), "mvg_track_eval")
+    return buffers
+
+
 ST_MAX_J, ST_MAX_V, ST_MAX_STEPS = 17, 32, 8       # MVG_ST_MAX_*
 ST_METHODS = {"LS": 0, "ST": 1}                     # MVG_ST_LS, MVG_ST_ST
 

@@ -46,6 +46,13 @@ key, ``motion=True`` or ``motion=dict(dt=1.0, q=25.0, r=400.0, v0=2500.0)``, tur
 (``tracking.PoseTracker(motion=...)``: two more launches in the graph, the four values fixed at capture): ``runner.track_poses``
 (B, dets_rows, J, 3) fp32 is then the filtered pose of every row of ``runner.detections[0]``, static like ``track_ids``.
 
+``track_evaluation=dict(dist_thr=500.0, max_persons=10, max_ids=1024)`` (requires ``tracking``) continues right behind the tracker
+with ``tracking.TrackEvaluator.update``, one more launch: the ids of every replayed frame are scored against the ground-truth
+identities (``load(ground_truth=(joints_3d, joints_3d_vis, num_person[, person_id]))``, the static inputs ``evaluation`` reads;
+a frame with ``num_person < 0`` has no annotation and is skipped) and the CLEAR-MOT counts and the identity overlap table are
+accumulated in ``runner.track_evaluator``; ``.report()`` is the one read-back (MOTA, MOTP, IDF1, mostly tracked / lost).  The
+warm-up forwards of a capture count no frame.
+
 ``refine=dict(bone_lengths=<J-1 values, mm>, n_steps=1, method="ST")`` (requires ``postprocess``) continues behind the NMS with
 ``structural.StructuralRefiner.update``, two more launches, independent of ``evaluation`` and ``tracking`` (which keep reading
 ``dets`` unchanged): the kept queries are re-solved from the last layer's 2D points in all views under the given bone lengths of
@@ -64,7 +71,7 @@ from .decoder import DecoderContext
 class GraphedDecoder:
     def __init__(self, decoder, meta, spatial_shapes, level_start_index, batch, num_queries, threshold=0.1, device=None,
                  producer_writes_in_place=False, channels=256, postprocess=None, convert_joint_format_indices=None, evaluation=None,
-                 tracking=None, refine=None):
+                 tracking=None, refine=None, track_evaluation=None):
         layer0 = decoder.layers[0]
         dev = torch.device(device) if device is not None else next(decoder.parameters()).device
         if dev.type != "cuda":
@@ -134,6 +141,27 @@ class GraphedDecoder:
             self.tracker = PoseTracker(batch=batch, rows=dets.shape[1], num_joints=dets.shape[2], device=dev, **tracking)
             self.track_ids = (self.tracker.buffers["ids"], self.tracker.buffers["slots"])
             self.track_poses = self.tracker.row_poses       # None without tracking["motion"]
+        # optional scoring of the track ids against ground truth identities right behind the tracker, inside the same graph
+        self.track_evaluator, self.person_id = None, None
+        if track_evaluation is not None:
+            from .tracking import TrackEvaluator
+            if tracking is None:
+                raise ValueError("GraphedDecoder: track_evaluation scores the ids of the tracker; it requires tracking")
+            unknown = set(track_evaluation) - {"dist_thr", "max_persons", "max_ids"}
+            if unknown:
+                raise TypeError("GraphedDecoder: unknown track_evaluation keys %s" % sorted(unknown))
+            given = dict(track_evaluation)
+            if self.evaluator is not None:      # one set of ground-truth buffers serves both: the evaluator's person slots
+                given.setdefault("max_persons", self.evaluator.max_persons)
+                if given["max_persons"] < self.evaluator.max_persons:
+                    raise ValueError("GraphedDecoder: track_evaluation max_persons = %d below the %d person slots of evaluation"
+                                     % (given["max_persons"], self.evaluator.max_persons))
+            self.track_evaluator = TrackEvaluator(batch=batch, device=dev, **given)
+            fresh = self.track_evaluator.ground_truth_buffers(batch, self._nms["dets"].shape[2])
+            if self.ground_truth is None:
+                self.ground_truth = fresh[:3]
+            self._slot_identity = fresh[3][:, :self.ground_truth[0].shape[1]].contiguous()      # slot g = identity g
+            self.person_id = self._slot_identity.clone()
         # optional structural triangulation of the kept queries (fixed bone lengths) behind the NMS, inside the same graph
         self.refiner, self.refined, self.bone_lengths, self._Pm = None, None, None, None
         if refine is not None:
@@ -158,15 +186,24 @@ class GraphedDecoder:
     # ------------------------------------------------------------------ inputs (device-side copies on the current stream)
     def load(self, src_views=None, tgt=None, query_pos=None, reference_points=None, ground_truth=None):
         """ground_truth = (joints_3d (B, G, J, 3), joints_3d_vis (B, G, J), num_person (B)) with G <= max_persons, for a runner
-        built with ``evaluation``: copied into the static inputs the evaluator reads; person slots behind G are not scored."""
+        built with ``evaluation`` or ``track_evaluation``: copied into the static inputs both read; person slots behind G are not
+        scored.  An optional fourth element person_id (B, G) int32 gives the slots' identities to ``track_evaluation`` (without
+        it, slot g is identity g); num_person < 0 marks a frame without annotation, which ``track_evaluation`` skips."""
         with torch.no_grad():
             if ground_truth is not None:
-                if self.evaluator is None:
-                    raise ValueError("GraphedDecoder: ground_truth needs a runner built with evaluation=dict(...)")
-                j3d, vis, num = ground_truth
+                if self.evaluator is None and self.track_evaluator is None:
+                    raise ValueError("GraphedDecoder: ground_truth needs a runner built with evaluation=dict(...) or "
+                                     "track_evaluation=dict(...)")
+                j3d, vis, num = ground_truth[:3]
+                if len(ground_truth) > 3 and self.track_evaluator is None:
+                    raise ValueError("GraphedDecoder: person_id needs a runner built with track_evaluation=dict(...)")
                 if j3d.shape[1] > self.ground_truth[0].shape[1]:
                     raise ValueError("GraphedDecoder: %d person slots, built for max_persons = %d"
                                      % (j3d.shape[1], self.ground_truth[0].shape[1]))
+                if self.person_id is not None:
+                    self.person_id.copy_(self._slot_identity)
+                    if len(ground_truth) > 3 and ground_truth[3] is not None:
+                        self.person_id[:, :j3d.shape[1]].copy_(ground_truth[3], non_blocking=True)
                 self.ground_truth[0][:, :j3d.shape[1]].copy_(j3d, non_blocking=True)
                 self.ground_truth[1][:, :vis.shape[1]].copy_(vis, non_blocking=True)
                 self.ground_truth[2].copy_(num, non_blocking=True)
@@ -208,6 +245,9 @@ class GraphedDecoder:
                 self.evaluator.update(self._nms["dets"], self._nms["count"], *self.ground_truth)
             if self.tracker is not None:
                 self.tracker.update(self._nms["dets"], self._nms["count"])
+            if self.track_evaluator is not None:
+                self.track_evaluator.update(self.tracker, self._nms["dets"], self._nms["count"], *self.ground_truth,
+                                            person_id=self.person_id)
             if self.refiner is not None:
                 self.refiner.update(outputs[2][-1], self.ctx.cams, self._Pm, self._nms["keep"], self._nms["count"])
         return outputs
@@ -217,8 +257,11 @@ class GraphedDecoder:
             # the warm-up forwards score whatever is loaded: the accumulators are put back, so a (re-)capture counts no frame
             saved = None if self.evaluator is None else {k: t.clone() for k, t in self.evaluator.buffers.items()}
             tracks = None if self.tracker is None else self.tracker.snapshot()      # nor do they age or create tracks
+            scores = None if self.track_evaluator is None else self.track_evaluator.snapshot()
             for _ in range(max(1, warmup)):         # builds the weight caches, sizes the per-layer buffers
                 self._forward()
+            if scores is not None:
+                self.track_evaluator.restore(scores)
             if saved is not None:
                 for k, t in self.evaluator.buffers.items():
                     t.copy_(saved[k])
@@ -244,6 +287,8 @@ class GraphedDecoder:
             keep += list(self._nms.values())
         if self.evaluator is not None:
             keep += list(self.evaluator.buffers.values()) + list(self.ground_truth)
+        if self.track_evaluator is not None:
+            keep += list(self.track_evaluator.buffers.values()) + list(self.ground_truth) + [self.person_id]
         if self.tracker is not None:
             keep += list(self.tracker.buffers.values()) + list((self.tracker.motion_buffers or {}).values())
         if self.refiner is not None:

@@ -20,6 +20,10 @@ an unmatched track coasts on at its velocity.  ``tracker.row_poses`` (B, R, J, 3
 ``tracker.motion()`` reads velocities and covariances back.  Without ``motion`` nothing else is launched or allocated.
 
 ``update`` has fixed shapes and launches only, so it can be captured in a HIP graph (``serving.GraphedDecoder(tracking=...)``).
+
+``TrackEvaluator`` scores the ids against ground truth on the device, one more launch behind the tracker's (``ops.track_eval``):
+CLEAR-MOT counts (MOTA, MOTP) and the person x track-id overlap table IDF1 is computed from at the one read-back
+(``serving.GraphedDecoder(tracking=..., track_evaluation=...)``).
 """
 from __future__ import annotations
 
@@ -29,7 +33,7 @@ import math
 
 import torch
 
-__all__ = ["PoseTracker", "Track"]
+__all__ = ["PoseTracker", "Track", "TrackEvaluator", "max_weight_assignment"]
 
 Track = collections.namedtuple("Track", "id slot hits misses born score pose")
 
@@ -45,7 +49,8 @@ class PoseTracker:
     the random acceleration, unit^2 / dt^4), r (variance of a detected coordinate, unit^2) and v0 (variance of a new track's
     velocity, unit^2 / dt^2).  The defaults -- 25.0, 400.0 and 2500.0: accelerations of 5 mm / frame^2, detections good to 20 mm,
     people no faster than about 50 mm per frame -- are a CHOICE made for poses in mm at video rate, not a measurement: they were
-    tuned on no recorded sequence, and no accuracy is claimed for them."""
+    tuned on no recorded sequence, and no accuracy is claimed for them (``TrackEvaluator`` below is the instrument; the one table
+    measured with it, profiles/track_eval.txt, is on synthetic sequences, not on Panoptic)."""
 
     def __init__(self, batch=1, rows=1024, num_joints=15, max_tracks=32, max_dist=500.0, max_misses=10, min_hits=1, device="cuda",
                  motion=None):
@@ -136,3 +141,187 @@ class PoseTracker:
         var = packed[B * T:4 * B * T].reshape(B, T, 3)
         vel = packed[4 * B * T:].reshape(B, T, J, 3)
         return [{t: (vel[b, t].copy(), tuple(float(p) for p in var[b, t])) for t in range(T) if ident[b, t] >= 0} for b in range(B)]
+
+
+def max_weight_assignment(table):
+    """table (n, m) of non-negative integers -> (total, col_of_row): the one-to-one assignment of rows to columns of maximum total
+    weight (col_of_row[r] = -1 for a row left out because n > m), by shortest augmenting paths with integer potentials, the inner
+    loop over the columns vectorised.  The identity overlap tables it is for have at most 64 rows."""
+    import numpy as np
+    w = np.asarray(table, dtype=np.int64)
+    if w.ndim != 2:
+        raise ValueError("max_weight_assignment: a 2-D table expected")
+    rows, cols = w.shape
+    col_of_row = np.full((rows,), -1, np.int64)
+    if rows == 0 or cols == 0:
+        return 0, col_of_row
+    flipped = rows > cols
+    if flipped:
+        w = w.T
+    n, m = w.shape
+    cost = -w                                            # minimise; every row gets a column (n <= m, weights >= 0: no loss)
+    big = np.iinfo(np.int64).max // 4
+    u, v = np.zeros(n + 1, np.int64), np.zeros(m + 1, np.int64)
+    p, way = np.zeros(m + 1, np.int64), np.zeros(m + 1, np.int64)     # p[j]: the row of column j, 1-based, 0 = none
+    for i in range(1, n + 1):
+        p[0], j0 = i, 0
+        minv, used = np.full(m + 1, big, np.int64), np.zeros(m + 1, bool)
+        for _ in range(m + 1):                           # every step uses one more column
+            used[j0] = True
+            i0 = p[j0]
+            cur = cost[i0 - 1] - u[i0] - v[1:]
+            better = ~used[1:] & (cur < minv[1:])
+            minv[1:][better] = cur[better]
+            way[1:][better] = j0
+            masked = np.where(used, big, minv)
+            j1 = int(np.argmin(masked[1:])) + 1
+            delta = masked[j1]
+            u[p[used]] += delta                          # the rows of the used columns are distinct
+            v[used] -= delta
+            minv[~used] -= delta
+            j0 = j1
+            if p[j0] == 0:
+                break
+        while j0:
+            j1 = way[j0]
+            p[j0] = p[j1]
+            j0 = j1
+    total = 0
+    for j in range(1, m + 1):
+        if p[j] > 0:
+            r, c = (j - 1, p[j] - 1) if flipped else (p[j] - 1, j - 1)
+            col_of_row[r] = c
+            total += int(w[p[j] - 1, j - 1])
+    return total, col_of_row
+
+
+def _ratio(num, den):
+    return float(num) / float(den) if den else math.nan
+
+
+class TrackEvaluator:
+    """CLEAR-MOT and identity scores of a ``PoseTracker``'s ids against ground truth, accumulated on the device
+    (``ops.track_eval``, csrc/track.hip: one launch per frame behind the tracker, nothing read back, fp64, no atomics).
+
+        scorer = TrackEvaluator(batch=1, max_persons=10)
+        for frame in stream:
+            ids, slots = tracker.update(dets, count)
+            scorer.update(tracker, dets, count, joints_3d, joints_3d_vis, num_person)      # launch only
+        scorer.report()["total"]["mota"]                                                    # one read-back
+
+    batch: streams; max_persons: identities per stream (<= 64), at least the person slots of the ground truth; max_ids: columns
+    of the person x track id overlap table IDF1 is computed from (<= 4096; ids at or above it are counted in ``id_overflow``);
+    dist_thr: the distance within which a pose can be a person's, in the unit of the poses (500 mm: the evaluation's recall
+    distance).  The rules are the contract of ``mvg_track_eval`` in include/mvg_decoder.h."""
+
+    def __init__(self, batch=1, max_persons=10, max_ids=1024, dist_thr=500.0, device="cuda"):
+        from . import ops
+        self.batch, self.max_persons, self.max_ids, self.dist_thr = int(batch), int(max_persons), int(max_ids), float(dist_thr)
+        if not (0.0 <= self.dist_thr <= ops.LAP_BIG):
+            raise ValueError("TrackEvaluator: 0 <= dist_thr <= %g expected (got %r)" % (ops.LAP_BIG, dist_thr))
+        self.device = torch.device(device)
+        self.buffers = ops.track_eval_buffers(self.batch, self.max_persons, self.max_ids, self.device)
+        self._next_id = None           # the last tracker's next_id: what report() names when ids overflowed the table
+
+    def ground_truth_buffers(self, batch, num_joints):
+        """zeroed static inputs (joints_3d, joints_3d_vis, num_person, person_id) for ``max_persons`` person slots (graph capture);
+        person_id is the identity map, slot g = identity g"""
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=self.device)         # noqa: E731
+        ident = torch.arange(self.max_persons, dtype=torch.int32, device=self.device).repeat(batch, 1).contiguous()
+        return (z((batch, self.max_persons, num_joints, 3), torch.float32), z((batch, self.max_persons, num_joints), torch.float32),
+                z((batch,), torch.int32), ident)
+
+    def update(self, tracker, dets, count, joints_3d, joints_3d_vis, num_person, person_id=None):
+        """score the frame ``tracker.update(dets, count)`` has just associated: the tracker's ids (and, with its motion model, its
+        filtered ``row_poses`` instead of the detections' poses) against joints_3d (B, G, J, 3), joints_3d_vis (B, G, J) fp32 and
+        num_person (B) int32 (< 0: the frame has no annotation and is skipped); person_id (B, G) int32 or None.  Launch only."""
+        from . import ops
+        if joints_3d.dim() == 4 and joints_3d.shape[1] > self.max_persons:
+            raise ValueError("TrackEvaluator: %d person slots, built for max_persons = %d" % (joints_3d.shape[1], self.max_persons))
+        self._next_id = tracker.buffers["next_id"]
+        with torch.cuda.device(dets.device) if dets.is_cuda else contextlib.nullcontext():
+            ops.track_eval(dets, count, tracker.buffers["ids"], joints_3d, joints_3d_vis, num_person, self.buffers, self.dist_thr,
+                           row_pose=tracker.row_poses, person_id=person_id)
+        return self
+
+    def reset(self):
+        """forget every count (device fills)"""
+        for k, t in self.buffers.items():
+            t.fill_(-1 if k == "last_track" else 0)
+        return self
+
+    def snapshot(self):
+        """clones of the state buffers (``restore`` puts them back: a graph capture's warm-up forwards must count no frame)"""
+        return {k: t.clone() for k, t in self.buffers.items()}
+
+    def restore(self, saved):
+        for k, t in self.buffers.items():
+            t.copy_(saved[k])
+        return self
+
+    def state(self):
+        """the named counters summed over the streams, as ints (a read-back)"""
+        from . import ops
+        return dict(zip(ops.TRACK_EVAL_STATE, self.buffers["counters"].sum(dim=0).cpu().tolist()))
+
+    def _read(self):
+        """every buffer in ONE copy to the host -> dict of numpy arrays (plus next_id of the last tracker, if any)"""
+        import numpy as np
+        named = dict(self.buffers)
+        if self._next_id is not None:
+            named["next_id"] = self._next_id
+        raw = torch.cat([t.reshape(-1).view(torch.uint8) for t in named.values()]).cpu().numpy()
+        out, at = {}, 0
+        for k, t in named.items():
+            size = t.numel() * t.element_size()
+            out[k] = np.frombuffer(raw[at:at + size].tobytes(), dtype=str(t.dtype).replace("torch.", "")).reshape(tuple(t.shape))
+            at += size
+        return out
+
+    @staticmethod
+    def _scores(c, dist_sum, idtp, seen, covered):
+        """the ratios of one stream or of the sum over the streams; a ratio is NaN when its denominator is 0"""
+        tracked = [(int(cv), int(sn)) for cv, sn in zip(covered.reshape(-1).tolist(), seen.reshape(-1).tolist()) if sn > 0]
+        out = dict(c)
+        out.update(dist_sum=float(dist_sum),
+                   mota=1.0 - _ratio(c["misses"] + c["false_pos"] + c["switches"], c["gt"]),
+                   motp=_ratio(dist_sum, c["matches"]), idtp=idtp,
+                   idf1=None if c["id_overflow"] > 0 else _ratio(2 * idtp, c["gt"] + c["hyp"]),
+                   identities=len(tracked),
+                   mostly_tracked=sum(1 for cv, sn in tracked if 5 * cv >= 4 * sn),       # covered / seen >= 0.8
+                   mostly_lost=sum(1 for cv, sn in tracked if 5 * cv <= sn))              # covered / seen <= 0.2
+        return out
+
+    def report(self):
+        """one read-back -> {"streams": [per stream], "total": summed over the streams}, each the named counters, dist_sum, mota =
+        1 - (misses + false_pos + switches) / gt, motp = dist_sum / matches, idtp = the maximum-weight one-to-one assignment of
+        identities to track ids on the overlap table (``max_weight_assignment``, on the host), idf1 = 2 idtp / (gt + hyp),
+        identities (those seen), mostly_tracked / mostly_lost (covered / seen >= 0.8 / <= 0.2).  A ratio is NaN when its
+        denominator is 0.  With ids that did not fit the table (id_overflow > 0) idf1 is None and "max_ids_needed" says which
+        ``max_ids`` the run needs."""
+        import numpy as np
+        from . import ops
+        host = self._read()
+        streams = []
+        for b in range(self.batch):
+            c = dict(zip(ops.TRACK_EVAL_STATE, (int(x) for x in host["counters"][b])))
+            table = host["overlap"][b]
+            used = np.flatnonzero(table.any(axis=0))                             # only the ids that were ever near a person
+            idtp = max_weight_assignment(table[:, used])[0] if len(used) else 0
+            streams.append(self._scores(c, host["dist_sum"][b], idtp, host["seen"][b], host["covered"][b]))
+        total_c = {k: sum(s[k] for s in streams) for k in ops.TRACK_EVAL_STATE}
+        dist_sum = 0.0
+        for b in range(self.batch):
+            dist_sum += float(host["dist_sum"][b])
+        total = self._scores(total_c, dist_sum, sum(s["idtp"] for s in streams), host["seen"], host["covered"])
+        out = dict(streams=streams, total=total, dist_thr=self.dist_thr, max_persons=self.max_persons, max_ids=self.max_ids)
+        if total_c["id_overflow"] > 0:
+            out["note"] = ("track ids at or above max_ids = %d were met %d times: the overlap table is incomplete and idf1 is not "
+                           "reported; " % (self.max_ids, total_c["id_overflow"]))
+            if "next_id" in host:
+                out["max_ids_needed"] = int(host["next_id"].max())
+                out["note"] += "rerun with max_ids >= %d" % out["max_ids_needed"]
+            else:       # the buffers were not filled through update(tracker, ...): the ids the tracker gave out are not known here
+                out["max_ids_needed"] = None
+                out["note"] += "rerun with max_ids above the largest track id (the tracker's next_id)"
+        return out

@@ -21,7 +21,8 @@ frame loop then reads nothing back and the metrics are fetched once per threshol
 constant-velocity motion model.  ``--device-refine 1 --bone-lengths FILE.npy`` (on top of ``--device-nms 1``) re-solves the kept
 poses under the J-1 bone lengths of the file (mm) by structural triangulation (``structural.StructuralRefiner``, inside the HIP
 graph with ``--graph 1``) and reports the share of kept rows it solved and their mean absolute bone-length residual
-before and after.
+before and after.  ``--device-track-eval 1`` (on top of ``--device-track 1``) scores the track ids against the ground-truth
+identities of frames that carry ``joints_3d`` (``tracking.TrackEvaluator``: CLEAR-MOT counts, MOTA, MOTP, IDF1 per threshold).
 """
 from __future__ import annotations
 
@@ -137,6 +138,20 @@ def device_ground_truth(frames, kind, num_joints, device):
     return G, out
 
 
+def track_ground_truth(frames, gt_dev, person_ids, persons, device):
+    """--device-track-eval: per frame the TrackEvaluator's inputs, the evaluator's (device_ground_truth) with num_person = -1 for a
+    frame without ground truth (it is skipped, not scored as empty) and person_id (1, G) int32: slot g is identity g unless the
+    npz's person_ids (F, G') says otherwise"""
+    out = []
+    for fi, ((_, _, gt), (j3d, vis, num)) in enumerate(zip(frames, gt_dev)):
+        pid = torch.arange(persons, dtype=torch.int32)[None].clone()
+        if person_ids is not None:
+            given = torch.from_numpy(np.asarray(person_ids[fi]).astype(np.int32))[:persons]
+            pid[0, :len(given)] = given
+        out.append((j3d, vis, num if gt is not None else torch.full_like(num, -1), pid.to(device)))
+    return out
+
+
 def pcp_report(kept, gts, gts_vis, evaluator=None):
     """the PCP entry of a result row (Shelf.evaluate / Campus.evaluate through evaluate.evaluate_pcp, or the counters of a
     DeviceEvaluator), in percent"""
@@ -177,6 +192,12 @@ def main(argv=None):
                     help="1 (needs --device-track 1): the tracker's constant-velocity motion model with its default parameters "
                          "(tracking.PoseTracker(motion=True), two more launches per frame); the report gains the mean speed of "
                          "the live tracks")
+    ap.add_argument("--device-track-eval", type=int, default=0, choices=[0, 1],
+                    help="1 (needs --device-track 1 and frames with ground truth): the track ids are scored against the ground-truth "
+                         "identities on the device (tracking.TrackEvaluator, one more launch per frame, inside the HIP graph with "
+                         "--graph 1); every threshold's row gains \"device_track_eval\" (CLEAR-MOT counts, MOTA, MOTP, IDF1, mostly "
+                         "tracked / lost).  Person slot g is identity g unless the npz holds person_ids (F, G); a frame without "
+                         "ground truth is skipped")
     ap.add_argument("--device-refine", type=int, default=0, choices=[0, 1],
                     help="1 (needs --device-nms 1 and --bone-lengths): the kept poses are re-solved under fixed bone lengths on the "
                          "device (structural.StructuralRefiner, two more launches per frame, inside the HIP graph with --graph 1)")
@@ -190,6 +211,8 @@ def main(argv=None):
         ap.error("--device-refine 1 holds given bone lengths fixed: it requires --bone-lengths FILE.npy")
     if args.device_track_motion and not args.device_track:
         ap.error("--device-track-motion 1 is an option of the device tracker: it requires --device-track 1")
+    if args.device_track_eval and not args.device_track:
+        ap.error("--device-track-eval 1 scores the ids of the device tracker: it requires --device-track 1")
     if args.device_eval and not args.device_nms:
         ap.error("--device-eval 1 scores the rows of the device NMS: it requires --device-nms 1")
     if args.device_track and not args.device_nms:
@@ -233,10 +256,26 @@ def main(argv=None):
             "pcp" if np.asarray(with_gt[0][0]).shape[-2] == len(conv) else None
         persons, gt_dev = device_ground_truth(frames, kind, j_out, dev)
         evaluation = dict(kind=kind or "panoptic", capacity=len(frames) * head.num_instance, max_persons=persons, actors=persons)
+    track_evaluation, track_gt = None, None
+    if args.device_track_eval:
+        if not any(f[2] is not None for f in frames):
+            raise SystemExit("--device-track-eval 1 scores the track ids against ground truth: no frame has joints_3d")
+        joints = {np.asarray(f[2][0]).shape[-2] for f in frames if f[2] is not None and len(f[2][0])}
+        if joints - {j_out}:
+            raise SystemExit("--device-track-eval 1: the ground truth has %s joints, the kept poses %d"
+                             % (sorted(joints), j_out))
+        if gt_dev is None:
+            persons, gt_dev = device_ground_truth(frames, "panoptic" if conv is None else "pcp", j_out, dev)
+        person_ids = None
+        if args.frames_npz and "person_ids" in np.load(args.frames_npz).files:
+            person_ids = np.load(args.frames_npz)["person_ids"]
+        track_gt = track_ground_truth(frames, gt_dev, person_ids, persons, dev)
+        track_evaluation = dict(dist_thr=500.0, max_persons=persons, max_ids=1024)
+        report["device_track_eval"] = True
     for thr in cfg.DECODER.inference_conf_thr:                                   # validate_3d.py:185
         preds, gts, gts_vis, t_dec, n_timed = [], [], [], 0.0, 0
         kept = []
-        runner, evaluator, nms_out, tracker, refiner = None, None, None, None, None
+        runner, evaluator, nms_out, tracker, refiner, track_scorer = None, None, None, None, None, None
         if refine is not None:
             refine_sums = torch.zeros(4, dtype=torch.float64, device=dev)        # kept rows, solved rows, residual before, after
         if (args.device_eval or args.device_track or args.device_refine) and not args.graph:
@@ -251,6 +290,9 @@ def main(argv=None):
             if args.device_track:                                                # a fresh tracker per threshold pass
                 from .tracking import PoseTracker
                 tracker = PoseTracker(batch=1, rows=head.num_instance, num_joints=j_out, device=dev, **tracking)
+            if args.device_track_eval:
+                from .tracking import TrackEvaluator
+                track_scorer = TrackEvaluator(batch=1, device=dev, **track_evaluation)
         for fi, (src, meta, gt) in enumerate(frames):
             src = [s.to(dev) for s in src]
             meta = to_device(meta, dev)
@@ -260,8 +302,8 @@ def main(argv=None):
                 runner = GraphedDecoder(head.decoder, meta, shapes, starts, 1, head.num_instance, thr,
                                         postprocess=dict(dist_thr=0.3, num_nearby_joints_thr=7) if args.device_nms else None,
                                         convert_joint_format_indices=head.convert_joint_format_indices, evaluation=evaluation,
-                                        tracking=tracking, refine=refine)
-                evaluator, tracker, refiner = runner.evaluator, runner.tracker, runner.refiner
+                                        tracking=tracking, refine=refine, track_evaluation=track_evaluation)
+                evaluator, tracker, refiner, track_scorer = runner.evaluator, runner.tracker, runner.refiner, runner.track_evaluator
                 qpos, tgt = caller.person_joint_queries(head.joint_embedding.weight, head.instance_embedding.weight, 1)
                 ref0 = caller.sample_space_reference_points(head.num_instance, head.space_size, head.space_center, 1, dev,
                                                             t_pose=head.t_pose)
@@ -269,7 +311,8 @@ def main(argv=None):
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             if runner is not None:
-                runner.set_cameras(meta).load(src_views=src, ground_truth=gt_dev[fi] if args.device_eval else None)
+                runner.set_cameras(meta).load(src_views=src, ground_truth=track_gt[fi] if args.device_track_eval else
+                                              gt_dev[fi] if args.device_eval else None)
                 hs, refs, r2d, p2d, cls = runner.replay()
                 if args.device_nms:
                     pred = runner.pred.clone()                                   # static buffer: the next replay overwrites it
@@ -296,6 +339,8 @@ def main(argv=None):
                     evaluator.update(dets, count, *gt_dev[fi])                   # launches only: nothing is read back per frame
                 if args.device_track:
                     tracker.update(dets, count)
+                if args.device_track_eval:
+                    track_scorer.update(tracker, dets, count, *track_gt[fi][:3], person_id=track_gt[fi][3])
             if refine is not None:                                               # device sums, read back once per threshold
                 from .structural import PANOPTIC15_PARENT, bone_lengths
                 poses, status = refiner.poses, refiner.status
@@ -329,6 +374,11 @@ def main(argv=None):
             if args.device_track_motion:                                         # mean joint speed of the live tracks, unit / frame
                 speeds = [float(np.linalg.norm(vel, axis=1).mean()) for vel, _ in tracker.motion()[0].values()]
                 row["track_motion"] = {"tracks": len(speeds), "mean_speed": round(sum(speeds) / max(len(speeds), 1), 3)}
+        if track_scorer is not None:                                             # the one read-back of the tracking scores
+            scores = track_scorer.report()
+            row["device_track_eval"] = {k: (round(v, 4) if isinstance(v, float) else v) for k, v in scores["total"].items()}
+            if "note" in scores:
+                row["device_track_eval"]["note"] = scores["note"]
         if refine is not None:
             n_live, n_solved, before, after = refine_sums.tolist()
             row["refine"] = {"kept_rows": int(n_live), "solved_share": round(n_solved / max(n_live, 1.0), 4),
