@@ -283,6 +283,14 @@ def _pcp_from_counters(correct, total, bone_correct, match_gt, total_gt):
 
 
 # --------------------------------------------------------------------------------------- scoring on the device
+def ground_truth_buffers(batch, max_persons, num_joints, device):
+    """zeroed static inputs (joints_3d, joints_3d_vis, num_person) for ``max_persons`` person slots: what ``DeviceEvaluator`` and
+    ``tracking.TrackEvaluator`` read under graph capture"""
+    z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=device)
+    return (z((batch, max_persons, num_joints, 3), torch.float32), z((batch, max_persons, num_joints), torch.float32),
+            z((batch,), torch.int32))
+
+
 class DeviceEvaluator:
     """``match_predictions`` (kind "panoptic") or the counters of ``evaluate_pcp`` (kind "pcp") accumulated in device memory by
     ``ops.eval_match`` / ``ops.eval_pcp``: ``update`` only launches (two launches / one, nothing read back, fixed shapes, so it can
@@ -308,9 +316,7 @@ class DeviceEvaluator:
 
     def ground_truth_buffers(self, batch, num_joints):
         """zeroed static inputs (joints_3d, joints_3d_vis, num_person) for ``max_persons`` person slots (graph capture)"""
-        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=self.device)
-        return (z((batch, self.max_persons, num_joints, 3), torch.float32), z((batch, self.max_persons, num_joints), torch.float32),
-                z((batch,), torch.int32))
+        return ground_truth_buffers(batch, self.max_persons, num_joints, self.device)
 
     def update(self, dets, count, joints_3d, joints_3d_vis, num_person):
         from . import ops
@@ -326,6 +332,19 @@ class DeviceEvaluator:
     def reset(self):
         for t in self.buffers.values():
             t.zero_()
+        return self
+
+    def tensors(self):
+        """every device tensor ``update`` addresses besides its arguments (what a captured graph must keep alive)"""
+        return list(self.buffers.values())
+
+    def snapshot(self):
+        """clones of the accumulators (``restore`` puts them back: a graph capture's warm-up forwards must count no frame)"""
+        return {k: t.clone() for k, t in self.buffers.items()}
+
+    def restore(self, saved):
+        for k, t in self.buffers.items():
+            t.copy_(saved[k])
         return self
 
     def state(self):

@@ -65,6 +65,10 @@ class StructuralRefiner:
     def status(self):
         return self.buffers["status"]
 
+    def tensors(self):
+        """every device tensor ``update`` addresses besides its arguments (what a captured graph must keep alive)"""
+        return list(self.buffers.values()) + [self.bone_lengths]
+
     def update(self, refs2d, cams, Pm, keep, count):
         """refs2d (B, V, NQ*J, 2) fp32 network-image px (the last layer's), cams the packed camera records, Pm (B, V, 3, 4) fp32, keep
         (B, NQ) int32 and count (B, 2) int32 as ``ops.pose_nms`` leaves them -> (poses, status), static tensors that the next update

@@ -100,6 +100,10 @@ class PoseTracker:
     def _all_buffers(self):
         return dict(self.buffers, **(self.motion_buffers or {}))
 
+    def tensors(self):
+        """every device tensor ``update`` addresses besides its arguments (what a captured graph must keep alive)"""
+        return list(self._all_buffers().values())
+
     def reset(self):
         """forget every track and counter (device fills)"""
         for k, t in self._all_buffers().items():
@@ -226,10 +230,9 @@ class TrackEvaluator:
     def ground_truth_buffers(self, batch, num_joints):
         """zeroed static inputs (joints_3d, joints_3d_vis, num_person, person_id) for ``max_persons`` person slots (graph capture);
         person_id is the identity map, slot g = identity g"""
-        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=self.device)         # noqa: E731
+        from .evaluate import ground_truth_buffers
         ident = torch.arange(self.max_persons, dtype=torch.int32, device=self.device).repeat(batch, 1).contiguous()
-        return (z((batch, self.max_persons, num_joints, 3), torch.float32), z((batch, self.max_persons, num_joints), torch.float32),
-                z((batch,), torch.int32), ident)
+        return (*ground_truth_buffers(batch, self.max_persons, num_joints, self.device), ident)
 
     def update(self, tracker, dets, count, joints_3d, joints_3d_vis, num_person, person_id=None):
         """score the frame ``tracker.update(dets, count)`` has just associated: the tracker's ids (and, with its motion model, its
@@ -249,6 +252,10 @@ class TrackEvaluator:
         for k, t in self.buffers.items():
             t.fill_(-1 if k == "last_track" else 0)
         return self
+
+    def tensors(self):
+        """every device tensor ``update`` addresses besides its arguments (what a captured graph must keep alive)"""
+        return list(self.buffers.values())
 
     def snapshot(self):
         """clones of the state buffers (``restore`` puts them back: a graph capture's warm-up forwards must count no frame)"""

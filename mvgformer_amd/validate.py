@@ -23,6 +23,8 @@ poses under the J-1 bone lengths of the file (mm) by structural triangulation (`
 graph with ``--graph 1``) and reports the share of kept rows it solved and their mean absolute bone-length residual
 before and after.  ``--device-track-eval 1`` (on top of ``--device-track 1``) scores the track ids against the ground-truth
 identities of frames that carry ``joints_3d`` (``tracking.TrackEvaluator``: CLEAR-MOT counts, MOTA, MOTP, IDF1 per threshold).
+All of these stages are one ``postprocess.PostProcess`` per threshold, in both modes: the runner's (``runner.post``) with
+``--graph 1``, one built from the same options and run behind the eager head with ``--graph 0``.
 """
 from __future__ import annotations
 
@@ -235,11 +237,11 @@ def main(argv=None):
                                 "n_ignored_keys_of_other_modules": len(ignored)}
     frames = list(npz_frames(args.frames_npz) if args.frames_npz else synthetic_frames(cfg, args.frames, args.seed))
     results = []
-    from . import caller
+    from . import caller, ops
+    from .postprocess import PostProcess
     from .serving import GraphedDecoder
     conv = getattr(cfg.DECODER, "convert_joint_format_indices", None)
     evaluation, gt_dev = None, None
-    from . import ops
     j_out = head.num_joints if conv is None else len(conv)
     tracking = dict(max_tracks=32, max_dist=500.0, max_misses=10, min_hits=1) if args.device_track else None
     if args.device_track_motion:
@@ -272,38 +274,27 @@ def main(argv=None):
         track_gt = track_ground_truth(frames, gt_dev, person_ids, persons, dev)
         track_evaluation = dict(dist_thr=500.0, max_persons=persons, max_ids=1024)
         report["device_track_eval"] = True
+    # the device stages behind the decoder (postprocess.PostProcess; its NMS defaults are validate_3d's 0.3 m / 7 joints) and the
+    # ground truth they read, per frame
+    stages = dict(postprocess={} if args.device_nms else None, convert_joint_format_indices=head.convert_joint_format_indices,
+                  evaluation=evaluation, tracking=tracking, refine=refine, track_evaluation=track_evaluation)
+    truths = track_gt or gt_dev
     for thr in cfg.DECODER.inference_conf_thr:                                   # validate_3d.py:185
         preds, gts, gts_vis, t_dec, n_timed = [], [], [], 0.0, 0
         kept = []
-        runner, evaluator, nms_out, tracker, refiner, track_scorer = None, None, None, None, None, None
+        runner, post = None, None               # post: fresh stages (tracker, accumulators) per threshold pass
         if refine is not None:
             refine_sums = torch.zeros(4, dtype=torch.float64, device=dev)        # kept rows, solved rows, residual before, after
-        if (args.device_eval or args.device_track or args.device_refine) and not args.graph:
-            nms_out = ops.pose_nms_buffers(1, head.num_instance, j_out, None, dev)
-            if args.device_refine:                                               # the eager form of GraphedDecoder(refine=...)
-                from .structural import StructuralRefiner
-                if conv is not None:
-                    raise ValueError("--device-refine 1 solves on the 15-joint tree: not with convert_joint_format_indices")
-                refiner = StructuralRefiner(batch=1, rows=head.num_instance, device=dev, **refine)
-            if args.device_eval:
-                evaluator = E.DeviceEvaluator(device=dev, **evaluation)
-            if args.device_track:                                                # a fresh tracker per threshold pass
-                from .tracking import PoseTracker
-                tracker = PoseTracker(batch=1, rows=head.num_instance, num_joints=j_out, device=dev, **tracking)
-            if args.device_track_eval:
-                from .tracking import TrackEvaluator
-                track_scorer = TrackEvaluator(batch=1, device=dev, **track_evaluation)
+        if args.device_nms and not args.graph:
+            post = PostProcess(1, head.num_instance, head.num_joints, thr, dev, **stages)
         for fi, (src, meta, gt) in enumerate(frames):
             src = [s.to(dev) for s in src]
             meta = to_device(meta, dev)
             if args.graph and runner is None:
                 # queries and initial poses do not depend on the frame (dq_transformer.py:394-432, 298-323): loaded once
                 shapes, starts = caller.level_tables(src)
-                runner = GraphedDecoder(head.decoder, meta, shapes, starts, 1, head.num_instance, thr,
-                                        postprocess=dict(dist_thr=0.3, num_nearby_joints_thr=7) if args.device_nms else None,
-                                        convert_joint_format_indices=head.convert_joint_format_indices, evaluation=evaluation,
-                                        tracking=tracking, refine=refine, track_evaluation=track_evaluation)
-                evaluator, tracker, refiner, track_scorer = runner.evaluator, runner.tracker, runner.refiner, runner.track_evaluator
+                runner = GraphedDecoder(head.decoder, meta, shapes, starts, 1, head.num_instance, thr, **stages)
+                post = runner.post
                 qpos, tgt = caller.person_joint_queries(head.joint_embedding.weight, head.instance_embedding.weight, 1)
                 ref0 = caller.sample_space_reference_points(head.num_instance, head.space_size, head.space_center, 1, dev,
                                                             t_pose=head.t_pose)
@@ -311,8 +302,7 @@ def main(argv=None):
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             if runner is not None:
-                runner.set_cameras(meta).load(src_views=src, ground_truth=track_gt[fi] if args.device_track_eval else
-                                              gt_dev[fi] if args.device_eval else None)
+                runner.set_cameras(meta).load(src_views=src, ground_truth=truths[fi] if truths else None)
                 hs, refs, r2d, p2d, cls = runner.replay()
                 if args.device_nms:
                     pred = runner.pred.clone()                                   # static buffer: the next replay overwrites it
@@ -327,37 +317,24 @@ def main(argv=None):
                 t_dec += time.perf_counter() - t0
                 n_timed += 1
             preds.extend(p for p in pred)
-            if nms_out is not None:                                              # with --graph 1 the replay has done it all
-                with torch.cuda.device(dev):
-                    keep, count, dets = ops.pose_nms(pred.contiguous(), 0.3, 7, out=nms_out)
-                    if refiner is not None:
-                        from .geometry_torch import proj_matrices_from_records
-                        cams = ops.pack_cameras(meta, head.decoder.layers[0].img_size, dev)
-                        refiner.update(out["pred_poses_2d"]["outputs_coord_2d"].contiguous(), cams,
-                                       proj_matrices_from_records(cams, len(meta), 1).contiguous(), keep, count)
-                if args.device_eval:
-                    evaluator.update(dets, count, *gt_dev[fi])                   # launches only: nothing is read back per frame
-                if args.device_track:
-                    tracker.update(dets, count)
-                if args.device_track_eval:
-                    track_scorer.update(tracker, dets, count, *track_gt[fi][:3], person_id=track_gt[fi][3])
+            if post is not None and runner is None:                              # with --graph 1 the replay has done it all
+                with torch.cuda.device(dev):                                     # launches only: nothing is read back per frame
+                    post.set_cameras(ops.pack_cameras(meta, head.decoder.layers[0].img_size, dev), len(meta))
+                    if truths:
+                        post.load_ground_truth(truths[fi])
+                    post.run_packed(pred.contiguous(), out["pred_poses_2d"]["outputs_coord_2d"])
             if refine is not None:                                               # device sums, read back once per threshold
                 from .structural import PANOPTIC15_PARENT, bone_lengths
-                poses, status = refiner.poses, refiner.status
-                dets, count = (runner.detections[0], runner.detections[1]) if runner is not None else (nms_out["dets"], nms_out["count"])
+                (poses, status), (dets, count, _) = post.refined, post.detections
                 live = torch.arange(poses.shape[1], device=dev)[None] < count[:, :1]
                 solved = live & (status == 0)
-                want = refiner.bone_lengths.double()
+                want = post.bone_lengths.double()
                 before = (bone_lengths(dets[..., :3].double(), PANOPTIC15_PARENT) - want).abs().mean(-1)
                 after = (bone_lengths(poses.double(), PANOPTIC15_PARENT) - want).abs().mean(-1)
                 refine_sums += torch.stack([live.sum(), solved.sum(), (before * solved).sum(), (after * solved).sum()])
-            if args.device_eval:
-                pass
-            elif args.device_nms and runner is not None:
-                dets, count, _ = runner.detections                               # static buffers, filled by the replayed graph
+            if args.device_nms and not args.device_eval:
+                dets, count, _ = post.detections                                 # static buffers, overwritten by the next frame
                 kept.extend(dets[b, :k].clone() for b, k in enumerate(count[:, 0].tolist()))   # the frame's one read-back
-            elif args.device_nms:
-                kept.extend(E.filter_and_nms_device(pred))
             if gt is not None:
                 gts.append(gt[0])
                 gts_vis.append(gt[1])
@@ -365,17 +342,17 @@ def main(argv=None):
             kept = [E.filter_and_nms(p) for p in preds]                          # validate_3d.py:228-234 (0.3 m, 7 joints)
         row = {"inference_conf_thr": thr, "frames": len(preds),
                "candidates_above_thr": int(sum(int((p[:, 0, 3] >= 0).sum()) for p in preds)),
-               "poses_after_nms": evaluator.state()["kept_rows"] if args.device_eval else int(sum(len(k) for k in kept)),
+               "poses_after_nms": post.evaluator.state()["kept_rows"] if args.device_eval else int(sum(len(k) for k in kept)),
                "decoder_ms_per_frame": round(1e3 * t_dec / max(n_timed, 1), 3),    # host-timed, incl. the camera H2D copy
                "hip_graph": runner is not None}
-        if tracker is not None:
-            st = tracker.state()
+        if args.device_track:
+            st = post.tracker.state()
             row["tracks"] = {k: st[k] for k in ("births", "deaths", "overflow", "dropped", "active")}
             if args.device_track_motion:                                         # mean joint speed of the live tracks, unit / frame
-                speeds = [float(np.linalg.norm(vel, axis=1).mean()) for vel, _ in tracker.motion()[0].values()]
+                speeds = [float(np.linalg.norm(vel, axis=1).mean()) for vel, _ in post.tracker.motion()[0].values()]
                 row["track_motion"] = {"tracks": len(speeds), "mean_speed": round(sum(speeds) / max(len(speeds), 1), 3)}
-        if track_scorer is not None:                                             # the one read-back of the tracking scores
-            scores = track_scorer.report()
+        if args.device_track_eval:                                               # the one read-back of the tracking scores
+            scores = post.track_evaluator.report()
             row["device_track_eval"] = {k: (round(v, 4) if isinstance(v, float) else v) for k, v in scores["total"].items()}
             if "note" in scores:
                 row["device_track_eval"]["note"] = scores["note"]
@@ -386,9 +363,9 @@ def main(argv=None):
                              "bone_residual_mm_after": round(after / max(n_solved, 1.0), 4)}
         if gts and conv is not None:
             if np.asarray(gts[0]).shape[-2] == len(conv):
-                row["PCP"] = pcp_report(kept, gts, gts_vis, evaluator if args.device_eval else None)   # shelf.py:255-330
+                row["PCP"] = pcp_report(kept, gts, gts_vis, post.evaluator if args.device_eval else None)   # shelf.py:255-330
         elif gts:
-            aps, recs, mpjpe, recall500 = evaluator.panoptic() if args.device_eval else \
+            aps, recs, mpjpe, recall500 = post.evaluator.panoptic() if args.device_eval else \
                 E.evaluate_panoptic(kept, gts, gts_vis)                          # panoptic.py:493-574
             row.update(AP={str(t): round(100 * a, 2) for t, a in zip(E.MPJPE_THRESHOLDS, aps)},
                        recall={str(t): round(100 * r, 2) for t, r in zip(E.MPJPE_THRESHOLDS, recs)},

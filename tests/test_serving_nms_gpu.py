@@ -47,7 +47,7 @@ def test_postprocess_in_the_graph_equals_the_host_path():
         torch.cuda.synchronize()
         assert _eq(got_out, want_out), i                                # the same five tensors, bit for bit
         dets, count, keep = post.detections
-        assert all(t.data_ptr() in [p.data_ptr() for p in post._pinned] for t in (dets, count, keep, post._nms["workspace"]))
+        assert all(t.data_ptr() in [p.data_ptr() for p in post._pinned] for t in (dets, count, keep, post.post.nms["workspace"]))
         pred = post.pred[0].cpu()
         assert tuple(post.pred.shape) == (1, c.NQ, 15, 5)
         want = E.filter_and_nms(pred.clone())
@@ -93,7 +93,7 @@ def _comparable(rep, drop=()):
 @pytest.mark.parametrize("graph", [1, 0])
 def test_validate_reports_are_equal_with_and_without_device_nms(graph):
     """the same synthetic frames through validate.main: every field but `device_nms` and the timing is equal; with --graph 1 the
-    kept poses come from the graph's static buffers, with --graph 0 from evaluate.filter_and_nms_device"""
+    kept poses come from the graph's static buffers, with --graph 0 from those of a postprocess.PostProcess behind the eager head"""
     host, dev = _report(1, 0), _report(graph, 1)
     assert host["device_nms"] is False and dev["device_nms"] is True
     assert dev["results"][0]["hip_graph"] is bool(graph)

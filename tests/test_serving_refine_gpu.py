@@ -59,14 +59,14 @@ def test_refine_in_the_graph():
     assert plain.refined is None and plain.refiner is None and plain.bone_lengths is None
     poses, status = fine.refined
     assert tuple(poses.shape) == (1, c.NQ, 15, 3) and tuple(status.shape) == (1, c.NQ) and tuple(fine.bone_lengths.shape) == (14,)
-    graphs, solved, pm_ptr, pm_seen = set(), 0, fine._Pm.data_ptr(), []
+    graphs, solved, pm_ptr, pm_seen = set(), 0, fine.post.Pm.data_ptr(), []
     for i, c in enumerate(cases):
         for run in (plain, fine):
             run.set_cameras(c.meta)
             run.load(src_views=c.src_views, tgt=c.tgt, query_pos=c.query_pos, reference_points=c.reference_points)
         # set_cameras refilled the static projection matrices in place
-        assert torch.equal(fine._Pm, proj_matrices_from_records(fine.ctx.cams, fine.V, 1)) and fine._Pm.data_ptr() == pm_ptr
-        pm_seen.append(fine._Pm.clone())
+        assert torch.equal(fine.post.Pm, proj_matrices_from_records(fine.ctx.cams, fine.V, 1)) and fine.post.Pm.data_ptr() == pm_ptr
+        pm_seen.append(fine.post.Pm.clone())
         want_out = _clone(plain.replay())
         want_pred, want_dets = plain.pred.clone(), [t.clone() for t in plain.detections]
         got_out = fine.replay()
@@ -75,7 +75,7 @@ def test_refine_in_the_graph():
         # the decoder's outputs, pred and the detections are those of a runner without refine, bit for bit
         assert _eq(got_out, want_out) and torch.equal(_bits(fine.pred), _bits(want_pred))
         assert all(torch.equal(_bits(a), _bits(b)) for a, b in zip(fine.detections, want_dets))
-        assert all(t.data_ptr() in [p.data_ptr() for p in fine._pinned] for t in (poses, status, fine.bone_lengths, fine._Pm))
+        assert all(t.data_ptr() in [p.data_ptr() for p in fine._pinned] for t in (poses, status, fine.bone_lengths, fine.post.Pm))
         k = int(fine.detections[1][0, 0])
         first = (poses.clone(), status.clone())
         (eager_X, eager_s), (ref_X, ref_s) = _restated(fine, LENGTHS)
