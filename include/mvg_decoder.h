@@ -187,7 +187,9 @@ int mvg_gather_ref(const void* feat, int dtype, const float* ref_lvl, const floa
  * dtype: bf16 weights -> bf16 MFMA, A converted on load; f32 weights -> fp32 products, formed either as six bf16 MFMAs on
  * operands split into three bf16 parts (default; fp32 accuracy, not bitwise an fmaf chain; Inf / > 3.39e38 inputs give NaN)
  * or as v_mfma_f32_32x32x2_f32 (mvg_set_tuning("f32_split", 0): bitwise an fp32 fmaf chain)).
- * relu: 0/1.  rowmask: NULL or uint8 (M).  lda/ldc in elements. */
+ * relu: 0/1.  rowmask: NULL or uint8 (M).  lda/ldc in elements.
+ * Per element: x = acc + bias; relu; rowmask ? x : 0; rounding to out_dtype (bf16: nearest even).  relu is torch.relu's: a NaN
+ * stays a NaN; a non-finite value of A reaches its own output row only; a row with rowmask 0 is +0 whatever its inputs hold. */
 int mvg_linear(const void* A, int a_dtype, int lda, const void* W, int w_dtype,
                const float* bias, void* out, int out_dtype, int ldc,
                const uint8_t* rowmask, int relu, int M, int N, int K, void* stream);

@@ -20,6 +20,13 @@
 // slab is permuted identically for A and W, which leaves the sum unchanged), a bf16 lane gets
 // k = 16g+8h..+7 (one 32x32x16 MFMA).
 // Global->register prefetch of slab t+1 overlaps the MFMAs of slab t.
+//
+// Epilogue, per element:  x = acc + bias;  relu;  keep ? x : 0;  round to the output type (bf16: nearest even).
+// Non-finite values (tests/test_bf16_gemm_fp64.py): a NaN or Inf in A reaches the output row of its own row and no other (rows past
+// the end of a tile re-read the tile's last row, and a row of A only reaches its row of the product).  The ReLU is torch.relu's,
+// as the oracle and the torch form of functions.linear have it: relu(NaN) = NaN -- the IEEE 754-2019 maximum, not fmaxf, which returns 0 for
+// a NaN and turned a diverged row back into a finite one.  The row mask is a select, not a product: a masked row is +0 in every
+// column whatever its inputs hold, NaN included (the consumers mask rows whose inputs are not meaningful).
 #include "common.h"
 
 int g_linear_tiles = 1;     // tuning knob "linear_tiles": 0 = always 128 x 128 tiles (rounds 1-2)
@@ -328,7 +335,7 @@ __global__ __launch_bounds__(256, (BN > 128 ? 2 : (SPLIT ? 3 : 1))) void linear_
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
           float x = acc[i][j][4 * g + t] + bq[t];
-          if (relu) x = fmaxf(x, 0.f);
+          if (relu) x = __builtin_elementwise_maximum(x, 0.f);   // IEEE 754-2019 maximum: keeps a NaN (fmaxf(NaN, 0) is 0)
           v[t] = keep ? x : 0.f;
         }
         char* dst = lds + (wm * 32 + rl) * EP + nl * (int)sizeof(TO);
