@@ -2,102 +2,93 @@
 
 There is NO CPU fallback: if the shared library is missing or a call fails, the product
 path raises.  torch is used only to own device memory and the current HIP stream.
+
+The header is the one declaration: the argument and return types of every entry point
+(SIGNATURES, PROTOTYPES) and the numeric limits and codes (DEFINES) are read from it at
+import, so a new entry point is bound by declaring it there.
 """
 from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # MVG_LIB: another build of the same library (measurement variants of tools/ab_*.sh); the product never sets it
 LIB_PATH = os.environ.get("MVG_LIB") or os.path.join(_HERE, "libmvgformer_hip.so")
-
-MVG_F32, MVG_BF16 = 0, 1
-CAM_STRIDE = 48
-
-_vp, _i, _f = C.c_void_p, C.c_int, C.c_float
-
-# name -> argtypes (restype is always int unless noted); must list EVERY symbol of the header
-SIGNATURES = {
-    "mvg_device_info": [C.c_char_p, _i, C.POINTER(_i)],
-    "mvg_set_tuning": [C.c_char_p, _i],
-    "mvg_msda_forward_f32": [_vp] * 6 + [_i] * 7 + [_vp],
-    "mvg_msda_forward_bf16": [_vp] * 6 + [_i] * 7 + [_vp],
-    "mvg_msda_backward_f32": [_vp] * 9 + [_i] * 7 + [_vp],
-    "mvg_msda_backward_det_workspace": [_i] * 7 + [_vp],
-    "mvg_msda_backward_det_f32": [_vp] * 9 + [_i] * 7 + [_vp, C.c_size_t, _vp],
-    "mvg_msda_backward_det_bf16": [_vp] * 9 + [_i] * 7 + [_vp, C.c_size_t, _vp],
-    "mvg_msda_backward_bal_workspace": [_i] * 7 + [_vp, _i],
-    "mvg_msda_backward_bal_f32": [_vp] * 9 + [_i] * 7 + [_vp, C.c_size_t, _vp, _i],
-    "mvg_msda_backward_bal_bf16": [_vp] * 9 + [_i] * 7 + [_vp, C.c_size_t, _vp, _i],
-    "mvg_msda_forward_f64": [_vp] * 6 + [_i] * 7 + [_vp],
-    "mvg_msda_backward_f64": [_vp] * 9 + [_i] * 7 + [_vp],
-    "mvg_pack_pyramid": [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _vp],
-    "mvg_project": [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp],
-    "mvg_gather_ref": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
-    "mvg_linear": [_vp, _i, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _vp],
-    "mvg_dlt_forward": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
-    "mvg_dlt_backward": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
-    "mvg_linear_wgrad_bias_f32": [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
-    "mvg_linear_wgrad_bias_bf16": [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
-    "mvg_linear_ordered": [_vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
-    "mvg_linear_sum": [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _vp],
-    "mvg_msda_fused": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
-    "mvg_msda_gfused_f32": [_vp] * 9 + [_i] * 5 + [_vp],
-    "mvg_chain_attn_pose": [_vp] * 14 + [_i, _vp],
-    "mvg_chain_update_ffn_class": [_vp, _i] + [_vp] * 13 + [_f] + [_vp] * 9 + [_i] * 5 + [_vp, _vp],
-    "mvg_chain_update_ffn_class_f32h": [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, C.c_float, _vp,
-                                        _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp],
-    "mvg_chain_attn_pose_f32h": [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp],
-    "mvg_pyramid_f32h": [_vp, _vp, _i, _vp, _vp, _i, _vp, _vp, C.c_int64, _i, _vp],
-    "mvg_pyramid_group_ws": [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp],
-    "mvg_msda_gsamp": [_vp] * 9 + [_i] * 5 + [_vp],
-    "mvg_bin_pairs": [_vp] * 3 + [_i] + [_vp] + [_i] * 2 + [_vp, C.c_size_t, _vp],
-    "mvg_bin_pairs_workspace": [_i, _i],
-    "mvg_mean_views": [_vp, _i, _vp, _i, _i, _i, _vp],
-    "mvg_add_layernorm": [_vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp],
-    "mvg_class_head": [_vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
-    "mvg_rowdot3": [_vp, _i, _vp, _vp, _vp, _i, _i, _vp],
-    "mvg_triangulate": [_vp] * 8 + [_i] * 4 + [_vp],
-    "mvg_triangulate_project": [_vp] * 8 + [_i] * 4 + [_vp, _i] + [_vp] * 4,
-    "mvg_uncrop_undistort_jac": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp],
-    "mvg_sym4_eigh": [_vp] * 3 + [C.c_long, _vp],
-    "mvg_knn_match_workspace": [_i] * 3,
-    "mvg_knn_match": [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _f] + [_i] * 5 + [_vp, C.c_size_t] + [_vp] * 5,
-    "mvg_knn_match_jm": [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _f] + [_i] * 5 + [_vp, _i, _vp, C.c_size_t] + [_vp] * 5,
-    "mvg_hungarian_match_workspace": [_i] * 3,
-    "mvg_hungarian_match": [_vp] * 4 + [_i, _vp, _vp, _i, _f, _f] + [_i] * 6 + [_vp, _vp, C.c_size_t] + [_vp] * 6,
-    "mvg_criterion_workspace": [_i] * 5,
-    "mvg_criterion": [_vp] * 10 + [_i] + [_vp] * 4 + [_f] * 3 + [_i] * 7 + [_vp, C.c_size_t] + [_vp] * 5,
-    "mvg_criterion_jm": [_vp] * 10 + [_i] + [_vp] * 4 + [_f] * 3 + [_i] * 5 + [_vp] + [_i] * 3 + [_vp, C.c_size_t] + [_vp] * 5,
-    "mvg_optim_workspace": [_i],
-    "mvg_optim_step": [_vp, _i, _vp, _i, _vp, _i, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _f, _i, _vp, _vp],
-    "mvg_refresh_operands": [_vp, _i, _vp, _i, _vp],
-    "mvg_pose_nms_workspace": [_i] * 3,
-    "mvg_self_attention": [_vp] * 4 + [_i] * 8 + [_vp],
-    "mvg_self_attention_train": [_vp] * 5 + [_i] * 8 + [_f, _vp, _vp],
-    "mvg_self_attention_backward_workspace": [_i, _i],
-    "mvg_self_attention_backward": [_vp] * 9 + [_i] * 11 + [_f, _vp, _vp, C.c_size_t, _vp],
-    "mvg_self_attention_dropout_mask": [_vp, _i, _i, _f, _vp, _vp],
-    "mvg_pose_nms": [_vp, _i, _i, _i, C.c_double, _i, _i, _vp, C.c_size_t, _vp, _vp, _vp, _i, _vp],
-    "mvg_eval_match": [_vp] * 5 + [_i] * 4 + [_vp] * 3 + [C.c_int64, _vp, _vp],
-    "mvg_eval_pcp": [_vp] * 5 + [_i] * 5 + [C.c_double] * 2 + [_vp] * 5,
-    "mvg_linear_assignment": [_vp] * 3 + [_i] * 3 + [_vp] * 3,
-    "mvg_track_update": [_vp] * 2 + [_i] * 4 + [_vp] * 8 + [C.c_double, _i, _i] + [_vp] * 3,
-    "mvg_track_predict": [_i] * 3 + [_vp] * 4 + [C.c_double] * 2 + [_vp],
-    "mvg_track_correct": [_i] * 4 + [_vp] * 7 + [C.c_double] * 2 + [_vp] * 2,
-    "mvg_track_eval": [_vp] * 8 + [_i] * 6 + [C.c_double] + [_vp] * 7,
-    "mvg_structural_triangulate": [_vp] * 5 + [_i] + [_vp] * 3 + [_i] * 3 + [_vp] * 2 + [_i] * 5 + [_vp],
-}
-
-_lib = None
-TUNING = {}     # knob values set through mvg_set_tuning in this process (library defaults are not listed)
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mvg_decoder.h")
 
 
 class MvgError(RuntimeError):
     pass
+
+
+class TensorPtr(C.c_void_p):
+    """argtype of every pointer parameter but char*: a torch.Tensor passes its data_ptr() (0 = NULL); None, an int, a c_void_p, a
+    ctypes array or byref() go through as for c_void_p"""
+
+    @classmethod
+    def from_param(cls, value):
+        if isinstance(value, torch.Tensor):
+            value = value.data_ptr() or None
+        return C.c_void_p.from_param(value)
+
+
+_SCALARS = {"int": C.c_int, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t, "int64_t": C.c_int64, "long": C.c_long,
+            "char*": C.c_char_p}
+
+
+def _ctype(text, decl, pointers=True):
+    t = re.sub(r"\bconst\b|\s+", "", text)
+    if t in _SCALARS:
+        return _SCALARS[t]
+    if pointers and re.fullmatch(r"\w+\*+", t):
+        return TensorPtr
+    raise MvgError("mvg_decoder.h: unknown type %r in %r" % (text.strip(), decl))
+
+
+def parse_header(text):
+    """-> (prototypes: name -> (restype, [(argtype, parameter name), ...]), defines: MVG_* name -> int | float) of the C ABI's
+    header.  A statement that is not a prototype of known types, or an MVG_* define that is not a number, raises MvgError."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    defines = {}
+    for name, value in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(MVG_\w+)[ \t]+(\S.*?)[ \t]*$", text, flags=re.M):
+        try:
+            defines[name] = int(value, 0)
+        except ValueError:
+            try:
+                defines[name] = float(value)
+            except ValueError:
+                raise MvgError("mvg_decoder.h: #define %s %s is not a number" % (name, value)) from None
+    text = re.sub(r'^[ \t]*#.*$|extern\s+"C"\s*\{|^[ \t]*\}[ \t]*$', "", text, flags=re.M)
+    protos = {}
+    for decl in filter(None, (" ".join(d.split()) for d in text.split(";"))):
+        m = re.fullmatch(r"(.+?)\b(mvg_\w+) ?\((.*)\)", decl)
+        if not m:
+            raise MvgError("mvg_decoder.h: cannot read %r" % decl)
+        params = []
+        for p in ([] if m.group(3).strip() == "void" else m.group(3).split(",")):
+            pm = re.fullmatch(r"(.+?)(\w+)", p.strip())
+            if not pm:
+                raise MvgError("mvg_decoder.h: cannot read parameter %r of %r" % (p.strip(), decl))
+            params.append((_ctype(pm.group(1), decl), pm.group(2)))
+        protos[m.group(2)] = (_ctype(m.group(1), decl, pointers=False), params)
+    return protos, defines
+
+
+with open(HEADER_PATH) as _f:
+    PROTOTYPES, DEFINES = parse_header(_f.read())
+# name -> argtypes of EVERY symbol of the header (the restype is PROTOTYPES[name][0])
+SIGNATURES = {name: [t for t, _ in params] for name, (_, params) in PROTOTYPES.items()}
+# the entry points whose last parameter is the stream (ops._launch appends it)
+STREAM_LAST = frozenset(name for name, (_, params) in PROTOTYPES.items() if params and params[-1][1] == "stream")
+MVG_F32, MVG_BF16 = DEFINES["MVG_F32"], DEFINES["MVG_BF16"]
+CAM_STRIDE = DEFINES["MVG_CAM_STRIDE"]
+
+_lib = None
+TUNING = {}     # knob values set through mvg_set_tuning in this process (library defaults are not listed)
 
 
 def load():
@@ -113,18 +104,7 @@ def load():
     for name, argtypes in SIGNATURES.items():
         fn = getattr(lib, name)   # AttributeError if the symbol is missing
         fn.argtypes = argtypes
-        fn.restype = C.c_int
-    lib.mvg_version.restype = C.c_char_p
-    lib.mvg_bin_pairs_workspace.restype = C.c_size_t
-    lib.mvg_msda_backward_det_workspace.restype = C.c_size_t
-    lib.mvg_msda_backward_bal_workspace.restype = C.c_size_t
-    lib.mvg_knn_match_workspace.restype = C.c_size_t
-    lib.mvg_hungarian_match_workspace.restype = C.c_size_t
-    lib.mvg_criterion_workspace.restype = C.c_size_t
-    lib.mvg_optim_workspace.restype = C.c_size_t
-    lib.mvg_pose_nms_workspace.restype = C.c_size_t
-    lib.mvg_self_attention_backward_workspace.restype = C.c_size_t
-    lib.mvg_version.argtypes = []
+        fn.restype = PROTOTYPES[name][0]
     # every knob change goes through this wrapper, so that host-side caches that depend on a knob (DQDecoderLayer's rows of
     # all-masked tiles: computed by the GEMM form that is active) can key on its value: TUNING[key] = last value set
     raw_set = lib.mvg_set_tuning

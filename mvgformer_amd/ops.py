@@ -14,6 +14,8 @@ import torch
 
 from . import _lib as L
 
+_D = L.DEFINES      # the numeric #defines of include/mvg_decoder.h: every limit and code below takes its value from there
+
 # backward of the sampling op: "det" = deterministic tile-binned form where the shape allows (D = 32), "atomic" = always the
 # fp32-atomics form of round 1 (the reference's own scheme), "balanced" = the deterministic form with its reduce step launched over
 # (bin, chunk) work items (mvg_msda_backward_bal_*: det's bits, a time that does not depend on where the samples fall)
@@ -24,17 +26,17 @@ BACKWARD_CHUNK = None
 
 
 def _det_entry(lib, bf16, dims, shapes_c):
-    """(function, name, workspace bytes, trailing arguments) of the deterministic backward that BACKWARD_MODE selects; workspace
-    bytes 0: the shape is not supported, the caller falls back to the atomic kernel."""
+    """(symbol, workspace bytes, trailing arguments) of the deterministic backward that BACKWARD_MODE selects; workspace bytes 0:
+    the shape is not supported, the caller falls back to the atomic kernel."""
     kind = "bf16" if bf16 else "f32"
     if BACKWARD_MODE == "balanced":
         chunk = 0 if BACKWARD_CHUNK is None else int(BACKWARD_CHUNK)
         if chunk < 0 or chunk % 256:
             raise L.MvgError("BACKWARD_CHUNK must be None, 0 or a positive multiple of 256 (got %r)" % (BACKWARD_CHUNK,))
-        name = "mvg_msda_backward_bal_" + kind
-        return getattr(lib, name), name, int(lib.mvg_msda_backward_bal_workspace(*dims, shapes_c, chunk)), (chunk,)
-    name = "mvg_msda_backward_det_" + kind
-    return getattr(lib, name), name, int(lib.mvg_msda_backward_det_workspace(*dims, shapes_c)), ()
+        # the chunk follows the stream in this prototype, so the stream is passed here
+        return ("mvg_msda_backward_bal_" + kind, int(lib.mvg_msda_backward_bal_workspace(*dims, shapes_c, chunk)),
+                (L.stream_ptr(), chunk))
+    return "mvg_msda_backward_det_" + kind, int(lib.mvg_msda_backward_det_workspace(*dims, shapes_c)), ()
 
 
 # ---- optional per-launch timing with HIP events on the launch stream (bench.py roofline) -----
@@ -56,6 +58,21 @@ class _timed:
             self.e.record()
             PROFILE.setdefault(self.name, []).append((self.s, self.e))
         return False
+
+
+def _launch(symbol, *args, label=None):
+    """The one way this module enqueues an entry point of the library: tensors (and None) are passed as they are (L.TensorPtr),
+    the current stream is appended where the prototype ends in it, the launch is timed under ``label`` (the key of bench.py's
+    per-kernel records; None: not timed) and a non-zero return code raises."""
+    fn = getattr(L.load(), symbol)
+    if symbol in L.STREAM_LAST:
+        args += (L.stream_ptr(),)
+    if label is None:
+        rc = fn(*args)
+    else:
+        with _timed(label):
+            rc = fn(*args)
+    L.check(rc, symbol)
 
 
 def profile_summary():
@@ -121,27 +138,24 @@ def msda_forward(value, spatial_shapes, level_start_index, sampling_loc, attn_we
         raise RuntimeError("spatial_shapes / level_start_index must be int64")
     N, S, M, D = value.shape
     _, Lq, _, nl, P, _ = sampling_loc.shape
-    lib = L.load()
+    L.load()
     out = torch.empty((N, Lq, M * D), dtype=value.dtype, device=value.device)
     if Lq == 0:
         return out
     if value.dtype == torch.float32:
         if sampling_loc.dtype != torch.float32 or attn_weight.dtype != torch.float32:
             raise RuntimeError("sampling_loc / attn_weight must be float32")
-        rc = lib.mvg_msda_forward_f32(L.ptr(value), L.ptr(spatial_shapes), L.ptr(level_start_index), L.ptr(sampling_loc),
-                                      L.ptr(attn_weight), L.ptr(out), N, S, M, D, nl, Lq, P, L.stream_ptr())
+        symbol = "mvg_msda_forward_f32"
     elif value.dtype == torch.float64:      # AT_DISPATCH_FLOATING_TYPES' double case (deform_cuda.cu:75)
         if sampling_loc.dtype != torch.float64 or attn_weight.dtype != torch.float64:
             raise RuntimeError("sampling_loc / attn_weight must be float64")
-        rc = lib.mvg_msda_forward_f64(L.ptr(value), L.ptr(spatial_shapes), L.ptr(level_start_index), L.ptr(sampling_loc),
-                                      L.ptr(attn_weight), L.ptr(out), N, S, M, D, nl, Lq, P, L.stream_ptr())
+        symbol = "mvg_msda_forward_f64"
     elif value.dtype == torch.bfloat16:
-        rc = lib.mvg_msda_forward_bf16(L.ptr(value), L.ptr(spatial_shapes), L.ptr(level_start_index),
-                                       L.ptr(sampling_loc.float().contiguous()), L.ptr(attn_weight.float().contiguous()),
-                                       L.ptr(out), N, S, M, D, nl, Lq, P, L.stream_ptr())
+        sampling_loc, attn_weight = sampling_loc.float().contiguous(), attn_weight.float().contiguous()
+        symbol = "mvg_msda_forward_bf16"
     else:
         raise RuntimeError("deform_forward: float32 / float64 / bfloat16 only (got %s)" % value.dtype)
-    L.check(rc, "mvg_msda_forward")
+    _launch(symbol, value, spatial_shapes, level_start_index, sampling_loc, attn_weight, out, N, S, M, D, nl, Lq, P)
     return out
 
 
@@ -169,23 +183,18 @@ def msda_backward(value, spatial_shapes, level_start_index, sampling_loc, attn_w
         # deterministic form (csrc/msda_bwd.hip): binned by destination tile, fixed-point accumulation in LDS
         lib = L.load()
         shapes_c, starts_c = host if host is not None else host_levels(spatial_shapes, level_start_index)
-        fn, fn_name, ws_bytes, tail = _det_entry(lib, False, (N, S, M, D, nl, Lq, P), shapes_c)
+        symbol, ws_bytes, tail = _det_entry(lib, False, (N, S, M, D, nl, Lq, P), shapes_c)
         if ws_bytes:
             ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=value.device)
             gv, gl, ga = torch.empty_like(value), torch.empty_like(sampling_loc), torch.empty_like(attn_weight)
-            with _timed("msda_backward_det"):
-              L.check(fn(L.ptr(value), shapes_c, starts_c, L.ptr(sampling_loc), L.ptr(attn_weight),
-                         L.ptr(grad_output), L.ptr(gv), L.ptr(gl), L.ptr(ga), N, S, M, D, nl, Lq, P,
-                         L.ptr(ws), ws_bytes, L.stream_ptr(), *tail), fn_name)
+            _launch(symbol, value, shapes_c, starts_c, sampling_loc, attn_weight, grad_output, gv, gl, ga, N, S, M, D, nl, Lq, P,
+                    ws, ws_bytes, *tail, label="msda_backward_det")
             return gv, gl, ga
     gv = torch.zeros_like(value)                                             # deform_cuda.cu:132-134
     gl = torch.empty_like(sampling_loc)
     ga = torch.empty_like(attn_weight)
-    fn = L.load().mvg_msda_backward_f32 if value.dtype == torch.float32 else L.load().mvg_msda_backward_f64
-    rc = fn(L.ptr(value), L.ptr(spatial_shapes), L.ptr(level_start_index),
-                                        L.ptr(sampling_loc), L.ptr(attn_weight), L.ptr(grad_output), L.ptr(gv), L.ptr(gl),
-                                        L.ptr(ga), N, S, M, D, nl, Lq, P, L.stream_ptr())
-    L.check(rc, "mvg_msda_backward")
+    _launch("mvg_msda_backward_f32" if value.dtype == torch.float32 else "mvg_msda_backward_f64", value, spatial_shapes,
+            level_start_index, sampling_loc, attn_weight, grad_output, gv, gl, ga, N, S, M, D, nl, Lq, P)
     return gv, gl, ga
 
 
@@ -205,23 +214,20 @@ def _msda_backward_bf16(value, spatial_shapes, level_start_index, sampling_loc, 
     lib = L.load()
     if BACKWARD_MODE != "atomic":
         shapes_c, starts_c = host if host is not None else host_levels(spatial_shapes, level_start_index)
-        fn, fn_name, ws_bytes, tail = _det_entry(lib, True, (N, S, M, D, nl, Lq, P), shapes_c)
+        symbol, ws_bytes, tail = _det_entry(lib, True, (N, S, M, D, nl, Lq, P), shapes_c)
         if ws_bytes:
             ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=value.device)
             gv = torch.empty(value.shape, dtype=torch.float32, device=value.device)
             gl, ga = torch.empty_like(sampling_loc), torch.empty_like(attn_weight)
-            with _timed("msda_backward_det_bf16"):
-              L.check(fn(L.ptr(value), shapes_c, starts_c, L.ptr(sampling_loc), L.ptr(attn_weight),
-                         L.ptr(grad_output), L.ptr(gv), L.ptr(gl), L.ptr(ga), N, S, M, D, nl, Lq, P,
-                         L.ptr(ws), ws_bytes, L.stream_ptr(), *tail), fn_name)
+            _launch(symbol, value, shapes_c, starts_c, sampling_loc, attn_weight, grad_output, gv, gl, ga, N, S, M, D, nl, Lq, P,
+                    ws, ws_bytes, *tail, label="msda_backward_det_bf16")
             return gv, gl, ga
     v32 = value.float()
     gv = torch.zeros_like(v32)
     gl = torch.empty_like(sampling_loc)
     ga = torch.empty_like(attn_weight)
-    L.check(lib.mvg_msda_backward_f32(L.ptr(v32), L.ptr(spatial_shapes), L.ptr(level_start_index), L.ptr(sampling_loc),
-                                      L.ptr(attn_weight), L.ptr(grad_output), L.ptr(gv), L.ptr(gl), L.ptr(ga), N, S, M, D, nl, Lq, P,
-                                      L.stream_ptr()), "mvg_msda_backward")
+    _launch("mvg_msda_backward_f32", v32, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output, gv, gl, ga,
+            N, S, M, D, nl, Lq, P)
     return gv, gl, ga
 
 
@@ -246,7 +252,7 @@ def pack_pyramid(src_views, levels, dtype, out=None):
       * it IS the level view of `out` (pyramid_level_views) in `dtype`: produced in place, nothing to do;
       * torch.channels_last memory format (fp32 / bf16 / fp16): one cast+copy, no transposition;
       * NCHW (what the reference's backbone emits, pose_resnet.py:198-216): LDS-tiled transpose kernel."""
-    lib = L.load()
+    L.load()
     n_img, Cc = src_views[0].shape[:2]
     feat = out if out is not None else torch.empty((n_img, levels.S, Cc), dtype=dtype, device=src_views[0].device)
     if tuple(feat.shape) != (n_img, levels.S, Cc) or feat.dtype != dtype or not feat.is_contiguous():
@@ -259,9 +265,8 @@ def pack_pyramid(src_views, levels, dtype, out=None):
                                 for l, s in enumerate(src_views))):
         # the reference's hand-over format on every level: one launch for the whole pyramid
         ptrs = (C.c_void_p * levels.L)(*[s.data_ptr() for s in src_views])
-        with _timed("pack_level"):
-            L.check(lib.mvg_pack_pyramid(ptrs, L.ptr(feat), L.dtype_code(dtype), n_img, Cc, levels.shapes_c, levels.starts_c,
-                                         levels.L, levels.S, L.stream_ptr()), "mvg_pack_pyramid")
+        _launch("mvg_pack_pyramid", ptrs, feat, L.dtype_code(dtype), n_img, Cc, levels.shapes_c, levels.starts_c, levels.L,
+                levels.S, label="pack_level")
         return feat
     for l, src in enumerate(src_views):
         L.require_cuda(src)
@@ -277,9 +282,8 @@ def pack_pyramid(src_views, levels, dtype, out=None):
             continue
         s = src.float().contiguous()
         one = (C.c_void_p * 1)(s.data_ptr())
-        with _timed("pack_level"):      # the same kernel on this level alone
-          L.check(lib.mvg_pack_pyramid(one, L.ptr(feat), L.dtype_code(dtype), n_img, Cc, (C.c_int64 * 2)(H, W),
-                                       (C.c_int64 * 1)(int(levels.starts[l])), 1, levels.S, L.stream_ptr()), "mvg_pack_pyramid")
+        _launch("mvg_pack_pyramid", one, feat, L.dtype_code(dtype), n_img, Cc, (C.c_int64 * 2)(H, W),       # the same kernel on
+                (C.c_int64 * 1)(int(levels.starts[l])), 1, levels.S, label="pack_level")                    # this level alone
     return feat
 
 
@@ -288,8 +292,7 @@ def project(X, cams, levels, V, B):
     r = torch.empty((V * B, Lq, 2), dtype=torch.float32, device=X.device)
     ref_lvl = torch.empty((V * B, Lq, levels.L, 2), dtype=torch.float32, device=X.device)
     inside = torch.empty((V * B, Lq), dtype=torch.uint8, device=X.device)
-    L.check(L.load().mvg_project(L.ptr(X), L.ptr(cams), levels.shapes_c, levels.L, L.ptr(r), L.ptr(ref_lvl),
-                                 L.ptr(inside), V, B, Lq, L.stream_ptr()), "mvg_project")
+    _launch("mvg_project", X, cams, levels.shapes_c, levels.L, r, ref_lvl, inside, V, B, Lq)
     return r, ref_lvl, inside
 
 
@@ -298,10 +301,8 @@ def gather_ref(feat, r, x, levels, V, B):
     n_img, S, Cc = feat.shape
     Lq = r.shape[1]
     ain = torch.empty((n_img * Lq * levels.L, Cc), dtype=feat.dtype, device=feat.device)
-    with _timed("gather_ref"):
-      L.check(L.load().mvg_gather_ref(L.ptr(feat), L.dtype_code(feat.dtype), L.ptr(r), L.ptr(x), levels.shapes_c,
-                                    levels.starts_c, L.ptr(ain), V, B, Lq, levels.L, S, Cc, L.stream_ptr()),
-            "mvg_gather_ref")
+    _launch("mvg_gather_ref", feat, L.dtype_code(feat.dtype), r, x, levels.shapes_c, levels.starts_c, ain, V, B, Lq, levels.L, S, Cc,
+            label="gather_ref")
     return ain
 
 
@@ -318,10 +319,8 @@ def linear(a, w, bias, out_dtype=None, relu=False, rowmask=None, out=None, add=N
     if add is not None and (add.dtype != torch.float32 or a.dtype != torch.float32 or add.shape != a.shape
                             or add.stride() != a.stride()):
         raise RuntimeError("mvg_linear_sum: the addend must be an fp32 tensor with a's shape and strides")
-    with _timed("linear_%dx%dx%d" % (M, N, K)):
-      L.check(L.load().mvg_linear_sum(L.ptr(a), L.ptr(add), L.dtype_code(a.dtype), a.stride(0), L.ptr(w),
-                                    L.dtype_code(w.dtype), L.ptr(bias), L.ptr(out), L.dtype_code(out.dtype), out.stride(0),
-                                    L.ptr(rowmask), 1 if relu else 0, M, N, K, L.stream_ptr()), "mvg_linear_sum")
+    _launch("mvg_linear_sum", a, add, L.dtype_code(a.dtype), a.stride(0), w, L.dtype_code(w.dtype), bias, out,
+            L.dtype_code(out.dtype), out.stride(0), rowmask, 1 if relu else 0, M, N, K, label="linear_%dx%dx%d" % (M, N, K))
     return out
 
 
@@ -347,9 +346,8 @@ def linear_wgrad_bias(dy, x, want_bias=True, splits=None):
     dw = torch.empty((N, K), dtype=torch.float32, device=dy.device)
     pdb = torch.empty((splits, N), dtype=torch.float32, device=dy.device) if want_bias else None
     db = torch.empty((N,), dtype=torch.float32, device=dy.device) if want_bias else None
-    with _timed("linear_wgrad_bias_%dx%dx%d" % (N, K, rows)):
-      L.check(L.load().mvg_linear_wgrad_bias_f32(L.ptr(dy), dy.stride(0), L.ptr(x), x.stride(0), L.ptr(partial), L.ptr(pdb), L.ptr(dw),
-                                                 L.ptr(db), rows, N, K, splits, L.stream_ptr()), "mvg_linear_wgrad_bias_f32")
+    _launch("mvg_linear_wgrad_bias_f32", dy, dy.stride(0), x, x.stride(0), partial, pdb, dw, db, rows, N, K, splits,
+            label="linear_wgrad_bias_%dx%dx%d" % (N, K, rows))
     return dw, db
 
 
@@ -375,9 +373,8 @@ def _linear_wgrad_bias_bf16(dy, x, want_bias, splits):
     dw = torch.empty((N, K), dtype=torch.float32, device=dy.device)
     pdb = torch.empty((splits, N), dtype=torch.float32, device=dy.device) if want_bias else None
     db = torch.empty((N,), dtype=torch.float32, device=dy.device) if want_bias else None
-    with _timed("linear_wgrad_bias_bf16_%dx%dx%d" % (N, K, rows)):
-      L.check(L.load().mvg_linear_wgrad_bias_bf16(L.ptr(dy), dy.stride(0), L.ptr(x), x.stride(0), L.ptr(partial), L.ptr(pdb), L.ptr(dw),
-                                                  L.ptr(db), rows, N, K, splits, L.stream_ptr()), "mvg_linear_wgrad_bias_bf16")
+    _launch("mvg_linear_wgrad_bias_bf16", dy, dy.stride(0), x, x.stride(0), partial, pdb, dw, db, rows, N, K, splits,
+            label="linear_wgrad_bias_bf16_%dx%dx%d" % (N, K, rows))
     return dw, db
 
 
@@ -404,10 +401,8 @@ def linear_ordered(a, w, bias, order, inside, masked_row, relu=False, rowmask=No
         raise RuntimeError("mvg_linear_ordered: rowmask must be a contiguous uint8 tensor with one entry per row (%d)" % M)
     if bias is not None and (bias.dtype != torch.float32 or bias.numel() != N):
         raise RuntimeError("mvg_linear_ordered: bias must be fp32 with %d entries" % N)
-    with _timed("linear_ordered_%dx%dx%d" % (M, N, K)):
-      L.check(L.load().mvg_linear_ordered(L.ptr(a), a.stride(0), L.ptr(w), L.ptr(bias), L.ptr(out), out.stride(0),
-                                        L.ptr(rowmask), 1 if relu else 0, M, N, K, L.ptr(order), L.ptr(inside),
-                                        L.ptr(masked_row), L.stream_ptr()), "mvg_linear_ordered")
+    _launch("mvg_linear_ordered", a, a.stride(0), w, bias, out, out.stride(0), rowmask, 1 if relu else 0, M, N, K, order, inside,
+            masked_row, label="linear_ordered_%dx%dx%d" % (M, N, K))
     return out
 
 
@@ -416,10 +411,8 @@ def msda_fused(value, oa, r, levels):
     n_img, S, Cc = value.shape
     Lq = r.shape[1]
     samp = torch.empty((n_img * Lq, Cc), dtype=value.dtype, device=value.device)
-    with _timed("msda_fused"):
-      L.check(L.load().mvg_msda_fused(L.ptr(value), L.dtype_code(value.dtype), L.ptr(oa), L.ptr(r), levels.shapes_c,
-                                    levels.starts_c, L.ptr(samp), n_img, Lq, levels.L, S, L.stream_ptr()),
-            "mvg_msda_fused")
+    _launch("mvg_msda_fused", value, L.dtype_code(value.dtype), oa, r, levels.shapes_c, levels.starts_c, samp, n_img, Lq, levels.L, S,
+            label="msda_fused")
     return samp
 
 
@@ -435,11 +428,8 @@ def msda_gfused_f32(value, G, xw, r, levels, B, pair_mask=None, order=None):
         assert pair_mask.dtype == torch.uint8 and pair_mask.numel() == n_img * Lq and pair_mask.is_contiguous()
     if order is not None:
         assert order.dtype == torch.int32 and order.numel() == n_img * Lq and order.is_contiguous()
-    with _timed("msda_gfused_f32"):
-      L.check(L.load().mvg_msda_gfused_f32(L.ptr(value), L.ptr(G), L.ptr(xw), L.ptr(r), levels.shapes_c, levels.starts_c,
-                                           L.ptr(samp), None if pair_mask is None else L.ptr(pair_mask),
-                                           None if order is None else L.ptr(order), n_img, Lq, levels.L, S, B,
-                                           L.stream_ptr()), "mvg_msda_gfused_f32")
+    _launch("mvg_msda_gfused_f32", value, G, xw, r, levels.shapes_c, levels.starts_c, samp, pair_mask, order, n_img, Lq, levels.L, S,
+            B, label="msda_gfused_f32")
     return samp
 
 
@@ -478,9 +468,8 @@ def pyramid_group_ws(feat, jobs, slots=0, label=None):
     outs = vpp(*[o.data_ptr() for _, _, o, _ in jobs])
     Ns = (C.c_int * n)(*[256 if p else 192 for _, _, _, p in jobs])
     planes = (C.c_int * n)(*[1 if p else 0 for _, _, _, p in jobs])
-    with _timed(label or "pyramid_group_ws_%d" % n):
-      L.check(L.load().mvg_pyramid_group_ws(L.ptr(feat), n_img, S, n, Wf, bias, outs, Ns, planes, int(slots), L.stream_ptr()),
-              "mvg_pyramid_group_ws")
+    _launch("mvg_pyramid_group_ws", feat, n_img, S, n, Wf, bias, outs, Ns, planes, int(slots),
+            label=label or "pyramid_group_ws_%d" % n)
 
 
 def gsamp_column_order(device=None):
@@ -504,11 +493,8 @@ def msda_gsamp(vp, G, xw, r, levels, B, pair_mask=None, order=None, out=None):
         assert pair_mask.dtype == torch.uint8 and pair_mask.numel() == n_img * Lq and pair_mask.is_contiguous()
     if order is not None:
         assert order.dtype == torch.int32 and order.numel() == n_img * Lq and order.is_contiguous()
-    with _timed("msda_gsamp"):
-      L.check(L.load().mvg_msda_gsamp(L.ptr(vp), L.ptr(G), L.ptr(xw), L.ptr(r), levels.shapes_c, levels.starts_c,
-                                      L.ptr(samp), None if pair_mask is None else L.ptr(pair_mask),
-                                      None if order is None else L.ptr(order), n_img, Lq, levels.L, levels.S, B,
-                                      L.stream_ptr()), "mvg_msda_gsamp")
+    _launch("mvg_msda_gsamp", vp, G, xw, r, levels.shapes_c, levels.starts_c, samp, pair_mask, order, n_img, Lq, levels.L, levels.S,
+            B, label="msda_gsamp")
     return samp
 
 
@@ -524,10 +510,7 @@ def bin_pairs(r, inside, levels, out=None):
     lib = L.load()
     ws_bytes = int(lib.mvg_bin_pairs_workspace(n_img, Lq))
     ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=r.device) if ws_bytes else None     # multi-workgroup variant
-    with _timed("bin_pairs"):
-      L.check(lib.mvg_bin_pairs(L.ptr(r), None if inside is None else L.ptr(inside), levels.shapes_c, levels.L,
-                                L.ptr(order), n_img, Lq, None if ws is None else L.ptr(ws), ws_bytes, L.stream_ptr()),
-              "mvg_bin_pairs")
+    _launch("mvg_bin_pairs", r, inside, levels.shapes_c, levels.L, order, n_img, Lq, ws, ws_bytes, label="bin_pairs")
     return order
 
 
@@ -589,9 +572,8 @@ def pyramid_f32h(feat, Wv_planes, wv_scale, bv, Wg_planes, wg_scale, n_g, value=
         G = torch.empty((rows, n_g), dtype=torch.float32, device=feat.device)
     assert value.dtype == torch.float32 and value.numel() == rows * 256 and value.is_contiguous()
     assert G.dtype == torch.float32 and tuple(G.shape) == (rows, n_g) and G.is_contiguous()
-    with _timed("pyramid_f32h"):
-      L.check(L.load().mvg_pyramid_f32h(L.ptr(feat), L.ptr(Wv_planes), int(wv_scale), L.ptr(bv), L.ptr(Wg_planes), int(wg_scale),
-                                        L.ptr(value), L.ptr(G), rows, n_g, L.stream_ptr()), "mvg_pyramid_f32h")
+    _launch("mvg_pyramid_f32h", feat, Wv_planes, int(wv_scale), bv, Wg_planes, int(wg_scale), value, G, rows, n_g,
+            label="pyramid_f32h")
     return value, G
 
 
@@ -612,12 +594,8 @@ def chain_attn_pose_f32h(samp, inside, Wp, swp, bp, W0, sw0, b0, W1, sw1, b1, W2
         assert order.dtype == torch.int32 and order.numel() == rows and order.is_contiguous()
     attn = torch.empty((rows, 256), dtype=torch.float32, device=samp.device)
     o = torch.empty((rows, 3), dtype=torch.float32, device=samp.device)
-    with _timed("chain_attn_pose_f32h"):
-      L.check(L.load().mvg_chain_attn_pose_f32h(L.ptr(samp), L.ptr(inside), L.ptr(Wp), int(swp), L.ptr(bp), L.ptr(W0), int(sw0), L.ptr(b0),
-                                                L.ptr(W1), int(sw1), L.ptr(b1), L.ptr(W2), L.ptr(b2), L.ptr(attn), L.ptr(o),
-                                                None if order is None else L.ptr(order),
-                                                None if o_masked is None else L.ptr(o_masked), rows, L.stream_ptr()),
-              "mvg_chain_attn_pose_f32h")
+    _launch("mvg_chain_attn_pose_f32h", samp, inside, Wp, int(swp), bp, W0, int(sw0), b0, W1, int(sw1), b1, W2, b2, attn, o, order,
+            o_masked, rows, label="chain_attn_pose_f32h")
     return attn, o
 
 
@@ -664,12 +642,9 @@ def chain_update_ffn_class_f32h(attn, V, tgt, Wu, su, bu, g2, be2, W1, s1, b1, W
         xw_next = torch.empty((rows, n_next), dtype=torch.float32, device=dev)
     if any_valid is None:
         any_valid = torch.zeros((1,), dtype=torch.int32, device=dev)
-    with _timed("chain_update_ffn_class_f32h"):
-      L.check(L.load().mvg_chain_update_ffn_class_f32h(
-          L.ptr(attn), V, L.ptr(tgt), L.ptr(Wu), int(su), L.ptr(bu), L.ptr(g2), L.ptr(be2), L.ptr(W1), int(s1 or 0), L.ptr(b1), L.ptr(W2),
-          int(s2 or 0), L.ptr(b2), L.ptr(g3), L.ptr(be3), L.ptr(Wc), L.ptr(bc), float(threshold), L.ptr(forced_valid), L.ptr(tgt_out),
-          L.ptr(prob), L.ptr(valid), L.ptr(any_valid), L.ptr(qpos), L.ptr(Wn), int(sn), L.ptr(bn), L.ptr(xw_next), n_next, B, NQ, J,
-          1 if has_ffn else 0, L.stream_ptr()), "mvg_chain_update_ffn_class_f32h")
+    _launch("mvg_chain_update_ffn_class_f32h", attn, V, tgt, Wu, int(su), bu, g2, be2, W1, int(s1 or 0), b1, W2, int(s2 or 0), b2, g3,
+            be3, Wc, bc, float(threshold), forced_valid, tgt_out, prob, valid, any_valid, qpos, Wn, int(sn), bn, xw_next, n_next,
+            B, NQ, J, 1 if has_ffn else 0, label="chain_update_ffn_class_f32h")
     if next_query_proj is not None:
         return tgt_out, prob, valid, any_valid, xw_next
     return tgt_out, prob, valid, any_valid
@@ -685,12 +660,8 @@ def chain_attn_pose(samp, inside, Wp, bp, W0, b0, W1, b1, W2, b2, order=None, o_
     o = torch.empty((rows, 3), dtype=torch.float32, device=samp.device)
     if order is not None:
         assert order.dtype == torch.int32 and order.numel() == rows and order.is_contiguous()
-    with _timed("chain_attn_pose"):
-      L.check(L.load().mvg_chain_attn_pose(L.ptr(samp), L.ptr(inside), L.ptr(Wp), L.ptr(bp), L.ptr(W0), L.ptr(b0), L.ptr(W1),
-                                           L.ptr(b1), L.ptr(W2), L.ptr(b2), L.ptr(attn), L.ptr(o),
-                                           None if order is None else L.ptr(order),
-                                           None if o_masked is None else L.ptr(o_masked), rows, L.stream_ptr()),
-              "mvg_chain_attn_pose")
+    _launch("mvg_chain_attn_pose", samp, inside, Wp, bp, W0, b0, W1, b1, W2, b2, attn, o, order, o_masked, rows,
+            label="chain_attn_pose")
     return attn, o
 
 
@@ -736,12 +707,9 @@ def chain_update_ffn_class(attn, V, tgt, Wu, bu, g2, be2, W1, b1, W2, b2, g3, be
         any_valid = torch.zeros((1,), dtype=torch.int32, device=dev)
     if attn_inside is not None:
         assert attn_inside.dtype == torch.uint8 and attn_inside.numel() == V * rows and attn_inside.is_contiguous()
-    with _timed("chain_update_ffn_class"):
-      L.check(L.load().mvg_chain_update_ffn_class(
-          L.ptr(attn), V, L.ptr(tgt), L.ptr(Wu), L.ptr(bu), L.ptr(g2), L.ptr(be2), L.ptr(W1), L.ptr(b1), L.ptr(W2), L.ptr(b2),
-          L.ptr(g3), L.ptr(be3), L.ptr(Wc), L.ptr(bc), float(threshold), L.ptr(forced_valid), L.ptr(tgt_out), L.ptr(prob),
-          L.ptr(valid), L.ptr(any_valid), L.ptr(qpos), L.ptr(Wn), L.ptr(bn), L.ptr(xw_next), n_next, B, NQ, J,
-          1 if has_ffn else 0, L.ptr(attn_inside), L.stream_ptr()), "mvg_chain_update_ffn_class")
+    _launch("mvg_chain_update_ffn_class", attn, V, tgt, Wu, bu, g2, be2, W1, b1, W2, b2, g3, be3, Wc, bc, float(threshold),
+            forced_valid, tgt_out, prob, valid, any_valid, qpos, Wn, bn, xw_next, n_next, B, NQ, J, 1 if has_ffn else 0, attn_inside,
+            label="chain_update_ffn_class")
     if next_query_proj is not None:
         return tgt_out, prob, valid, any_valid, xw_next
     return tgt_out, prob, valid, any_valid
@@ -750,16 +718,14 @@ def chain_update_ffn_class(attn, V, tgt, Wu, bu, g2, be2, W1, b1, W2, b2, g3, be
 def mean_views(attn, V):
     rows = attn.shape[0] // V
     out = torch.empty((rows, attn.shape[1]), dtype=attn.dtype, device=attn.device)
-    L.check(L.load().mvg_mean_views(L.ptr(attn), L.dtype_code(attn.dtype), L.ptr(out), V, rows, attn.shape[1],
-                                    L.stream_ptr()), "mvg_mean_views")
+    _launch("mvg_mean_views", attn, L.dtype_code(attn.dtype), out, V, rows, attn.shape[1])
     return out
 
 
 def add_layernorm(res, h, gamma, beta):
     rows, Cc = res.shape
     y = torch.empty((rows, Cc), dtype=torch.float32, device=res.device)
-    L.check(L.load().mvg_add_layernorm(L.ptr(res), L.ptr(h), L.dtype_code(h.dtype), L.ptr(gamma), L.ptr(beta), L.ptr(y),
-                                       rows, Cc, L.stream_ptr()), "mvg_add_layernorm")
+    _launch("mvg_add_layernorm", res, h, L.dtype_code(h.dtype), gamma, beta, y, rows, Cc)
     return y
 
 
@@ -770,9 +736,8 @@ def self_attention(q, k, v):
     in-projection's output is attended where it lies.  Returns (B, Lq, 256) in the inputs' dtype.  Finite inputs only."""
     B, Lq, Cc = _attention_operands("self_attention", q=q, k=k, v=v)
     out = torch.empty((B, Lq, Cc), dtype=q.dtype, device=q.device)
-    with _timed("self_attention"):
-      L.check(L.load().mvg_self_attention(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(out), q.stride(1), k.stride(1), v.stride(1), B, Lq, Cc,
-                                          8, L.dtype_code(q.dtype), L.stream_ptr()), "mvg_self_attention")
+    _launch("mvg_self_attention", q, k, v, out, q.stride(1), k.stride(1), v.stride(1), B, Lq, Cc, 8, L.dtype_code(q.dtype),
+            label="self_attention")
     return out
 
 
@@ -823,10 +788,8 @@ def self_attention_train(q, k, v, p_drop=0.0, seed=None):
     p_drop, seed = _attention_seed("self_attention_train", p_drop, seed, q.device)
     out = torch.empty((B, Lq, Cc), dtype=q.dtype, device=q.device)
     lse = torch.empty((B, 8, Lq), dtype=torch.float32, device=q.device)
-    with _timed("self_attention_train"):
-      L.check(L.load().mvg_self_attention_train(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(out), L.ptr(lse), q.stride(1), k.stride(1),
-                                                v.stride(1), B, Lq, Cc, 8, L.dtype_code(q.dtype), p_drop, L.ptr(seed), L.stream_ptr()),
-              "mvg_self_attention_train")
+    _launch("mvg_self_attention_train", q, k, v, out, lse, q.stride(1), k.stride(1), v.stride(1), B, Lq, Cc, 8,
+            L.dtype_code(q.dtype), p_drop, seed, label="self_attention_train")
     return out, lse
 
 
@@ -840,14 +803,10 @@ def self_attention_backward(q, k, v, out, dout, lse, p_drop=0.0, seed=None):
     if lse.shape != (B, 8, Lq) or lse.dtype != torch.float32 or not lse.is_contiguous() or lse.device != q.device:
         raise RuntimeError("self_attention_backward: lse (B, 8, Lq) float32 contiguous expected, got %s %s" % (tuple(lse.shape), lse.dtype))
     dq, dk, dv = (torch.empty((B, Lq, Cc), dtype=q.dtype, device=q.device) for _ in range(3))
-    lib = L.load()
-    nbytes = int(lib.mvg_self_attention_backward_workspace(B, Lq))
+    nbytes = int(L.load().mvg_self_attention_backward_workspace(B, Lq))
     ws = torch.empty((nbytes // 4,), dtype=torch.float32, device=q.device)
-    with _timed("self_attention_backward"):
-      L.check(lib.mvg_self_attention_backward(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(out), L.ptr(dout), L.ptr(lse), L.ptr(dq), L.ptr(dk),
-                                              L.ptr(dv), q.stride(1), k.stride(1), v.stride(1), Cc, Cc, Cc, B, Lq, Cc, 8,
-                                              L.dtype_code(q.dtype), p_drop, L.ptr(seed), L.ptr(ws), nbytes, L.stream_ptr()),
-              "mvg_self_attention_backward")
+    _launch("mvg_self_attention_backward", q, k, v, out, dout, lse, dq, dk, dv, q.stride(1), k.stride(1), v.stride(1), Cc, Cc, Cc,
+            B, Lq, Cc, 8, L.dtype_code(q.dtype), p_drop, seed, ws, nbytes, label="self_attention_backward")
     return dq, dk, dv
 
 
@@ -859,8 +818,7 @@ def self_attention_dropout_mask(B, Lq, p_drop, seed):
     if B < 1 or not 1 <= Lq <= 1024:
         raise RuntimeError("self_attention_dropout_mask: B >= 1, 1 <= Lq <= 1024 expected, got B %d Lq %d" % (B, Lq))
     mask = torch.empty((B, 8, Lq, Lq), dtype=torch.uint8, device="cuda" if seed is None else seed.device)
-    L.check(L.load().mvg_self_attention_dropout_mask(L.ptr(mask), B, Lq, p_drop, L.ptr(seed), L.stream_ptr()),
-            "mvg_self_attention_dropout_mask")
+    _launch("mvg_self_attention_dropout_mask", mask, B, Lq, p_drop, seed)
     return mask
 
 
@@ -869,16 +827,14 @@ def class_head(tgt, Wc, bc, threshold, B, NQ, J, forced_valid=None):
     prob = torch.empty((B, NQ, 2), dtype=torch.float32, device=tgt.device)
     valid = torch.empty((B, NQ), dtype=torch.uint8, device=tgt.device)
     any_valid = torch.zeros((1,), dtype=torch.int32, device=tgt.device)
-    L.check(L.load().mvg_class_head(L.ptr(tgt), L.ptr(Wc), L.ptr(bc), float(threshold), L.ptr(forced_valid), L.ptr(prob),
-                                    L.ptr(valid), L.ptr(any_valid), B, NQ, J, Cc, L.stream_ptr()), "mvg_class_head")
+    _launch("mvg_class_head", tgt, Wc, bc, float(threshold), forced_valid, prob, valid, any_valid, B, NQ, J, Cc)
     return prob, valid, any_valid
 
 
 def rowdot3(h, W3, b3):
     rows, Cc = h.shape
     o = torch.empty((rows, 3), dtype=torch.float32, device=h.device)
-    L.check(L.load().mvg_rowdot3(L.ptr(h), L.dtype_code(h.dtype), L.ptr(W3), L.ptr(b3), L.ptr(o), rows, Cc,
-                                 L.stream_ptr()), "mvg_rowdot3")
+    _launch("mvg_rowdot3", h, L.dtype_code(h.dtype), W3, b3, o, rows, Cc)
     return o
 
 
@@ -901,15 +857,10 @@ def triangulate(r, o, cams, valid, any_valid, V, B, NQ, J, out=None, next_levels
         r_n = torch.empty((V * B, Lq, 2), dtype=torch.float32, device=dev)
         ref_n = torch.empty((V * B, Lq, lv.L, 2), dtype=torch.float32, device=dev)
         in_n = torch.empty((V * B, Lq), dtype=torch.uint8, device=dev)
-        with _timed("triangulate_project"):
-          L.check(L.load().mvg_triangulate_project(L.ptr(r), L.ptr(o), L.ptr(cams), L.ptr(valid), L.ptr(any_valid),
-                                                   L.ptr(new_ref), L.ptr(ref2d), L.ptr(proj2d), V, B, NQ, J, lv.shapes_c, lv.L,
-                                                   L.ptr(r_n), L.ptr(ref_n), L.ptr(in_n), L.stream_ptr()),
-                  "mvg_triangulate_project")
+        _launch("mvg_triangulate_project", r, o, cams, valid, any_valid, new_ref, ref2d, proj2d, V, B, NQ, J, lv.shapes_c, lv.L,
+                r_n, ref_n, in_n, label="triangulate_project")
         return new_ref, ref2d, proj2d, (r_n, ref_n, in_n)
-    with _timed("triangulate"):
-      L.check(L.load().mvg_triangulate(L.ptr(r), L.ptr(o), L.ptr(cams), L.ptr(valid), L.ptr(any_valid), L.ptr(new_ref),
-                                     L.ptr(ref2d), L.ptr(proj2d), V, B, NQ, J, L.stream_ptr()), "mvg_triangulate")
+    _launch("mvg_triangulate", r, o, cams, valid, any_valid, new_ref, ref2d, proj2d, V, B, NQ, J, label="triangulate")
     return new_ref, ref2d, proj2d
 
 
@@ -960,8 +911,7 @@ def uncrop_undistort_jac(ref2d, cams, V, B):
     Lq = ref2d.shape[2]
     ud = torch.empty_like(ref2d)
     jac = torch.empty((B, V, Lq, 2, 2), dtype=torch.float32, device=ref2d.device)
-    L.check(L.load().mvg_uncrop_undistort_jac(L.ptr(ref2d), L.ptr(cams), L.ptr(ud), L.ptr(jac), V, B, Lq, L.stream_ptr()),
-            "mvg_uncrop_undistort_jac")
+    _launch("mvg_uncrop_undistort_jac", ref2d, cams, ud, jac, V, B, Lq)
     return ud, jac
 
 
@@ -978,8 +928,7 @@ def dlt_forward(ud, conf, Pm, valid, J):
     B, V, Lq = _dlt_args(ud, conf, Pm, valid, J)
     ud, conf, Pm, valid = ud.contiguous(), conf.contiguous(), Pm.contiguous(), valid.contiguous()
     X = torch.empty((B, Lq, 3), dtype=torch.float32, device=ud.device)
-    L.check(L.load().mvg_dlt_forward(L.ptr(ud), L.ptr(conf), L.ptr(Pm), L.ptr(valid), L.ptr(X), V, B, Lq // J, J, L.stream_ptr()),
-            "mvg_dlt_forward")
+    _launch("mvg_dlt_forward", ud, conf, Pm, valid, X, V, B, Lq // J, J)
     return X
 
 
@@ -991,8 +940,7 @@ def dlt_backward(ud, conf, Pm, valid, J, gX):
     ud, conf, Pm, valid, gX = ud.contiguous(), conf.contiguous(), Pm.contiguous(), valid.contiguous(), gX.contiguous()
     g_ud = torch.empty_like(ud)
     g_conf = torch.empty_like(conf)
-    L.check(L.load().mvg_dlt_backward(L.ptr(ud), L.ptr(conf), L.ptr(Pm), L.ptr(valid), L.ptr(gX), L.ptr(g_ud), L.ptr(g_conf), V, B,
-                                      Lq // J, J, L.stream_ptr()), "mvg_dlt_backward")
+    _launch("mvg_dlt_backward", ud, conf, Pm, valid, gX, g_ud, g_conf, V, B, Lq // J, J)
     return g_ud, g_conf
 
 
@@ -1005,12 +953,12 @@ def sym4_eigh(G):
     n = Gc.numel() // 16
     w = torch.empty(Gc.shape[:-1], dtype=torch.float64, device=G.device)
     V = torch.empty_like(Gc)
-    L.check(L.load().mvg_sym4_eigh(L.ptr(Gc), L.ptr(w), L.ptr(V), n, L.stream_ptr()), "mvg_sym4_eigh")
+    _launch("mvg_sym4_eigh", Gc, w, V, n)
     return w, V
 
 
 # ---- training criterion (csrc/criterion.hip) ---------------------------------------------------------------------------------
-MATCH_METHODS = {"KNN": 0, "multiple": 1}
+MATCH_METHODS = {"KNN": _D["MVG_MATCH_KNN"], "multiple": _D["MVG_MATCH_MULTIPLE"]}
 CRITERION_COLUMNS = ("loss_ce", "class_error", "class_recall", "class_precision", "cardinality_error", "loss_pose_perjoint",
                      "loss_pose_perprojection_2d", "keep_2d")
 
@@ -1079,21 +1027,17 @@ def knn_match(poses, joints_3d, num_person, space_size, space_center, method="KN
     matched = torch.empty((B, NQ), dtype=torch.uint8, device=dev)
     nbytes = lib.mvg_knn_match_workspace(B, NQ, Gmax)
     ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev) if nbytes else None
-    with _timed("knn_match"):
-        if jm is None:
-            L.check(lib.mvg_knn_match(L.ptr(poses), L.ptr(joints_3d), L.ptr(num_person), is64, _host3(space_size),
-                                      _host3(space_center), MATCH_METHODS[method], K, float(value), B, NQ, Gmax, J, Pmax, L.ptr(ws),
-                                      nbytes, L.ptr(pq), L.ptr(pg), L.ptr(pc), L.ptr(matched), L.stream_ptr()), "mvg_knn_match")
-        else:
-            L.check(lib.mvg_knn_match_jm(L.ptr(poses), L.ptr(joints_3d), L.ptr(num_person), is64, _host3(space_size),
-                                         _host3(space_center), MATCH_METHODS[method], K, float(value), B, NQ, Gmax, Jp, J, jm, Pmax,
-                                         L.ptr(ws), nbytes, L.ptr(pq), L.ptr(pg), L.ptr(pc), L.ptr(matched), L.stream_ptr()),
-                    "mvg_knn_match_jm")
+    head = (poses, joints_3d, num_person, is64, _host3(space_size), _host3(space_center), MATCH_METHODS[method], K, float(value))
+    tail = (Pmax, ws, nbytes, pq, pg, pc, matched)
+    if jm is None:
+        _launch("mvg_knn_match", *head, B, NQ, Gmax, J, *tail, label="knn_match")
+    else:
+        _launch("mvg_knn_match_jm", *head, B, NQ, Gmax, Jp, J, jm, *tail, label="knn_match")
     return pq, pg, pc, matched
 
 
-HUNGARIAN_METHODS = {"hungarian": 2, "hungarian-dis": 3}       # MVG_MATCH_HUNGARIAN, MVG_MATCH_HUNGARIAN_DIS
-HUNGARIAN_MAX_G, HUNGARIAN_MAX_NQ = 64, 4096
+HUNGARIAN_METHODS = {"hungarian": _D["MVG_MATCH_HUNGARIAN"], "hungarian-dis": _D["MVG_MATCH_HUNGARIAN_DIS"]}
+HUNGARIAN_MAX_G, HUNGARIAN_MAX_NQ = _D["MVG_HUNGARIAN_MAX_G"], _D["MVG_HUNGARIAN_MAX_NQ"]
 
 
 def hungarian_match(poses, joints_3d, num_person, space_size, space_center, logits=None, method="hungarian", cost_class=1.0,
@@ -1140,11 +1084,9 @@ def hungarian_match(poses, joints_3d, num_person, space_size, space_center, logi
     uv = torch.empty(head + (Gmax + NQ,), dtype=torch.float64, device=dev) if duals else None
     nbytes = lib.mvg_hungarian_match_workspace(P, NQ, Gmax)
     ws = torch.empty(((nbytes + 3) // 4,), dtype=torch.float32, device=dev) if nbytes else None
-    with _timed("hungarian_match"):
-        L.check(lib.mvg_hungarian_match(L.ptr(logits), L.ptr(poses), L.ptr(joints_3d), L.ptr(num_person), is64, _host3(space_size),
-                                        _host3(space_center), HUNGARIAN_METHODS[method], float(cost_class), float(cost_pose), P, B,
-                                        NQ, Gmax, Jp, J, jm, L.ptr(ws), nbytes, L.ptr(pq), L.ptr(pg), L.ptr(pc), L.ptr(matched),
-                                        L.ptr(uv), L.stream_ptr()), "mvg_hungarian_match")
+    _launch("mvg_hungarian_match", logits, poses, joints_3d, num_person, is64, _host3(space_size), _host3(space_center),
+            HUNGARIAN_METHODS[method], float(cost_class), float(cost_pose), P, B, NQ, Gmax, Jp, J, jm, ws, nbytes, pq, pg, pc, matched,
+            uv, label="hungarian_match")
     if duals:
         return pq, pg, pc, matched, uv[..., :Gmax], uv[..., Gmax:]
     return pq, pg, pc, matched
@@ -1193,28 +1135,21 @@ def criterion(logits, poses, poses_2d, pair_query, pair_gt, pair_count, joints_3
     ws = torch.empty(((nbytes + 7) // 8,), dtype=torch.float64, device=dev)
     table = torch.empty((Ln, len(CRITERION_COLUMNS)), dtype=torch.float32, device=dev)
     gl, gp, gp2 = torch.empty_like(logits), torch.empty_like(poses), torch.empty_like(poses_2d)
-    with _timed("criterion"):
-        if jm is None:
-            L.check(lib.mvg_criterion(L.ptr(logits), L.ptr(poses), L.ptr(poses_2d), L.ptr(pair_query), L.ptr(pair_gt),
-                                      L.ptr(pair_count), L.ptr(joints_3d), L.ptr(joints_3d_vis), L.ptr(joints_vis), L.ptr(num_person),
-                                      is64, L.ptr(num_samples), L.ptr(cams), _host3(space_size), _host3(space_center),
-                                      float(pred_conf_threshold), float(focal_alpha), float(focal_gamma), Ln, B, NQ, J, V, Gmax, Pmax,
-                                      L.ptr(ws), nbytes, L.ptr(table), L.ptr(gl), L.ptr(gp), L.ptr(gp2), L.stream_ptr()),
-                    "mvg_criterion")
-        else:
-            L.check(lib.mvg_criterion_jm(L.ptr(logits), L.ptr(poses), L.ptr(poses_2d), L.ptr(pair_query), L.ptr(pair_gt),
-                                         L.ptr(pair_count), L.ptr(joints_3d), L.ptr(joints_3d_vis), L.ptr(joints_vis),
-                                         L.ptr(num_person), is64, L.ptr(num_samples), L.ptr(cams), _host3(space_size),
-                                         _host3(space_center), float(pred_conf_threshold), float(focal_alpha), float(focal_gamma),
-                                         Ln, B, NQ, Jp, J, jm, V, Gmax, Pmax, L.ptr(ws), nbytes, L.ptr(table), L.ptr(gl), L.ptr(gp),
-                                         L.ptr(gp2), L.stream_ptr()), "mvg_criterion_jm")
+    head = (logits, poses, poses_2d, pair_query, pair_gt, pair_count, joints_3d, joints_3d_vis, joints_vis, num_person, is64,
+            num_samples, cams, _host3(space_size), _host3(space_center), float(pred_conf_threshold), float(focal_alpha),
+            float(focal_gamma))
+    tail = (V, Gmax, Pmax, ws, nbytes, table, gl, gp, gp2)
+    if jm is None:
+        _launch("mvg_criterion", *head, Ln, B, NQ, J, *tail, label="criterion")
+    else:
+        _launch("mvg_criterion_jm", *head, Ln, B, NQ, Jp, J, jm, *tail, label="criterion")
     return table, gl, gp, gp2
 
 
 # ---- optimizer step (csrc/optim.hip) -----------------------------------------------------------------------------------------
-OPTIM_CHUNK = 4096                 # MVG_OPTIM_CHUNK
-OPTIM_TENSOR_WORDS, OPTIM_GROUP_WORDS = 6, 6
-OPTIM_STATE_HEADER, OPTIM_STATE_PER_GROUP = 64, 16
+OPTIM_CHUNK = _D["MVG_OPTIM_CHUNK"]
+OPTIM_TENSOR_WORDS, OPTIM_GROUP_WORDS = _D["MVG_OPTIM_TENSOR_WORDS"], _D["MVG_OPTIM_GROUP_WORDS"]
+OPTIM_STATE_HEADER, OPTIM_STATE_PER_GROUP = _D["MVG_OPTIM_STATE_HEADER"], _D["MVG_OPTIM_STATE_PER_GROUP"]
 
 
 def optim_state_words(n_groups):
@@ -1238,17 +1173,13 @@ def optim_step(tensor_table, chunk_table, group_table, state, workspace, loss=No
     for s in (loss, norm_out):
         if s is not None and (s.dtype != torch.float32 or s.numel() != 1):
             raise RuntimeError("mvg_optim_step: loss / norm_out must be float32 device scalars")
-    lib = L.load()
-    with _timed("optim_step"):
-        L.check(lib.mvg_optim_step(L.ptr(tensor_table), tensor_table.shape[0], L.ptr(chunk_table), chunk_table.shape[0],
-                                   L.ptr(group_table), group_table.shape[0], L.ptr(state), state.numel() * 8, L.ptr(workspace),
-                                   workspace.numel() * 8, L.ptr(loss), float(max_norm), int(bool(zero_grad)), L.ptr(norm_out),
-                                   L.stream_ptr()), "mvg_optim_step")
+    _launch("mvg_optim_step", tensor_table, tensor_table.shape[0], chunk_table, chunk_table.shape[0], group_table,
+            group_table.shape[0], state, state.numel() * 8, workspace, workspace.numel() * 8, loss, float(max_norm),
+            int(bool(zero_grad)), norm_out, label="optim_step")
 
 
 # ---- derived bf16 operands of the bf16 training path (csrc/operands.hip) ---------------------------------------------------------
-OPERANDS_TILE = 64                 # MVG_OPERANDS_TILE
-OPERANDS_RECORD_WORDS = 8          # MVG_OPERANDS_RECORD_WORDS
+OPERANDS_TILE, OPERANDS_RECORD_WORDS = _D["MVG_OPERANDS_TILE"], _D["MVG_OPERANDS_RECORD_WORDS"]
 
 
 def refresh_operands(record_table, tile_table):
@@ -1260,14 +1191,70 @@ def refresh_operands(record_table, tile_table):
             or tile_table.dtype != torch.int32 or tile_table.dim() != 2 or tile_table.shape[1] != 2
             or not record_table.is_contiguous() or not tile_table.is_contiguous()):
         raise RuntimeError("mvg_refresh_operands: tables (n, 8) int64 / (n, 2) int32, contiguous, expected")
-    lib = L.load()
-    with _timed("refresh_operands"):
-        L.check(lib.mvg_refresh_operands(L.ptr(record_table), record_table.shape[0], L.ptr(tile_table), tile_table.shape[0],
-                                         L.stream_ptr()), "mvg_refresh_operands")
+    _launch("mvg_refresh_operands", record_table, record_table.shape[0], tile_table, tile_table.shape[0], label="refresh_operands")
 
 
-NMS_MAX_N = 2048                   # MVG_NMS_MAX_N
-NMS_MAX_J = 32                     # MVG_NMS_MAX_J
+# ---- serving: caller-owned static buffers and the checks their wrappers share ---------------------------------------------------
+class _Layout:
+    """One family of caller-owned static buffers, written once: entries (key, dtype, shape, fill), the shape in named dimensions
+    and plain ints (("B", "T", "J", 3)), fill None for memory that is left uninitialised.  ``maker`` is the *_buffers function
+    that messages point to."""
+
+    def __init__(self, maker, *entries):
+        self.maker, self.entries, self.keys = maker, entries, tuple(e[0] for e in entries)
+
+    def alloc(self, dims, device):
+        out = {}
+        for key, dtype, shape, fill in self.entries:
+            shape = tuple(dims[d] if isinstance(d, str) else d for d in shape)
+            out[key] = (torch.empty(shape, dtype=dtype, device=device) if fill is None
+                        else torch.full(shape, fill, dtype=dtype, device=device))
+        return out
+
+    def check(self, buffers, dims, keys=None, who=None):
+        """raises unless the tensors ``keys`` (default: all) of ``buffers`` have the family's dtype, its shape for ``dims`` and are
+        contiguous"""
+        for key, dtype, shape, _ in self.entries:
+            if keys is not None and key not in keys:
+                continue
+            shape = tuple(dims[d] if isinstance(d, str) else d for d in shape)
+            t = buffers[key]
+            if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
+                raise RuntimeError("%s: buffer %r must be a contiguous %s tensor of shape %s, got %s %s with strides %s (see %s)"
+                                   % (who or self.maker, key, dtype, shape, t.dtype, tuple(t.shape), t.stride(), self.maker))
+
+
+def _check_limits(who, *terms):
+    """terms (name, value, largest value): raises unless 1 <= value <= largest for each"""
+    if not all(1 <= v <= hi for _, v, hi in terms):
+        raise L.MvgError("%s: unsupported shape %s" % (who, ", ".join("%s = %d (<= %d)" % t for t in terms)))
+
+
+def _check_dets(who, dets, count):
+    """dets (B, R, J, 5) fp32 and count (B, 2) int32 or None, as pose_nms leaves them -> (B, R, J)"""
+    if dets.dim() != 4 or dets.shape[-1] != 5 or dets.dtype != torch.float32:
+        raise RuntimeError("%s: dets (B, R, J, 5) float32 expected" % who)
+    B, R, J = dets.shape[:3]
+    if count is not None and (count.dtype != torch.int32 or tuple(count.shape) != (B, 2)):
+        raise RuntimeError("%s: count (B, 2) int32 or None expected" % who)
+    return B, R, J
+
+
+def _check_ground_truth(who, joints_3d, joints_3d_vis, num_person, B, J):
+    """joints_3d (B, G, J, 3) fp32, joints_3d_vis (B, G, J) fp32 and num_person (B) int32, as the evaluators take them -> G"""
+    if joints_3d.dim() != 4 or joints_3d.dtype != torch.float32 or joints_3d.shape[0] != B or tuple(joints_3d.shape[2:]) != (J, 3):
+        raise RuntimeError("%s: joints_3d (B, G, J, 3) float32 expected" % who)
+    G = joints_3d.shape[1]
+    if joints_3d_vis.dtype != torch.float32 or tuple(joints_3d_vis.shape) != (B, G, J):
+        raise RuntimeError("%s: joints_3d_vis (B, G, J) float32 expected" % who)
+    if num_person.dtype != torch.int32 or tuple(num_person.shape) != (B,):
+        raise RuntimeError("%s: num_person (B) int32 expected" % who)
+    return G
+
+
+NMS_MAX_N, NMS_MAX_J = _D["MVG_NMS_MAX_N"], _D["MVG_NMS_MAX_J"]
+_NMS = _Layout("pose_nms_buffers", ("keep", torch.int32, ("B", "N"), None), ("count", torch.int32, ("B", 2), None),
+               ("dets", torch.float32, ("B", "rows", "J", 5), None), ("workspace", torch.uint8, ("nbytes",), None))
 
 
 def pose_nms_buffers(B, N, J, dets_rows=None, device="cuda"):
@@ -1278,10 +1265,7 @@ def pose_nms_buffers(B, N, J, dets_rows=None, device="cuda"):
     if nbytes == 0 or rows < 1:
         raise L.MvgError("mvg_pose_nms: unsupported shape B = %d, N = %d (<= %d), J = %d (<= %d), dets_rows = %d"
                          % (B, N, NMS_MAX_N, J, NMS_MAX_J, rows))
-    return dict(keep=torch.empty((B, N), dtype=torch.int32, device=device),
-                count=torch.empty((B, 2), dtype=torch.int32, device=device),
-                dets=torch.empty((B, rows, J, 5), dtype=torch.float32, device=device),
-                workspace=torch.empty((nbytes,), dtype=torch.uint8, device=device))
+    return _NMS.alloc(dict(B=B, N=N, J=J, rows=rows, nbytes=nbytes), device)
 
 
 def pose_nms(pred, dist_thr=0.3, num_nearby_joints_thr=7, max_dets=-1, dets_rows=None, out=None):
@@ -1312,21 +1296,19 @@ def pose_nms(pred, dist_thr=0.3, num_nearby_joints_thr=7, max_dets=-1, dets_rows
         out = pose_nms_buffers(B, N, J, dets_rows, pred.device)
     keep, count, dets, ws = out["keep"], out["count"], out["dets"], out["workspace"]
     L.require_cuda(keep, count, dets, ws)
-    if (keep.dtype != torch.int32 or tuple(keep.shape) != (B, N) or count.dtype != torch.int32 or tuple(count.shape) != (B, 2)
-            or dets.dtype != torch.float32 or dets.dim() != 4 or dets.shape[0] != B or tuple(dets.shape[2:]) != (J, 5)
-            or (dets_rows is not None and dets.shape[1] != dets_rows)
-            or not (keep.is_contiguous() and count.is_contiguous() and dets.is_contiguous() and ws.is_contiguous())):
-        raise RuntimeError("mvg_pose_nms: out buffers do not fit pred %s (see pose_nms_buffers)" % (tuple(pred.shape),))
-    lib = L.load()
-    with _timed("pose_nms"):
-        L.check(lib.mvg_pose_nms(L.ptr(pred), B, N, J, float(dist_thr), int(num_nearby_joints_thr), int(max_dets), L.ptr(ws),
-                                 ws.numel() * ws.element_size(), L.ptr(keep), L.ptr(count), L.ptr(dets), dets.shape[1],
-                                 L.stream_ptr()), "mvg_pose_nms")
+    rows = dets_rows if dets_rows is not None else dets.shape[1] if dets.dim() == 4 else 0      # any number of rows, or dets_rows
+    _NMS.check(out, dict(B=B, N=N, J=J, rows=rows, nbytes=ws.numel()), who="mvg_pose_nms")
+    _launch("mvg_pose_nms", pred, B, N, J, float(dist_thr), int(num_nearby_joints_thr), int(max_dets), ws, ws.numel(), keep, count,
+            dets, dets.shape[1], label="pose_nms")
     return keep, count, dets
 
 
-EVAL_MAX_R, EVAL_MAX_J, EVAL_MAX_G, EVAL_MAX_B = 2048, 32, 64, 256      # MVG_EVAL_MAX_*
+EVAL_MAX_R, EVAL_MAX_J, EVAL_MAX_G, EVAL_MAX_B = (_D["MVG_EVAL_MAX_" + k] for k in "RJGB")
 EVAL_STATE = ("n_entries", "total_gt", "frames", "overflow", "kept_rows", "match_gt", "empty_frame", "reserved")
+_EVAL = _Layout("eval_buffers", ("mpjpe", torch.float64, ("capacity",), 0), ("score", torch.float64, ("capacity",), 0),
+                ("gt_id", torch.int64, ("capacity",), 0), ("correct", torch.int64, ("actors",), 0),
+                ("total", torch.int64, ("actors",), 0), ("bone_correct", torch.int64, ("actors", 10), 0),
+                ("state", torch.int64, (len(EVAL_STATE),), 0))
 
 
 def eval_buffers(capacity, actors=4, device="cuda"):
@@ -1336,29 +1318,17 @@ def eval_buffers(capacity, actors=4, device="cuda"):
     capacity, actors = int(capacity), int(actors)
     if capacity < 1 or not 1 <= actors <= EVAL_MAX_G:
         raise L.MvgError("eval_buffers: capacity >= 1 and 1 <= actors <= %d expected (got %d, %d)" % (EVAL_MAX_G, capacity, actors))
-    z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=device)
-    return dict(mpjpe=z((capacity,), torch.float64), score=z((capacity,), torch.float64), gt_id=z((capacity,), torch.int64),
-                correct=z((actors,), torch.int64), total=z((actors,), torch.int64), bone_correct=z((actors, 10), torch.int64),
-                state=z((len(EVAL_STATE),), torch.int64))
+    return _EVAL.alloc(dict(capacity=capacity, actors=actors), device)
 
 
-def _eval_inputs(name, dets, count, joints_3d, joints_3d_vis, num_person, buffers, keys):
-    out = [buffers[k] for k in keys]
-    L.require_cuda(dets, count, joints_3d, joints_3d_vis, num_person, *out)
-    if dets.dim() != 4 or dets.shape[-1] != 5 or dets.dtype != torch.float32:
-        raise RuntimeError("%s: dets (B, R, J, 5) float32 expected" % name)
-    B, R, J = dets.shape[:3]
-    if (joints_3d.dim() != 4 or joints_3d.dtype != torch.float32 or joints_3d.shape[0] != B or tuple(joints_3d.shape[2:]) != (J, 3)):
-        raise RuntimeError("%s: joints_3d (B, Gmax, J, 3) float32 expected for dets %s" % (name, tuple(dets.shape)))
-    G = joints_3d.shape[1]
-    if (joints_3d_vis.dtype != torch.float32 or tuple(joints_3d_vis.shape) != (B, G, J) or num_person.dtype != torch.int32
-            or tuple(num_person.shape) != (B,) or (count is not None and (count.dtype != torch.int32 or tuple(count.shape) != (B, 2)))):
-        raise RuntimeError("%s: joints_3d_vis (B, Gmax, J) float32, num_person (B) int32 and count (B, 2) int32 or None expected" % name)
-    if not all(t is None or t.is_contiguous() for t in (dets, count, joints_3d, joints_3d_vis, num_person, *out)):
+def _eval_inputs(name, dets, count, joints_3d, joints_3d_vis, num_person, buffers, keys, dims):
+    """the checks eval_match and eval_pcp share -> (B, R, J, G)"""
+    L.require_cuda(dets, count, joints_3d, joints_3d_vis, num_person, *(buffers[k] for k in keys))
+    B, R, J = _check_dets(name, dets, count)
+    G = _check_ground_truth(name, joints_3d, joints_3d_vis, num_person, B, J)
+    if not all(t is None or t.is_contiguous() for t in (dets, count, joints_3d, joints_3d_vis, num_person)):
         raise RuntimeError("%s: every tensor must be contiguous" % name)
-    if any(t.dtype != (torch.int64 if k in ("gt_id", "correct", "total", "bone_correct", "state") else torch.float64)
-           for k, t in zip(keys, out)) or buffers["state"].numel() != len(EVAL_STATE):
-        raise RuntimeError("%s: buffers are not those of eval_buffers" % name)
+    _EVAL.check(buffers, dims, keys, who=name)
     return B, R, J, G
 
 
@@ -1369,14 +1339,12 @@ def eval_match(dets, count, joints_3d, joints_3d_vis, num_person, buffers):
     num_person (B) int32.  Appends (mpjpe, score, gt_id) of every participating row to ``buffers`` (eval_buffers) in the
     reference's order and advances the state block; entries past the capacity are counted, not written."""
     keys = ("mpjpe", "score", "gt_id", "state")
-    B, R, J, G = _eval_inputs("mvg_eval_match", dets, count, joints_3d, joints_3d_vis, num_person, buffers, keys)
+    capacity = buffers["mpjpe"].numel()      # the entry list is as long as the caller made it
+    B, R, J, G = _eval_inputs("mvg_eval_match", dets, count, joints_3d, joints_3d_vis, num_person, buffers, keys,
+                              dict(capacity=capacity))
     mp, sc, gid, state = (buffers[k] for k in keys)
-    if not (mp.dim() == 1 and mp.shape == sc.shape == gid.shape):
-        raise RuntimeError("mvg_eval_match: buffers are not those of eval_buffers")
-    lib = L.load()
-    with _timed("eval_match"):
-        L.check(lib.mvg_eval_match(L.ptr(dets), L.ptr(count), L.ptr(joints_3d), L.ptr(joints_3d_vis), L.ptr(num_person), B, R, J, G,
-                                   L.ptr(mp), L.ptr(sc), L.ptr(gid), mp.numel(), L.ptr(state), L.stream_ptr()), "mvg_eval_match")
+    _launch("mvg_eval_match", dets, count, joints_3d, joints_3d_vis, num_person, B, R, J, G, mp, sc, gid, capacity, state,
+            label="eval_match")
 
 
 def eval_pcp(dets, count, joints_3d, joints_3d_vis, num_person, buffers, recall_threshold=500.0, alpha=0.5):
@@ -1384,24 +1352,27 @@ def eval_pcp(dets, count, joints_3d, joints_3d_vis, num_person, buffers, recall_
     as evaluate.evaluate_pcp restates it).  Inputs as eval_match, in the 14-joint format; actor slot a of element b is annotated
     when some joints_3d_vis[b, a] != 0.  Adds to correct / total / bone_correct and the state block of ``buffers``."""
     keys = ("correct", "total", "bone_correct", "state")
-    B, R, J, G = _eval_inputs("mvg_eval_pcp", dets, count, joints_3d, joints_3d_vis, num_person, buffers, keys)
+    A = buffers["correct"].numel()           # as many actors as the caller's counters have
+    B, R, J, G = _eval_inputs("mvg_eval_pcp", dets, count, joints_3d, joints_3d_vis, num_person, buffers, keys, dict(actors=A))
     correct, total, bones, state = (buffers[k] for k in keys)
-    A = correct.numel()
-    if tuple(total.shape) != (A,) or tuple(bones.shape) != (A, 10):
-        raise RuntimeError("mvg_eval_pcp: buffers are not those of eval_buffers")
-    lib = L.load()
-    with _timed("eval_pcp"):
-        L.check(lib.mvg_eval_pcp(L.ptr(dets), L.ptr(count), L.ptr(joints_3d), L.ptr(joints_3d_vis), L.ptr(num_person), B, R, J, G, A,
-                                 float(recall_threshold), float(alpha), L.ptr(correct), L.ptr(total), L.ptr(bones), L.ptr(state),
-                                 L.stream_ptr()), "mvg_eval_pcp")
+    _launch("mvg_eval_pcp", dets, count, joints_3d, joints_3d_vis, num_person, B, R, J, G, A, float(recall_threshold), float(alpha),
+            correct, total, bones, state, label="eval_pcp")
 
 
-LAP_MAX_N = 64                     # MVG_LAP_MAX_N
-LAP_BIG = 1e15                     # MVG_LAP_BIG
-TRACK_MAX_D, TRACK_MAX_T, TRACK_MAX_J, TRACK_MAX_R, TRACK_MAX_B = 64, 64, 32, 16384, 4096      # MVG_TRACK_MAX_*
+LAP_MAX_N, LAP_BIG = _D["MVG_LAP_MAX_N"], _D["MVG_LAP_BIG"]
+TRACK_MAX_D, TRACK_MAX_T, TRACK_MAX_J, TRACK_MAX_R, TRACK_MAX_B = (_D["MVG_TRACK_MAX_" + k] for k in "DTJRB")
 TRACK_STATE = ("frames", "matches", "births", "deaths", "overflow", "dropped", "active", "reserved")
-_TRACK_KEYS = (("id", torch.int32), ("hits", torch.int32), ("misses", torch.int32), ("born", torch.int64), ("score", torch.float32),
-               ("pose", torch.float32), ("next_id", torch.int32), ("state", torch.int64), ("ids", torch.int32), ("slots", torch.int32))
+_TRACK = _Layout("track_buffers", ("id", torch.int32, ("B", "T"), -1), ("hits", torch.int32, ("B", "T"), 0),
+                 ("misses", torch.int32, ("B", "T"), 0), ("born", torch.int64, ("B", "T"), 0), ("score", torch.float32, ("B", "T"), 0),
+                 ("pose", torch.float32, ("B", "T", "J", 3), 0), ("next_id", torch.int32, ("B",), 0),
+                 ("state", torch.int64, (len(TRACK_STATE),), 0), ("ids", torch.int32, ("B", "R"), -1),
+                 ("slots", torch.int32, ("B", "R"), -1))
+_TRACK_MOTION = _Layout("track_motion_buffers", ("mean", torch.float64, ("B", "T", "J", 2, 3), 0),
+                        ("var", torch.float64, ("B", "T", 3), 0), ("row_pose", torch.float32, ("B", "R", "J", 3), 0))
+
+
+def _check_track_limits(who, B, T, J, R):
+    _check_limits(who, ("B", B, TRACK_MAX_B), ("T", T, TRACK_MAX_T), ("J", J, TRACK_MAX_J), ("R", R, TRACK_MAX_R))
 
 
 def linear_assignment(cost, n=None, m=None):
@@ -1425,10 +1396,7 @@ def linear_assignment(cost, n=None, m=None):
                          % (B, TRACK_MAX_B, N, M, LAP_MAX_N))
     col = torch.empty((B, N), dtype=torch.int32, device=cost.device)
     total = torch.empty((B,), dtype=torch.float64, device=cost.device)
-    lib = L.load()
-    with _timed("linear_assignment"):
-        L.check(lib.mvg_linear_assignment(L.ptr(cost), L.ptr(n), L.ptr(m), B, N, M, L.ptr(col), L.ptr(total), L.stream_ptr()),
-                "mvg_linear_assignment")
+    _launch("mvg_linear_assignment", cost, n, m, B, N, M, col, total, label="linear_assignment")
     return col, total
 
 
@@ -1438,15 +1406,8 @@ def track_buffers(B, T, J, R, device="cuda"):
     (TRACK_STATE) -- plus the static outputs ids, slots (B, R) int32 (-1).  Allocated once and kept alive by the caller: a captured
     HIP graph addresses them by pointer, like pose_nms_buffers."""
     B, T, J, R = int(B), int(T), int(J), int(R)
-    if not (1 <= B <= TRACK_MAX_B and 1 <= T <= TRACK_MAX_T and 1 <= J <= TRACK_MAX_J and 1 <= R <= TRACK_MAX_R):
-        raise L.MvgError("track_buffers: unsupported shape B = %d (<= %d), T = %d (<= %d), J = %d (<= %d), R = %d (<= %d)"
-                         % (B, TRACK_MAX_B, T, TRACK_MAX_T, J, TRACK_MAX_J, R, TRACK_MAX_R))
-    shapes = dict(id=(B, T), hits=(B, T), misses=(B, T), born=(B, T), score=(B, T), pose=(B, T, J, 3), next_id=(B,),
-                  state=(len(TRACK_STATE),), ids=(B, R), slots=(B, R))
-    out = {k: torch.zeros(shapes[k], dtype=dt, device=device) for k, dt in _TRACK_KEYS}
-    for k in ("id", "ids", "slots"):
-        out[k].fill_(-1)
-    return out
+    _check_track_limits("track_buffers", B, T, J, R)
+    return _TRACK.alloc(dict(B=B, T=T, J=J, R=R), device)
 
 
 def track_update(dets, count, buffers, max_dist=500.0, max_misses=10, min_hits=1):
@@ -1456,36 +1417,22 @@ def track_update(dets, count, buffers, max_dist=500.0, max_misses=10, min_hits=1
     than max_dist (the unit of the poses) costing max_dist like a non-match; matched tracks take the detection, the others age and
     are freed after more than max_misses misses, unmatched detections open tracks in the lowest free slots.  -> (ids, slots), the
     (B, R) int32 tensors of ``buffers``: per row the track's id (once it has min_hits hits) and slot, else -1."""
-    tensors = [buffers[k] for k, _ in _TRACK_KEYS]
+    tensors = [buffers[k] for k in _TRACK.keys]
     L.require_cuda(dets, count, *tensors)
-    if dets.dim() != 4 or dets.shape[-1] != 5 or dets.dtype != torch.float32:
-        raise RuntimeError("mvg_track_update: dets (B, R, J, 5) float32 expected")
-    B, R, J = dets.shape[:3]
-    if count is not None and (count.dtype != torch.int32 or tuple(count.shape) != (B, 2)):
-        raise RuntimeError("mvg_track_update: count (B, 2) int32 or None expected")
-    if not all(t is None or t.is_contiguous() for t in (dets, count, *tensors)):
+    B, R, J = _check_dets("mvg_track_update", dets, count)
+    if not all(t is None or t.is_contiguous() for t in (dets, count)):
         raise RuntimeError("mvg_track_update: every tensor must be contiguous")
     ident = buffers["id"]
-    T = ident.shape[1] if ident.dim() == 2 else 0
-    shapes = dict(id=(B, T), hits=(B, T), misses=(B, T), born=(B, T), score=(B, T), pose=(B, T, J, 3), next_id=(B,),
-                  state=(len(TRACK_STATE),), ids=(B, R), slots=(B, R))
-    if any(t.dtype != dt or tuple(t.shape) != shapes[k] for (k, dt), t in zip(_TRACK_KEYS, tensors)):
-        raise RuntimeError("mvg_track_update: buffers are not those of track_buffers for dets %s" % (tuple(dets.shape),))
-    if not (1 <= B <= TRACK_MAX_B and 1 <= T <= TRACK_MAX_T and 1 <= J <= TRACK_MAX_J and 1 <= R <= TRACK_MAX_R):
-        raise L.MvgError("mvg_track_update: unsupported shape B = %d (<= %d), T = %d (<= %d), J = %d (<= %d), R = %d (<= %d)"
-                         % (B, TRACK_MAX_B, T, TRACK_MAX_T, J, TRACK_MAX_J, R, TRACK_MAX_R))
+    T = ident.shape[1] if ident.dim() == 2 else 0         # as many slots as the caller's state has
+    _TRACK.check(buffers, dict(B=B, T=T, J=J, R=R), who="mvg_track_update")
+    _check_track_limits("mvg_track_update", B, T, J, R)
     if not (0.0 <= float(max_dist) <= LAP_BIG) or int(max_misses) < 0 or int(min_hits) < 0:
         raise L.MvgError("mvg_track_update: 0 <= max_dist <= %g, max_misses >= 0 and min_hits >= 0 expected (got %r, %r, %r)"
                          % (LAP_BIG, max_dist, max_misses, min_hits))
-    lib = L.load()
-    with _timed("track_update"):
-        L.check(lib.mvg_track_update(L.ptr(dets), L.ptr(count), B, R, J, T, *(L.ptr(t) for t in tensors[:8]), float(max_dist),
-                                     int(max_misses), int(min_hits), L.ptr(buffers["ids"]), L.ptr(buffers["slots"]),
-                                     L.stream_ptr()), "mvg_track_update")
+    state = (buffers[k] for k in ("id", "hits", "misses", "born", "score", "pose", "next_id", "state"))
+    _launch("mvg_track_update", dets, count, B, R, J, T, *state, float(max_dist), int(max_misses), int(min_hits), buffers["ids"],
+            buffers["slots"], label="track_update")
     return buffers["ids"], buffers["slots"]
-
-
-_TRACK_MOTION_KEYS = (("mean", torch.float64), ("var", torch.float64), ("row_pose", torch.float32))
 
 
 def track_motion_buffers(B, T, J, R, device="cuda"):
@@ -1493,34 +1440,22 @@ def track_motion_buffers(B, T, J, R, device="cuda"):
     xyz per joint), var (B, T, 3) fp64 (pxx, pxv, pvv: one covariance per track) -- plus the static output row_pose (B, R, J, 3)
     fp32, the filtered pose of every row.  All zeros; allocated once and kept alive by the caller like track_buffers."""
     B, T, J, R = int(B), int(T), int(J), int(R)
-    if not (1 <= B <= TRACK_MAX_B and 1 <= T <= TRACK_MAX_T and 1 <= J <= TRACK_MAX_J and 1 <= R <= TRACK_MAX_R):
-        raise L.MvgError("track_motion_buffers: unsupported shape B = %d (<= %d), T = %d (<= %d), J = %d (<= %d), R = %d (<= %d)"
-                         % (B, TRACK_MAX_B, T, TRACK_MAX_T, J, TRACK_MAX_J, R, TRACK_MAX_R))
-    shapes = dict(mean=(B, T, J, 2, 3), var=(B, T, 3), row_pose=(B, R, J, 3))
-    return {k: torch.zeros(shapes[k], dtype=dt, device=device) for k, dt in _TRACK_MOTION_KEYS}
+    _check_track_limits("track_motion_buffers", B, T, J, R)
+    return _TRACK_MOTION.alloc(dict(B=B, T=T, J=J, R=R), device)
 
 
 def _track_motion_inputs(name, buffers, motion, keys):
     """the checks track_predict and track_correct share -> (B, T, J, R)"""
-    tensors = [buffers[k] for k in keys] + [motion[k] for k, _ in _TRACK_MOTION_KEYS]
-    L.require_cuda(*tensors)
+    L.require_cuda(*(buffers[k] for k in keys), *(motion[k] for k in _TRACK_MOTION.keys))
     pose = buffers["pose"]
     if pose.dim() != 4 or pose.shape[-1] != 3:
         raise RuntimeError("%s: buffers are not those of track_buffers" % name)
     B, T, J = pose.shape[:3]
     R = buffers["slots"].shape[1] if buffers["slots"].dim() == 2 else 0
-    want = dict(id=(B, T), hits=(B, T), misses=(B, T), pose=(B, T, J, 3), slots=(B, R))
-    dtypes = dict(_TRACK_KEYS)
-    if any(buffers[k].dtype != dtypes[k] or tuple(buffers[k].shape) != want[k] for k in keys):
-        raise RuntimeError("%s: buffers are not those of track_buffers" % name)
-    shapes = dict(mean=(B, T, J, 2, 3), var=(B, T, 3), row_pose=(B, R, J, 3))
-    if any(motion[k].dtype != dt or tuple(motion[k].shape) != shapes[k] for k, dt in _TRACK_MOTION_KEYS):
-        raise RuntimeError("%s: motion buffers are not those of track_motion_buffers for pose %s" % (name, tuple(pose.shape)))
-    if not all(t.is_contiguous() for t in tensors):
-        raise RuntimeError("%s: every tensor must be contiguous" % name)
-    if not (1 <= B <= TRACK_MAX_B and 1 <= T <= TRACK_MAX_T and 1 <= J <= TRACK_MAX_J and 1 <= R <= TRACK_MAX_R):
-        raise L.MvgError("%s: unsupported shape B = %d (<= %d), T = %d (<= %d), J = %d (<= %d), R = %d (<= %d)"
-                         % (name, B, TRACK_MAX_B, T, TRACK_MAX_T, J, TRACK_MAX_J, R, TRACK_MAX_R))
+    dims = dict(B=B, T=T, J=J, R=R)
+    _TRACK.check(buffers, dims, keys, who=name)
+    _TRACK_MOTION.check(motion, dims, who=name)
+    _check_track_limits(name, B, T, J, R)
     return B, T, J, R
 
 
@@ -1533,10 +1468,7 @@ def track_predict(buffers, motion, dt=1.0, q=25.0):
     dt, q = float(dt), float(q)
     if not (0.0 < dt < float("inf")) or not (0.0 <= q <= LAP_BIG):
         raise L.MvgError("mvg_track_predict: finite dt > 0 and 0 <= q <= %g expected (got %r, %r)" % (LAP_BIG, dt, q))
-    lib = L.load()
-    with _timed("track_predict"):
-        L.check(lib.mvg_track_predict(B, T, J, L.ptr(buffers["id"]), L.ptr(buffers["pose"]), L.ptr(motion["mean"]),
-                                      L.ptr(motion["var"]), dt, q, L.stream_ptr()), "mvg_track_predict")
+    _launch("mvg_track_predict", B, T, J, buffers["id"], buffers["pose"], motion["mean"], motion["var"], dt, q, label="track_predict")
 
 
 def track_correct(buffers, motion, r=400.0, v0=2500.0):
@@ -1549,23 +1481,18 @@ def track_correct(buffers, motion, r=400.0, v0=2500.0):
     r, v0 = float(r), float(v0)
     if not (0.0 < r <= LAP_BIG) or not (0.0 <= v0 <= LAP_BIG):
         raise L.MvgError("mvg_track_correct: 0 < r <= %g and 0 <= v0 <= %g expected (got %r, %r)" % (LAP_BIG, LAP_BIG, r, v0))
-    lib = L.load()
-    with _timed("track_correct"):
-        L.check(lib.mvg_track_correct(B, R, T, J, *(L.ptr(buffers[k]) for k in ("id", "hits", "misses", "slots", "pose")),
-                                      L.ptr(motion["mean"]), L.ptr(motion["var"]), r, v0, L.ptr(motion["row_pose"]),
-                                      L.stream_ptr()), "mvg_track_correct")
+    _launch("mvg_track_correct", B, R, T, J, *(buffers[k] for k in ("id", "hits", "misses", "slots", "pose")), motion["mean"],
+            motion["var"], r, v0, motion["row_pose"], label="track_correct")
     return motion["row_pose"]
 
 
-TRACK_EVAL_MAX_P, TRACK_EVAL_MAX_K = 64, 4096      # MVG_TRACK_EVAL_MAX_*
+TRACK_EVAL_MAX_P, TRACK_EVAL_MAX_K = _D["MVG_TRACK_EVAL_MAX_P"], _D["MVG_TRACK_EVAL_MAX_K"]
 TRACK_EVAL_STATE = ("frames", "gt", "hyp", "matches", "misses", "false_pos", "switches", "kept", "dropped", "unreported", "bad_id",
                     "id_overflow", "reserved")      # MVG_TRACK_EVAL_WORDS
-_TRACK_EVAL_KEYS = (("last_track", torch.int32), ("counters", torch.int64), ("dist_sum", torch.float64), ("seen", torch.int64),
-                    ("covered", torch.int64), ("overlap", torch.int32))
-
-
-def _track_eval_shapes(B, P, K):
-    return dict(last_track=(B, P), counters=(B, len(TRACK_EVAL_STATE)), dist_sum=(B,), seen=(B, P), covered=(B, P), overlap=(B, P, K))
+_TRACK_EVAL = _Layout("track_eval_buffers", ("last_track", torch.int32, ("B", "P"), -1),
+                      ("counters", torch.int64, ("B", len(TRACK_EVAL_STATE)), 0), ("dist_sum", torch.float64, ("B",), 0),
+                      ("seen", torch.int64, ("B", "P"), 0), ("covered", torch.int64, ("B", "P"), 0),
+                      ("overlap", torch.int32, ("B", "P", "K"), 0))
 
 
 def track_eval_buffers(B, P, K, device="cuda"):
@@ -1573,13 +1500,8 @@ def track_eval_buffers(B, P, K, device="cuda"):
     (B, len(TRACK_EVAL_STATE)) int64, dist_sum (B) fp64, seen, covered (B, P) int64, overlap (B, P, K) int32, zeros.  Allocated
     once and kept alive by the caller, like track_buffers."""
     B, P, K = int(B), int(P), int(K)
-    if not (1 <= B <= TRACK_MAX_B and 1 <= P <= TRACK_EVAL_MAX_P and 1 <= K <= TRACK_EVAL_MAX_K):
-        raise L.MvgError("track_eval_buffers: unsupported shape B = %d (<= %d), P = %d (<= %d), K = %d (<= %d)"
-                         % (B, TRACK_MAX_B, P, TRACK_EVAL_MAX_P, K, TRACK_EVAL_MAX_K))
-    shapes = _track_eval_shapes(B, P, K)
-    out = {k: torch.zeros(shapes[k], dtype=dt, device=device) for k, dt in _TRACK_EVAL_KEYS}
-    out["last_track"].fill_(-1)
-    return out
+    _check_limits("track_eval_buffers", ("B", B, TRACK_MAX_B), ("P", P, TRACK_EVAL_MAX_P), ("K", K, TRACK_EVAL_MAX_K))
+    return _TRACK_EVAL.alloc(dict(B=B, P=P, K=K), device)
 
 
 def track_eval(dets, count, ids, joints_3d, joints_3d_vis, num_person, buffers, dist_thr=500.0, row_pose=None, person_id=None):
@@ -1591,34 +1513,23 @@ def track_eval(dets, count, ids, joints_3d, joints_3d_vis, num_person, buffers, 
     with an id are matched to the persons by the CLEAR-MOT rules of include/mvg_decoder.h (last frame's pairs first while within
     dist_thr, the rest by minimum-cost assignment) and misses, false positives, identity switches, the matched distance and the
     person x track id overlap table are accumulated.  -> buffers."""
-    tensors = [buffers[k] for k, _ in _TRACK_EVAL_KEYS]
+    name = "mvg_track_eval"
+    keys = ("last_track", "counters", "dist_sum", "seen", "covered", "overlap")
+    tensors = [buffers[k] for k in keys]
     L.require_cuda(dets, count, ids, row_pose, joints_3d, joints_3d_vis, num_person, person_id, *tensors)
-    if dets.dim() != 4 or dets.shape[-1] != 5 or dets.dtype != torch.float32:
-        raise RuntimeError("mvg_track_eval: dets (B, R, J, 5) float32 expected")
-    B, R, J = dets.shape[:3]
-    if count is not None and (count.dtype != torch.int32 or tuple(count.shape) != (B, 2)):
-        raise RuntimeError("mvg_track_eval: count (B, 2) int32 or None expected")
+    B, R, J = _check_dets(name, dets, count)
     if ids.dtype != torch.int32 or tuple(ids.shape) != (B, R):
         raise RuntimeError("mvg_track_eval: ids (B, R) int32 expected")
     if row_pose is not None and (row_pose.dtype != torch.float32 or tuple(row_pose.shape) != (B, R, J, 3)):
         raise RuntimeError("mvg_track_eval: row_pose (B, R, J, 3) float32 or None expected")
-    if joints_3d.dim() != 4 or joints_3d.dtype != torch.float32 or joints_3d.shape[0] != B or tuple(joints_3d.shape[2:]) != (J, 3):
-        raise RuntimeError("mvg_track_eval: joints_3d (B, G, J, 3) float32 expected")
-    G = joints_3d.shape[1]
-    if joints_3d_vis.dtype != torch.float32 or tuple(joints_3d_vis.shape) != (B, G, J):
-        raise RuntimeError("mvg_track_eval: joints_3d_vis (B, G, J) float32 expected")
-    if num_person.dtype != torch.int32 or tuple(num_person.shape) != (B,):
-        raise RuntimeError("mvg_track_eval: num_person (B) int32 expected")
+    G = _check_ground_truth(name, joints_3d, joints_3d_vis, num_person, B, J)
     if person_id is not None and (person_id.dtype != torch.int32 or tuple(person_id.shape) != (B, G)):
         raise RuntimeError("mvg_track_eval: person_id (B, G) int32 or None expected")
-    if not all(t is None or t.is_contiguous() for t in (dets, count, ids, row_pose, joints_3d, joints_3d_vis, num_person, person_id,
-                                                         *tensors)):
+    if not all(t is None or t.is_contiguous() for t in (dets, count, ids, row_pose, joints_3d, joints_3d_vis, num_person, person_id)):
         raise RuntimeError("mvg_track_eval: every tensor must be contiguous")
     overlap = buffers["overlap"]
-    P, K = (overlap.shape[1], overlap.shape[2]) if overlap.dim() == 3 else (0, 0)
-    shapes = _track_eval_shapes(B, P, K)
-    if any(t.dtype != dt or tuple(t.shape) != shapes[k] for (k, dt), t in zip(_TRACK_EVAL_KEYS, tensors)):
-        raise RuntimeError("mvg_track_eval: buffers are not those of track_eval_buffers for dets %s" % (tuple(dets.shape),))
+    P, K = (overlap.shape[1], overlap.shape[2]) if overlap.dim() == 3 else (0, 0)      # as the caller's tables have them
+    _TRACK_EVAL.check(buffers, dict(B=B, P=P, K=K), who=name)
     if not (1 <= B <= TRACK_MAX_B and 1 <= R <= TRACK_MAX_R and 1 <= J <= TRACK_MAX_J and 1 <= G <= P <= TRACK_EVAL_MAX_P
             and 1 <= K <= TRACK_EVAL_MAX_K):
         raise L.MvgError("mvg_track_eval: unsupported shape B = %d (<= %d), R = %d (<= %d), J = %d (<= %d), G = %d <= P = %d (<= %d), "
@@ -1626,22 +1537,19 @@ def track_eval(dets, count, ids, joints_3d, joints_3d_vis, num_person, buffers, 
                                              TRACK_EVAL_MAX_K))
     if not (0.0 <= float(dist_thr) <= LAP_BIG):
         raise L.MvgError("mvg_track_eval: 0 <= dist_thr <= %g expected (got %r)" % (LAP_BIG, dist_thr))
-    lib = L.load()
-    with _timed("track_eval"):
-        L.check(lib.mvg_track_eval(L.ptr(dets), L.ptr(count), L.ptr(ids), L.ptr(row_pose), L.ptr(joints_3d), L.ptr(joints_3d_vis),
-                                   L.ptr(num_person), L.ptr(person_id), B, R, J, G, P, K, float(dist_thr),
-                                   *(L.ptr(t) for t in tensors), L.stream_ptr()), "mvg_track_eval")
+    _launch(name, dets, count, ids, row_pose, joints_3d, joints_3d_vis, num_person, person_id, B, R, J, G, P, K, float(dist_thr),
+            *tensors, label="track_eval")
     return buffers
 
 
-ST_MAX_J, ST_MAX_V, ST_MAX_STEPS = 17, 32, 8       # MVG_ST_MAX_*
-ST_METHODS = {"LS": 0, "ST": 1}                     # MVG_ST_LS, MVG_ST_ST
+ST_MAX_J, ST_MAX_V, ST_MAX_STEPS = _D["MVG_ST_MAX_J"], _D["MVG_ST_MAX_V"], _D["MVG_ST_MAX_STEPS"]
+ST_METHODS = {"LS": _D["MVG_ST_LS"], "ST": _D["MVG_ST_ST"]}
+_STRUCTURAL = _Layout("structural_buffers", ("poses", torch.float32, ("B", "P", "J", 3), 0), ("status", torch.int32, ("B", "P"), -1))
 
 
 def structural_check(parent, n_steps=1, method="ST"):
     """the host-side argument checks of structural_triangulate: parent a tree rooted at joint 0 with 2 .. ST_MAX_J joints, n_steps
     in 1 .. ST_MAX_STEPS, method "ST" or "LS" -> (parent as a ctypes int array, the method's code)"""
-    import ctypes as C
     if torch.is_tensor(parent):
         if parent.is_cuda:
             raise RuntimeError("mvg_structural_triangulate: parent travels by value with the launch: host ints expected, not a device "
@@ -1674,8 +1582,7 @@ def structural_buffers(B, P, J, device="cuda"):
     B, P, J = int(B), int(P), int(J)
     if not (B >= 1 and P >= 1 and 2 <= J <= ST_MAX_J):
         raise L.MvgError("structural_buffers: unsupported shape B = %d, P = %d, J = %d (2 .. %d)" % (B, P, J, ST_MAX_J))
-    return dict(poses=torch.zeros((B, P, J, 3), dtype=torch.float32, device=device),
-                status=torch.full((B, P), -1, dtype=torch.int32, device=device))
+    return _STRUCTURAL.alloc(dict(B=B, P=P, J=J), device)
 
 
 def structural_triangulate(ud, conf, Pm, parent, bone_lengths, valid=None, rows=None, count=None, n_steps=1, method="ST", out=None):
@@ -1734,12 +1641,7 @@ def structural_triangulate(ud, conf, Pm, parent, bone_lengths, valid=None, rows=
         out = structural_buffers(B, P, J, ud.device)
     X, status = out["poses"], out["status"]
     L.require_cuda(X, status)
-    if (X.dtype != torch.float32 or tuple(X.shape) != (B, P, J, 3) or status.dtype != torch.int32 or tuple(status.shape) != (B, P)
-            or not (X.is_contiguous() and status.is_contiguous())):
-        raise RuntimeError("%s: out buffers do not fit (B, P, J) = (%d, %d, %d) (see structural_buffers)" % (name, B, P, J))
-    lib = L.load()
-    with _timed("structural_triangulate"):
-        L.check(lib.mvg_structural_triangulate(L.ptr(ud), L.ptr(conf), L.ptr(Pm), L.ptr(valid), L.ptr(rows), rows_ld, L.ptr(count),
-                                               parent_c, L.ptr(bone_lengths), per_person, method_c, int(n_steps), L.ptr(X),
-                                               L.ptr(status), V, B, NQ, P, J, L.stream_ptr()), name)
+    _STRUCTURAL.check(out, dict(B=B, P=P, J=J), who=name)
+    _launch(name, ud, conf, Pm, valid, rows, rows_ld, count, parent_c, bone_lengths, per_person, method_c, int(n_steps), X, status,
+            V, B, NQ, P, J, label="structural_triangulate")
     return X, status

@@ -32,9 +32,95 @@ def test_library_exports_every_declared_symbol():
 
 
 def test_ctypes_table_matches_header():
-    declared = set(_header_symbols()) - {"mvg_version"}
-    assert declared == set(_lib.SIGNATURES), declared ^ set(_lib.SIGNATURES)
-    assert _lib.load().mvg_version().startswith(b"mvgformer_amd")
+    """the parser that builds the ctypes table finds exactly the names this file's own regex finds (mvg_version included), and
+    each resolves in the built library with the parsed types set on it"""
+    assert sorted(_lib.PROTOTYPES) == sorted(_lib.SIGNATURES) == _header_symbols()
+    lib = _lib.load()
+    for name, argtypes in _lib.SIGNATURES.items():
+        if name != "mvg_set_tuning":                 # load() wraps this one in a Python function
+            fn = getattr(lib, name)
+            assert list(fn.argtypes) == argtypes and fn.restype is _lib.PROTOTYPES[name][0], name
+    assert lib.mvg_version().startswith(b"mvgformer_amd")
+
+
+def test_parsed_signatures_equal_the_ones_written_out_here():
+    """one entry point per scalar kind, two long ones and the return types, as the hand-kept table had them before the header
+    became the declaration"""
+    i, f, d, z, P = ctypes.c_int, ctypes.c_float, ctypes.c_double, ctypes.c_size_t, _lib.TensorPtr
+    pinned = {
+        "mvg_device_info": [ctypes.c_char_p, i, P],
+        "mvg_set_tuning": [ctypes.c_char_p, i],
+        "mvg_class_head": [P, P, P, f, P, P, P, P, i, i, i, i, P],
+        "mvg_pose_nms": [P, i, i, i, d, i, i, P, z, P, P, P, i, P],
+        "mvg_pyramid_f32h": [P, P, i, P, P, i, P, P, ctypes.c_int64, i, P],
+        "mvg_sym4_eigh": [P, P, P, ctypes.c_long, P],
+        "mvg_optim_step": [P, i, P, i, P, i, P, z, P, z, P, f, i, P, P],
+        "mvg_track_update": [P, P, i, i, i, i, P, P, P, P, P, P, P, P, d, i, i, P, P, P],
+        "mvg_version": [],
+    }
+    for name, argtypes in pinned.items():
+        assert _lib.SIGNATURES[name] == argtypes, name
+    restypes = {name: restype for name, (restype, _) in _lib.PROTOTYPES.items()}
+    assert restypes.pop("mvg_version") is ctypes.c_char_p
+    assert {name for name, r in restypes.items() if r is z} == {
+        "mvg_bin_pairs_workspace", "mvg_msda_backward_det_workspace", "mvg_msda_backward_bal_workspace", "mvg_knn_match_workspace",
+        "mvg_hungarian_match_workspace", "mvg_criterion_workspace", "mvg_optim_workspace", "mvg_pose_nms_workspace",
+        "mvg_self_attention_backward_workspace"}
+    assert all(r is z or r is i for r in restypes.values())
+    assert issubclass(P, ctypes.c_void_p) and ctypes.sizeof(P) == ctypes.sizeof(ctypes.c_void_p)
+
+
+def test_parser_reads_a_header_text_and_refuses_what_it_does_not_know():
+    protos, defines = _lib.parse_header("""
+        /* int mvg_in_a_comment(int x); */
+        #define MVG_N 7   /* a limit */
+        #define MVG_BIG 1e15
+        #define MVG_GUARD
+        extern "C" {
+        int mvg_a(const float* const* x, int64_t n,
+                  const char* key, void* stream);
+        size_t mvg_b(void);
+        }""")
+    assert defines == {"MVG_N": 7, "MVG_BIG": 1e15} and isinstance(defines["MVG_N"], int) and isinstance(defines["MVG_BIG"], float)
+    assert protos == {"mvg_a": (ctypes.c_int, [(_lib.TensorPtr, "x"), (ctypes.c_int64, "n"), (ctypes.c_char_p, "key"),
+                                                 (_lib.TensorPtr, "stream")]), "mvg_b": (ctypes.c_size_t, [])}
+    for bad in ("int mvg_a(unsigned n);", "int mvg_a(struct dims d);", "int mvg_a(int);", "short mvg_a(int n);", "float* mvg_a(int n);",
+                "int mvg_a(int n", "int mvg_a(int n[3]);", "typedef int mvg_t;", "#define MVG_N (3 + 4)\nint mvg_a(int n);"):
+        with pytest.raises(_lib.MvgError, match="mvg_decoder.h"):
+            _lib.parse_header(bad)
+
+
+def test_header_defines_are_numbers():
+    D = _lib.DEFINES
+    assert isinstance(D["MVG_LAP_BIG"], float) and D["MVG_LAP_BIG"] == 1e15
+    assert isinstance(D["MVG_NMS_MAX_N"], int) and D["MVG_NMS_MAX_N"] == 2048
+    assert D["MVG_E_BADARG"] == 10001 and (D["MVG_F32"], D["MVG_BF16"]) == (0, 1) == (_lib.MVG_F32, _lib.MVG_BF16)
+    assert all(k.startswith("MVG_") and type(v) in (int, float) for k, v in D.items()) and "MVG_DECODER_H" not in D
+    from mvgformer_amd import ops
+    assert ops.MATCH_METHODS == {"KNN": 0, "multiple": 1} and ops.HUNGARIAN_METHODS == {"hungarian": 2, "hungarian-dis": 3}
+    assert ops.ST_METHODS == {"LS": 0, "ST": 1} and (ops.HUNGARIAN_MAX_G, ops.HUNGARIAN_MAX_NQ) == (64, 4096)
+    assert (ops.OPTIM_CHUNK, ops.OPTIM_TENSOR_WORDS, ops.OPTIM_GROUP_WORDS, ops.OPTIM_STATE_HEADER, ops.OPTIM_STATE_PER_GROUP) \
+        == (4096, 6, 6, 64, 16)
+
+
+def test_tensor_pointer_argtype():
+    """_lib.TensorPtr through libc's memcmp: a tensor passes its data pointer, everything c_void_p takes still passes, a zero-element
+    tensor is NULL, a Python float is refused"""
+    libc = ctypes.CDLL(None)
+    memcmp = libc.memcmp
+    memcmp.argtypes, memcmp.restype = [_lib.TensorPtr, _lib.TensorPtr, ctypes.c_size_t], ctypes.c_int
+    data = [3, 1, 4, 1, 5, 9, 2, 6]
+    t = torch.tensor(data, dtype=torch.uint8)
+    arr = (ctypes.c_uint8 * 8)(*data)
+    for other in (arr, ctypes.c_void_p(ctypes.addressof(arr)), ctypes.addressof(arr), ctypes.byref(arr), t.clone(), _lib.ptr(t)):
+        assert memcmp(t, other, 8) == 0 and memcmp(other, t, 8) == 0
+    assert memcmp(t, torch.tensor(data[:7] + [7], dtype=torch.uint8), 8) != 0
+    assert memcmp(t[2:], (ctypes.c_uint8 * 2)(4, 1), 2) == 0                    # a view passes where it starts
+    empty = torch.empty((0,), dtype=torch.uint8)
+    assert memcmp(empty, None, 0) == 0 and memcmp(None, t, 0) == 0
+    assert _lib.TensorPtr.from_param(empty) is None and _lib.TensorPtr.from_param(None) is None      # NULL, as ctypes passes it
+    with pytest.raises(ctypes.ArgumentError):
+        memcmp(t, 1.5, 8)
 
 
 def test_camera_stride_matches_header():

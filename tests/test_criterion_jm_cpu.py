@@ -90,7 +90,7 @@ def test_header_declares_the_joint_map_entry_points_and_the_ctypes_table_matches
         m = re.search(r"\bint\s+%s\s*\(([^)]*)\)\s*;" % name, src)
         assert m, "%s is not declared in include/mvg_decoder.h" % name
         args = [a.strip() for a in m.group(1).split(",")]
-        want = [C.c_void_p if "*" in a else ctype_of[a.split()[0]] for a in args]
+        want = [_lib.TensorPtr if "*" in a else ctype_of[a.split()[0]] for a in args]      # the table's type of a device pointer
         assert _lib.SIGNATURES[name] == want, name
         assert any(re.fullmatch(r"const int\s*\*\s*joint_map", a) for a in args) and "int Jp" in args and "int Jc" in args
         assert hasattr(_lib.load(), name)
