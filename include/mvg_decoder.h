@@ -73,6 +73,9 @@ const char* mvg_version(void);
  * Every knob but f32_split, auto_small (chain B's 32-row tiles sum the FFN in another order) and chain_rm = 256 selects
  * bit-identical results (tests/test_hip_parity.py: test_every_kernel_variant_behind_a_tuning_knob). */
 int mvg_set_tuning(const char* key, int value);
+/* Getter and enumerator of the same knobs (process-global and not thread-safe like the setter; host-only): for 0 <= index < the
+ * number of knobs stores the knob's key (a static string) and its current value and returns 0, MVG_E_BADARG otherwise. */
+int mvg_tuning_knob(int index, const char** key, int* value);
 
 /* ---- Deformable.deform_forward / deform_backward (deform.h:32-72) -------------------
  * value (N,S,M,D); spatial_shapes (L,2) int64 (H,W); level_start_index (L,) int64;

@@ -9,6 +9,7 @@ import, so a new entry point is bound by declaring it there.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 import re
@@ -88,7 +89,7 @@ MVG_F32, MVG_BF16 = DEFINES["MVG_F32"], DEFINES["MVG_BF16"]
 CAM_STRIDE = DEFINES["MVG_CAM_STRIDE"]
 
 _lib = None
-TUNING = {}     # knob values set through mvg_set_tuning in this process (library defaults are not listed)
+TUNING = {}     # every knob of the library with its current value, from load() on (mvg_tuning_knob, kept current by mvg_set_tuning)
 
 
 def load():
@@ -106,7 +107,7 @@ def load():
         fn.argtypes = argtypes
         fn.restype = PROTOTYPES[name][0]
     # every knob change goes through this wrapper, so that host-side caches that depend on a knob (DQDecoderLayer's rows of
-    # all-masked tiles: computed by the GEMM form that is active) can key on its value: TUNING[key] = last value set
+    # all-masked tiles: computed by the GEMM form that is active) can key on its value: TUNING[key] = the knob's current value
     raw_set = lib.mvg_set_tuning
 
     def set_tuning(key, value):
@@ -115,12 +116,31 @@ def load():
             TUNING[key.decode() if isinstance(key, bytes) else str(key)] = int(value)
         return rc
     lib.mvg_set_tuning = set_tuning
+    key, value, index = C.c_char_p(), C.c_int(), 0
+    while lib.mvg_tuning_knob(index, C.byref(key), C.byref(value)) == 0:
+        TUNING[key.value.decode()] = value.value
+        index += 1
     _lib = lib
     # A/B knobs for measurements: MVG_TUNE="chain_rm=128,gsamp_threads=256"
     for item in filter(None, os.environ.get("MVG_TUNE", "").split(",")):
         k, v = item.split("=")
         check(lib.mvg_set_tuning(k.strip().encode(), int(v)), "mvg_set_tuning(%s)" % item)
     return lib
+
+
+@contextlib.contextmanager
+def tuning(**knobs):
+    """Set the given knobs for the body of a `with`; on exit, also when the body raises, every one of them is back at the
+    value TUNING held on entry.  A rejected key or value raises MvgError and leaves every knob as it was."""
+    lib = load()
+    before = {k: TUNING[k] for k in knobs if k in TUNING}
+    try:
+        for k, v in knobs.items():
+            check(lib.mvg_set_tuning(k.encode(), int(v)), "mvg_set_tuning(%s=%s)" % (k, v))
+        yield
+    finally:
+        for k, v in before.items():
+            check(lib.mvg_set_tuning(k.encode(), v), "mvg_set_tuning(%s=%s)" % (k, v))
 
 
 def check(code, what):

@@ -22,45 +22,25 @@
 // "B" operand, the weight fragment the "A" operand, so a lane ends with 4 consecutive output
 // columns of one row and writes the next stage's input back to LDS with 8-byte stores.
 #include "common.h"
+#include "stamps.h"
+#include "tuning.h"
 #include <type_traits>
 
 // Probe build only (tools/probes/stamps_chain.py, -DCHAIN_STAMPS): every workgroup appends one record
 // [kernel id | blockIdx, start, end (s_memrealtime, 100 MHz), HW_ID | XCC_ID, up to 12 s_memtime phase stamps] (16 words) to a device buffer.
 #ifdef CHAIN_STAMPS
-__device__ unsigned long long chain_stamps[8192 * 16];
-__device__ unsigned int chain_stamp_count;
-#define CSTAMP_DECL unsigned long long cst_[16]; cst_[0] = 0
+MVG_STAMP_LOG(chain_stamps, 8192, 16, mvg_chain_read_stamps)
+#define CSTAMP_DECL stamp_t cst_[16]; cst_[0] = 0
 #define CSTAMP_REAL(i) cst_[i] = __builtin_amdgcn_s_memrealtime()
 #define CSTAMP(i) cst_[i] = __builtin_amdgcn_s_memtime()
 #define CSTAMP_FLUSH(kernel_id, flag)                                                                                     \
   do {                                                                                                                    \
     if (threadIdx.x == 0) {                                                                                               \
-      const unsigned slot = atomicAdd(&chain_stamp_count, 1u);                                                            \
-      if (slot < 8192) {                                                                                                  \
-        unsigned hw, xcc;                                                                                                 \
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));                                                  \
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));                                                \
-        cst_[0] = ((unsigned long long)(kernel_id) << 48) | ((unsigned long long)(flag) << 32) | blockIdx.x;              \
-        cst_[3] = ((unsigned long long)xcc << 32) | hw;                                                                   \
-        for (int i_ = 0; i_ < 16; ++i_) chain_stamps[slot * 16 + i_] = cst_[i_];                                          \
-      }                                                                                                                   \
+      cst_[0] = ((stamp_t)(kernel_id) << 48) | ((stamp_t)(flag) << 32) | blockIdx.x;                                      \
+      cst_[3] = stamp_hw_id();                                                                                            \
+      chain_stamps_append(cst_);                                                                                          \
     }                                                                                                                     \
   } while (0)
-extern "C" int mvg_chain_read_stamps(unsigned long long* host, int max_records, int reset) {
-  unsigned n = 0;
-  hipError_t e = hipMemcpyFromSymbol(&n, HIP_SYMBOL(chain_stamp_count), sizeof(n));
-  if (e != hipSuccess) return -(int)e;
-  if (n > 8192) n = 8192;
-  if ((int)n > max_records) n = max_records;
-  if (host && n) e = hipMemcpyFromSymbol(host, HIP_SYMBOL(chain_stamps), sizeof(unsigned long long) * 16 * n);
-  if (e != hipSuccess) return -(int)e;
-  if (reset) {
-    const unsigned z = 0;
-    e = hipMemcpyToSymbol(HIP_SYMBOL(chain_stamp_count), &z, sizeof(z));
-    if (e != hipSuccess) return -(int)e;
-  }
-  return (int)n;
-}
 #else
 #define CSTAMP_DECL
 #define CSTAMP_REAL(i)
@@ -547,17 +527,12 @@ __global__ __launch_bounds__(NT) void chain_b_kernel(
 
 }  // namespace
 
-extern int g_auto_small;   // tuning knob "auto_small" (msda.hip): launches with few rows pick smaller tiles (bit-identical rows)
-int g_chain_a_lds_pad = 0;   // probe knob "chain_a_lds_pad": unused dynamic LDS per chain-A workgroup (caps the workgroups per CU)
-int g_chain_rm = 128;  // tuning knob "chain_rm": rows per workgroup of chain A (64 | 128 | 256); 128: 65 -> 55 us (half the weight
-                       // bytes per row).  Geometries measured and deleted (rounds 1-4, Appendix A of DESIGN.md): 8 wavefronts for
-                       // chain A (93 vs 79 us), 4 wavefronts / row-block split / fragment rings of 8 and 16 for chain B.
 
 template <int RM, int NT, int JN>
 static int launch_chain_a(const void* samp, const uint8_t* inside, const void* Wp, const float* bp, const void* W0,
                           const float* b0, const void* W1, const float* b1, const float* W2, const float* b2, void* attn,
                           float* o, const int* order, const float* o_masked, int rows, hipStream_t st) {
-  const size_t lds = RM * ACT_PITCH + 2 * RM * sizeof(int) + 768 * sizeof(float) + (size_t)g_chain_a_lds_pad;
+  const size_t lds = RM * ACT_PITCH + 2 * RM * sizeof(int) + 768 * sizeof(float) + (size_t)g_tune.chain_a_lds_pad;
   // the attribute is per DEVICE: a process that drives several GPUs configures the > 64-KB LDS kernels on each of them
   static bool configured[MVG_MAX_DEVICES] = {};
   int dev = 0;
@@ -587,10 +562,10 @@ extern "C" int mvg_chain_attn_pose(const void* samp, const uint8_t* inside, cons
   // at most 320 tiles of 128 rows -- a rank's shard of a query-sharded run, small scenes -- 64-row tiles put twice as many
   // workgroups on the chip (measured at cfg-2 with 128 / 256 / 512 queries: -2.6 / -0.6 / -1.4 % of the forward; the full 1024
   // queries are 1.4 % faster with 128-row tiles).
-  if (g_auto_small && g_chain_rm == 128 && rows <= 320 * 128)
+  if (g_tune.auto_small && g_tune.chain_rm == 128 && rows <= 320 * 128)
     return launch_chain_a<64, 256, 2>(samp, inside, Wp, bp, W0, b0, W1, b1, W2, b2, attn, o, order, o_masked, rows, st);
-  if (g_chain_rm == 256) return launch_chain_a<256, 512, 1>(samp, inside, Wp, bp, W0, b0, W1, b1, W2, b2, attn, o, order, o_masked, rows, st);
-  if (g_chain_rm == 128) return launch_chain_a<128, 256, 2>(samp, inside, Wp, bp, W0, b0, W1, b1, W2, b2, attn, o, order, o_masked, rows, st);
+  if (g_tune.chain_rm == 256) return launch_chain_a<256, 512, 1>(samp, inside, Wp, bp, W0, b0, W1, b1, W2, b2, attn, o, order, o_masked, rows, st);
+  if (g_tune.chain_rm == 128) return launch_chain_a<128, 256, 2>(samp, inside, Wp, bp, W0, b0, W1, b1, W2, b2, attn, o, order, o_masked, rows, st);
   return launch_chain_a<64, 256, 2>(samp, inside, Wp, bp, W0, b0, W1, b1, W2, b2, attn, o, order, o_masked, rows, st);
 }
 
@@ -609,7 +584,7 @@ extern "C" int mvg_chain_update_ffn_class(const void* attn, int V, const float* 
   const int nq_total = B * NQ, rows = nq_total * J;
   if (rows == 0) return 0;
   // few rows (a rank's shard of a query-sharded run): 32-row tiles (2 persons) fill twice as many CUs
-  const bool small = g_auto_small && J <= 16 && (nq_total + (64 / J) - 1) / (64 / J) <= 128;
+  const bool small = g_tune.auto_small && J <= 16 && (nq_total + (64 / J) - 1) / (64 / J) <= 128;
   const int RMr = small ? 32 : 64;
   const int qpt = RMr / J;
   const size_t lds = 2 * RMr * ACT_PITCH + RMr * XP + RMr * 2 * sizeof(float) + 9 * 256 * sizeof(float);

@@ -29,6 +29,8 @@ __device__ __forceinline__ unsigned pack_bf16(float lo, float hi) {
 }
 __device__ __forceinline__ bf16_t f32_to_bf16(float f) { return (bf16_t)(pack_bf16(f, 0.f) & 0xffffu); }
 
+#define MVG_SW8(K, X) __builtin_amdgcn_ds_swizzle((X), 24 | ((K) << 5))      /* value of lane K of every group of 8 lanes */
+
 // ---- 4-channel vector load / store in either storage type (always fp32 in registers)
 template <typename T> struct Vec4;
 template <> struct Vec4<float> {

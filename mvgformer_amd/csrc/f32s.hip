@@ -19,6 +19,8 @@
 #include <type_traits>
 
 #include "common.h"
+#include "stamps.h"
+#include "tuning.h"
 
 #include "f32s_dev.h"
 
@@ -30,18 +32,15 @@
 
 // measurement builds (tools/probes/stamps_pyr_ws.py): s_memtime per wavefront at the phase boundaries of one steady-state tile
 #ifdef PYRWS_STAMPS
-__device__ unsigned long long pyrws_stamps[512 * 8 * 16];
+MVG_STAMP_GRID(pyrws_stamps, 512, 8, mvg_pyrws_read_stamps)
 #define PWSTAMP(i)                                                                                                        \
   do {                                                                                                                    \
     if (k == PYRWS_STAMPS && lane == 0) {                                                                                 \
       asm volatile("" ::: "memory");                                                                                      \
-      pyrws_stamps[(blockIdx.x * 8 + w) * 16 + (i)] = __builtin_amdgcn_s_memtime();                                       \
+      pyrws_stamps_at(w, (i)) = __builtin_amdgcn_s_memtime();                                                             \
       asm volatile("" ::: "memory");                                                                                      \
     }                                                                                                                     \
   } while (0)
-extern "C" int mvg_pyrws_read_stamps(unsigned long long* host, int n_blocks) {
-  return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(pyrws_stamps), sizeof(unsigned long long) * 128 * n_blocks);
-}
 #else
 #define PWSTAMP(i)
 #endif
@@ -806,7 +805,6 @@ int cu_count() {
 
 }  // namespace
 
-int g_f32h_rows = 0;      // tuning knob "f32h_rows": rows per tile of the two fp32 chains (0 = by the row count | 32 | 64); both sizes sum a row identically
 
 extern "C" int mvg_chain_update_ffn_class_f32h(const float* attn, int V, const float* tgt, const void* Wu, int wu_scale, const float* bu,
                                               const float* g2, const float* be2, const void* W1, int w1_scale, const float* b1,
@@ -826,7 +824,7 @@ extern "C" int mvg_chain_update_ffn_class_f32h(const float* attn, int V, const f
   // both tile sizes sum a row identically: 64-row tiles (one workgroup per CU, fragment ring 4) unless they would leave a quarter of
   // the CUs without a workgroup (then 32-row tiles, two workgroups per CU)
   const int tiles64 = (nq_total + 64 / J - 1) / (64 / J);
-  const bool big = J <= 32 && (g_f32h_rows == 64 || (g_f32h_rows == 0 && tiles64 > (cu_count() * 3) / 4));
+  const bool big = J <= 32 && (g_tune.f32h_rows == 64 || (g_tune.f32h_rows == 0 && tiles64 > (cu_count() * 3) / 4));
   static bool configured[MVG_MAX_DEVICES] = {}, configured2[MVG_MAX_DEVICES] = {};
 #define MVG_CBH(MTV, CFG)                                                                                                              \
   {                                                                                                                                    \
@@ -858,7 +856,7 @@ extern "C" int mvg_chain_attn_pose_f32h(const float* samp, const uint8_t* inside
     return MVG_E_BADARG;
   static bool configured[MVG_MAX_DEVICES] = {}, configured2[MVG_MAX_DEVICES] = {};
   // both tile sizes sum a row identically: 64-row tiles (half the fragment loads per row) once they fill the CUs
-  if (g_f32h_rows == 64 || (g_f32h_rows == 0 && (rows + 63) / 64 >= cu_count())) {
+  if (g_tune.f32h_rows == 64 || (g_tune.f32h_rows == 0 && (rows + 63) / 64 >= cu_count())) {
     const size_t lds = 2 * 64 * PLP + 3 * 64 * sizeof(int) + 64 * 8 * sizeof(float) + 2 * 768 * sizeof(float);
     if (int rc = configure_lds(&chain_a_f32h_small_kernel<2>, lds, configured2)) return rc;
     hipLaunchKernelGGL(chain_a_f32h_small_kernel<2>, dim3((rows + 63) / 64), dim3(NT), lds, (hipStream_t)stream, samp, inside, (const bf16_t*)Wp,

@@ -28,10 +28,9 @@
 // a NaN and turned a diverged row back into a finite one.  The row mask is a select, not a product: a masked row is +0 in every
 // column whatever its inputs hold, NaN included (the consumers mask rows whose inputs are not meaningful).
 #include "common.h"
+#include "tuning.h"
 
-int g_linear_tiles = 1;     // tuning knob "linear_tiles": 0 = always 128 x 128 tiles (rounds 1-2)
 static const int g_linear_xcd = 1;   // the column tiles of one row tile run on the same XCD (shared L2); 0 measured slower (round 3)
-int g_f32_split = 1;        // tuning knob "f32_split": 1 = fp32 GEMMs as six bf16 MFMAs on 3-way split operands (see above)
 
 namespace {
 
@@ -634,7 +633,7 @@ int launch_linear_tile(const void* A, const void* A2, long lda, const void* W, c
                        const uint8_t* rowmask, int relu, int M, int N, int K, hipStream_t st) {
   dim3 grid((N + BN - 1) / BN, (M + BM - 1) / BM);
   if constexpr (!BF16 && sizeof(TA) == 4) {
-    if (g_f32_split) {
+    if (g_tune.f32_split) {
       hipLaunchKernelGGL((linear_kernel<TA, false, TO, BM, BN, false, true>), grid, dim3(256), 0, st, (const TA*)A, (const TA*)A2,
                          lda, W, bias, (TO*)out, ldc, rowmask, relu, M, N, K, nullptr, nullptr, nullptr, g_linear_xcd);
       MVG_LAUNCH_CHECK();
@@ -653,7 +652,7 @@ int launch_linear_idx(const float* A, long lda, const float* W, const float* bia
                       int relu, int M, int N, int K, const int* order, const uint8_t* inside, const float* masked_row,
                       hipStream_t st) {
   dim3 grid((N + 127) / 128, (M + BM - 1) / BM);
-  if (g_f32_split) {
+  if (g_tune.f32_split) {
     hipLaunchKernelGGL((linear_kernel<float, false, float, BM, 128, true, true>), grid, dim3(256), 0, st, A, (const float*)nullptr,
                        lda, (const void*)W, bias, out, ldc, rowmask, relu, M, N, K, order, inside, masked_row, g_linear_xcd);
     MVG_LAUNCH_CHECK();
@@ -668,11 +667,11 @@ int launch_linear_idx(const float* A, long lda, const float* W, const float* bia
 template <typename TA, bool BF16, typename TO>
 int launch_linear(const void* A, const void* A2, long lda, const void* W, const float* bias, void* out, long ldc,
                   const uint8_t* rowmask, int relu, int M, int N, int K, hipStream_t st) {
-  if (g_linear_tiles) {
+  if (g_tune.linear_tiles) {
     if (N % 192 == 0 && N % 128 != 0)        // N = 192, 576, ...: no padded column tile
       return launch_linear_tile<TA, BF16, TO, 128, 192>(A, A2, lda, W, bias, out, ldc, rowmask, relu, M, N, K, st);
     const long tiles128 = (long)((N + 127) / 128) * ((M + 127) / 128);
-    if ((tiles128 < 384 && M > 64) || g_linear_tiles == 2)   // fewer than 1.5 workgroups per CU of an MI355X: halve the row tile
+    if ((tiles128 < 384 && M > 64) || g_tune.linear_tiles == 2)   // fewer than 1.5 workgroups per CU of an MI355X: halve the row tile
       return launch_linear_tile<TA, BF16, TO, 64, 128>(A, A2, lda, W, bias, out, ldc, rowmask, relu, M, N, K, st);
   }
   return launch_linear_tile<TA, BF16, TO, 128, 128>(A, A2, lda, W, bias, out, ldc, rowmask, relu, M, N, K, st);
@@ -695,7 +694,7 @@ extern "C" int mvg_linear_ordered(const float* A, int lda, const float* W, const
     return MVG_E_BADARG;
   hipStream_t st = (hipStream_t)stream;
   const long tiles128 = (long)((N + 127) / 128) * ((M + 127) / 128);
-  if (g_linear_tiles && tiles128 < 384 && M > 64)
+  if (g_tune.linear_tiles && tiles128 < 384 && M > 64)
     return launch_linear_idx<64>(A, lda, W, bias, out, ldc, rowmask, relu, M, N, K, order, inside, masked_row, st);
   return launch_linear_idx<128>(A, lda, W, bias, out, ldc, rowmask, relu, M, N, K, order, inside, masked_row, st);
 }

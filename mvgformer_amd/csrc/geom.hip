@@ -3,6 +3,8 @@
 // residual+LayerNorm, class head, last pose-MLP layer, and the fused
 // refine-2D -> undistort -> DLT -> smallest-singular-vector -> scatter kernel.
 #include "common.h"
+#include "stamps.h"
+#include "tuning.h"
 
 // ------------------------------------------------------------------------------------------
 // NCHW level -> channels-last pyramid rows.  64 (pixels) x 64 (channels) tile transposed through LDS (65-float
@@ -585,40 +587,18 @@ __device__ __forceinline__ void jacobi_round_lanes(double (&col)[4], const int j
 // Probe build only (-DTRI_STAMPS, tools/probes/stamps_tri.py): thread 0 of every workgroup appends [blockIdx, start, end (s_memrealtime),
 // HW_ID | XCC_ID << 32, s_memtime at: start, phase 1 done, barrier passed, Jacobi + divide done, next projection done].
 #ifdef TRI_STAMPS
-__device__ unsigned long long tri_stamps[4096 * 12];
-__device__ unsigned int tri_stamp_count;
-#define TSTAMP_DECL unsigned long long tst_[12]; tst_[0] = 0
+MVG_STAMP_LOG(tri_stamps, 4096, 12, mvg_tri_read_stamps)
+#define TSTAMP_DECL stamp_t tst_[12]; tst_[0] = 0
 #define TSTAMP_REAL(i) tst_[i] = __builtin_amdgcn_s_memrealtime()
 #define TSTAMP(i) tst_[i] = __builtin_amdgcn_s_memtime()
 #define TSTAMP_FLUSH()                                                                                                    \
   do {                                                                                                                    \
     if (threadIdx.x == 0) {                                                                                               \
-      const unsigned slot_ = atomicAdd(&tri_stamp_count, 1u);                                                             \
-      if (slot_ < 4096) {                                                                                                 \
-        unsigned hw_, xcc_;                                                                                               \
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw_));                                                 \
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc_));                                               \
-        tst_[0] = blockIdx.x;                                                                                             \
-        tst_[3] = ((unsigned long long)xcc_ << 32) | hw_;                                                                 \
-        for (int i_ = 0; i_ < 12; ++i_) tri_stamps[slot_ * 12 + i_] = tst_[i_];                                           \
-      }                                                                                                                   \
+      tst_[0] = blockIdx.x;                                                                                               \
+      tst_[3] = stamp_hw_id();                                                                                            \
+      tri_stamps_append(tst_);                                                                                            \
     }                                                                                                                     \
   } while (0)
-extern "C" int mvg_tri_read_stamps(unsigned long long* host, int max_records, int reset) {
-  unsigned n = 0;
-  hipError_t e = hipMemcpyFromSymbol(&n, HIP_SYMBOL(tri_stamp_count), sizeof(n));
-  if (e != hipSuccess) return -(int)e;
-  if (n > 4096) n = 4096;
-  if ((int)n > max_records) n = max_records;
-  if (host && n) e = hipMemcpyFromSymbol(host, HIP_SYMBOL(tri_stamps), sizeof(unsigned long long) * 12 * n);
-  if (e != hipSuccess) return -(int)e;
-  if (reset) {
-    const unsigned z = 0;
-    e = hipMemcpyToSymbol(HIP_SYMBOL(tri_stamp_count), &z, sizeof(z));
-    if (e != hipSuccess) return -(int)e;
-  }
-  return (int)n;
-}
 #else
 #define TSTAMP_DECL
 #define TSTAMP_REAL(i)
@@ -1004,7 +984,6 @@ __global__ __launch_bounds__(1024) void bin_pairs_kernel(const float* __restrict
 //   bin_scatter_kernel: every part re-derives the global offsets from all parts' counters (key-major, then part:
 //                       offset(k, p) = sum_{k' < k} total(k') + sum_{p' < p} count(p', k)) and scatters its slice.
 // No workgroup waits for another one: the dependency is the kernel boundary.
-int g_bin_multi = 1;                            // tuning knob "bin_multi": 0 = always the single-workgroup binning kernel
 constexpr int BIN_PARTS = 8;                    // 4 / 16 parts per image measured: +0.7 / +2.8 % per forward
 constexpr int BIN_MULTI_MIN = 8192;             // pairs per image from which the multi-workgroup variant is used
 constexpr int BIN_CNT_STRIDE = BIN_KEYS + 4;        // counters per (image, part), padded to 16 bytes
@@ -1497,7 +1476,7 @@ int mvg_bin_pairs(const float* ref_lvl, const uint8_t* inside, const int64_t* sh
   while (((W0 - 1) >> shift) >= (1 << BIN_BITS) || ((H0 - 1) >> shift) >= (1 << BIN_BITS)) ++shift;
   if (Lq > 64 * 1024) return MVG_E_BADARG;        // more than 65 536 tokens per image: run the sampler unordered
   hipStream_t st = (hipStream_t)stream;
-  if (g_bin_multi && Lq >= BIN_MULTI_MIN && workspace && workspace_bytes >= mvg_bin_pairs_workspace(N_img, Lq)) {
+  if (g_tune.bin_multi && Lq >= BIN_MULTI_MIN && workspace && workspace_bytes >= mvg_bin_pairs_workspace(N_img, Lq)) {
     // many pairs per image: BIN_PARTS workgroups per image, two kernels (see bin_count_kernel)
     unsigned* cnt = reinterpret_cast<unsigned*>(workspace);
     unsigned short* keys = reinterpret_cast<unsigned short*>(cnt + (size_t)N_img * BIN_PARTS * BIN_CNT_STRIDE);

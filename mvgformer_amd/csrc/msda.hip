@@ -15,10 +15,10 @@
 //     15 joints of a person, neighbouring persons of the query grid) share one XCD's L2.
 // msda_fwd_kernel = the drop-in for Deformable.deform_forward; msda_fused_kernel = generic fused form
 // (fp32 / bf16, pixel-major value); msda_gsamp_kernel = the benchmarked bf16 kernel (see its header).
-#include <string.h>
-
 #include "common.h"
 #include "gsamp_dev.h"
+#include "stamps.h"
+#include "tuning.h"
 
 
 // ------------------------------------------------------------------------------------------
@@ -200,7 +200,6 @@ __global__ __launch_bounds__(256) void msda_fwd_hp8_kernel(
   const long n_blocks = (long)N * n_qblocks * M;
   const int sub = threadIdx.x & 7, qs = threadIdx.x >> 3;
   const int LP = L * P;
-#define MVG_SW8(K, X) __builtin_amdgcn_ds_swizzle((X), 24 | ((K) << 5))      /* value of lane K of every group of 8 lanes */
   for (long blk = blockIdx.x; blk < n_blocks; blk += gridDim.x) {
     const int m = (int)(blk % M);
     const long t = blk / M;
@@ -276,7 +275,6 @@ __global__ __launch_bounds__(256) void msda_fwd_hp8_kernel(
     }
     Vec4<T>::store(out + qm * D + sub * 4, acc4);
   }
-#undef MVG_SW8
 }
 
 // fp64 drop-in (the `double` case of AT_DISPATCH_FLOATING_TYPES, deform_cuda.cu:75: gradcheck-style calls): one thread
@@ -379,7 +377,6 @@ __global__ __launch_bounds__(256) void msda_bwd_f64_kernel(
   }
 }
 
-static int g_fwd_map = 1;          // tuning knob "fwd_map": mvg_msda_forward, 0 = a wavefront takes the M heads of a query, 1 = one head per workgroup (D = 32: per-sample arithmetic shared out over the unit's 8 lanes), 2 = one head per workgroup, every lane computes every sample
 template <typename T>
 static int launch_msda_fwd(const T* value, const int64_t* shapes, const int64_t* starts, const float* loc,
                            const float* wgt, T* out, int N, int S, int M, int D, int L, int Lq, int P,
@@ -391,11 +388,11 @@ static int launch_msda_fwd(const T* value, const int64_t* shapes, const int64_t*
   const int block = 256;
   long grid = (total + block - 1) / block;
   if (grid > (1L << 22)) grid = 1L << 22;
-  if (vec && g_fwd_map >= 1 && 256 % (D / 4) == 0) {
+  if (vec && g_tune.fwd_map >= 1 && 256 % (D / 4) == 0) {
     const int qpb = 256 / (D / 4), n_qblocks = (Lq + qpb - 1) / qpb;
     long blocks = (long)N * n_qblocks * M;
     if (blocks > (1L << 22)) blocks = (1L << 22) / M * M;        // grid-stride, a whole number of heads per stride
-    if (D == 32 && g_fwd_map == 1 && (long)S * M * D < (1L << 31))
+    if (D == 32 && g_tune.fwd_map == 1 && (long)S * M * D < (1L << 31))
       hipLaunchKernelGGL((msda_fwd_hp8_kernel<T>), dim3((unsigned)blocks), dim3(block), 0, st, value, shapes, starts, loc, wgt, out, N, S,
                          M, L, Lq, P, n_qblocks);
     else
@@ -626,20 +623,19 @@ __global__ __launch_bounds__(256, MVG_GFUSED_HP_OCC) void msda_gfused_f32_hp_ker
   // Round 6: lane 0 of the group reads the slot's pair and its mask byte, lanes 0..L-1 the reference point of level `lane`; the
   // others get them through the swizzle crossbar.  The texture-address path takes a clock per 4 ACTIVE lanes of a load and this
   // kernel runs at its rate (profiles/r06_experiments.txt sections 2, 5): 8 + 8 + 8 L lane addresses per wavefront for 5 x 64.
-#define MVG_GRP8(K, X) __builtin_amdgcn_ds_swizzle((X), 24 | ((K) << 5))      /* value of lane K of every group of 8 lanes */
   static_assert(L <= 8, "lane `sub` of a group carries the reference point of level `sub`");
   int pair = slot;
   if (order) {
     int p0 = 0;
     if (sub == 0) p0 = order[slot];
-    pair = MVG_GRP8(0, p0);
+    pair = MVG_SW8(0, p0);
   }
   float2 mine = float2{0.f, 0.f};
   if (sub < L) mine = *reinterpret_cast<const float2*>(r + ((long)pair * L + sub) * 2);
   if (pair_mask) {
     int mk = 0;
     if (sub == 0) mk = pair_mask[pair];
-    if (!MVG_GRP8(0, mk)) {
+    if (!MVG_SW8(0, mk)) {
       *reinterpret_cast<f32x4*>(samp + (long)pair * C + m * D + sub * CPL) = f32x4{0.f, 0.f, 0.f, 0.f};
       return;
     }
@@ -658,17 +654,16 @@ __global__ __launch_bounds__(256, MVG_GFUSED_HP_OCC) void msda_gfused_f32_hp_ker
   for (int l = 0; l < L; ++l) {
     const int mx_ = __float_as_int(mine.x), my_ = __float_as_int(mine.y);
     switch (l) {          // (the swizzle pattern is an immediate)
-      case 0: rr[l] = float2{__int_as_float(MVG_GRP8(0, mx_)), __int_as_float(MVG_GRP8(0, my_))}; break;
-      case 1: rr[l] = float2{__int_as_float(MVG_GRP8(1, mx_)), __int_as_float(MVG_GRP8(1, my_))}; break;
-      case 2: rr[l] = float2{__int_as_float(MVG_GRP8(2, mx_)), __int_as_float(MVG_GRP8(2, my_))}; break;
-      case 3: rr[l] = float2{__int_as_float(MVG_GRP8(3, mx_)), __int_as_float(MVG_GRP8(3, my_))}; break;
-      case 4: rr[l] = float2{__int_as_float(MVG_GRP8(4, mx_)), __int_as_float(MVG_GRP8(4, my_))}; break;
-      case 5: rr[l] = float2{__int_as_float(MVG_GRP8(5, mx_)), __int_as_float(MVG_GRP8(5, my_))}; break;
-      case 6: rr[l] = float2{__int_as_float(MVG_GRP8(6, mx_)), __int_as_float(MVG_GRP8(6, my_))}; break;
-      default: rr[l] = float2{__int_as_float(MVG_GRP8(7, mx_)), __int_as_float(MVG_GRP8(7, my_))}; break;
+      case 0: rr[l] = float2{__int_as_float(MVG_SW8(0, mx_)), __int_as_float(MVG_SW8(0, my_))}; break;
+      case 1: rr[l] = float2{__int_as_float(MVG_SW8(1, mx_)), __int_as_float(MVG_SW8(1, my_))}; break;
+      case 2: rr[l] = float2{__int_as_float(MVG_SW8(2, mx_)), __int_as_float(MVG_SW8(2, my_))}; break;
+      case 3: rr[l] = float2{__int_as_float(MVG_SW8(3, mx_)), __int_as_float(MVG_SW8(3, my_))}; break;
+      case 4: rr[l] = float2{__int_as_float(MVG_SW8(4, mx_)), __int_as_float(MVG_SW8(4, my_))}; break;
+      case 5: rr[l] = float2{__int_as_float(MVG_SW8(5, mx_)), __int_as_float(MVG_SW8(5, my_))}; break;
+      case 6: rr[l] = float2{__int_as_float(MVG_SW8(6, mx_)), __int_as_float(MVG_SW8(6, my_))}; break;
+      default: rr[l] = float2{__int_as_float(MVG_SW8(7, mx_)), __int_as_float(MVG_SW8(7, my_))}; break;
     }
   }
-#undef MVG_GRP8
   f32x4 ga[NK], gb[NK], gc[NK], gd[NK], gx4[NK];
   float w00[NK], w10[NK], w01[NK], w11[NK];
 #pragma unroll
@@ -754,7 +749,6 @@ __global__ __launch_bounds__(256, MVG_GFUSED_HP_OCC) void msda_gfused_f32_hp_ker
   // weights + 3 element offsets per sample; two half batches of 4 samples = 16 gathers in flight as before.  Same operations in
   // the same order for every sample and every accumulation: bit-identical to the first form.
   static_assert(P == 8 && NB == 4, "one sample per lane of the head's 8");
-#define MVG_SW8(K, X) __builtin_amdgcn_ds_swizzle((X), 24 | ((K) << 5))      /* value of lane K of every group of 8 lanes */
 #pragma unroll 1
   for (int l = 0; l < L; ++l) {
     const int H = lv.H[l], W = lv.W[l];
@@ -820,7 +814,6 @@ __global__ __launch_bounds__(256, MVG_GFUSED_HP_OCC) void msda_gfused_f32_hp_ker
         for (int k = 0; k < 4; ++k) RV::fma(acc, raw[s_][k], cw[s_][k]);
     }
   }
-#undef MVG_SW8
   if (live) store_acc<float, CPL>(samp + (long)pair * C + m * D + sub * CPL, acc);
 }
 
@@ -855,23 +848,7 @@ __global__ __launch_bounds__(256, MVG_GFUSED_HP_OCC) void msda_gfused_f32_hp_ker
 // Probe build only (-DGSAMP_STAMPS, tools/probes/stamps_gsamp.py): wavefront 0 of every workgroup appends [blockIdx, start, end
 // (s_memrealtime), HW_ID | XCC_ID << 32, lanes that sampled] to a device buffer.
 #ifdef GSAMP_STAMPS
-__device__ unsigned long long gsamp_stamps[65536 * 4];
-__device__ unsigned int gsamp_stamp_count;
-extern "C" int mvg_gsamp_read_stamps(unsigned long long* host, int max_records, int reset) {
-  unsigned n = 0;
-  hipError_t e = hipMemcpyFromSymbol(&n, HIP_SYMBOL(gsamp_stamp_count), sizeof(n));
-  if (e != hipSuccess) return -(int)e;
-  if (n > 65536) n = 65536;
-  if ((int)n > max_records) n = max_records;
-  if (host && n) e = hipMemcpyFromSymbol(host, HIP_SYMBOL(gsamp_stamps), sizeof(unsigned long long) * 4 * n);
-  if (e != hipSuccess) return -(int)e;
-  if (reset) {
-    const unsigned z = 0;
-    e = hipMemcpyToSymbol(HIP_SYMBOL(gsamp_stamp_count), &z, sizeof(z));
-    if (e != hipSuccess) return -(int)e;
-  }
-  return (int)n;
-}
+MVG_STAMP_LOG(gsamp_stamps, 65536, 4, mvg_gsamp_read_stamps)
 #endif
 
 template <int L, int NT, int PIPE = 0>   // NT threads per workgroup = NT/4 consecutive slots of the processing order, one head
@@ -910,16 +887,8 @@ __device__ __forceinline__ void msda_gsamp_body(const bf16_t* __restrict__ vp, c
     // (lane 0 may have left: the first lane still here writes)
     const int first = __ffsll((unsigned long long)__ballot(true)) - 1;
     if (wave == 0 && lane == first) {
-      const unsigned s_ = atomicAdd(&gsamp_stamp_count, 1u);
-      if (s_ < 65536) {
-        unsigned hw, xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        gsamp_stamps[s_ * 4] = blockIdx.x | ((unsigned long long)__popcll(act) << 32);
-        gsamp_stamps[s_ * 4 + 1] = gs_t0;
-        gsamp_stamps[s_ * 4 + 2] = __builtin_amdgcn_s_memrealtime();
-        gsamp_stamps[s_ * 4 + 3] = ((unsigned long long)xcc << 32) | hw;
-      }
+      const stamp_t rec[4] = {blockIdx.x | ((stamp_t)__popcll(act) << 32), gs_t0, __builtin_amdgcn_s_memrealtime(), stamp_hw_id()};
+      gsamp_stamps_append(rec);
     }
   };
 #endif
@@ -974,13 +943,6 @@ __global__ __launch_bounds__(NT) void msda_gsamp_pipe_kernel(const bf16_t* __res
   msda_gsamp_body<L, NT, 1>(vp, G, xw, r, lv, samp, pair_mask, order, n_pairs, Lq, S, B, map_ch);
 }
 
-static int g_gsamp_pipe = 0;       // tuning knob "gsamp_pipe": gathers double-buffered in half batches (93 VGPRs) -- 0 = from 32 768 pairs per launch on, 1 = always, 2 = never
-int g_auto_small = 1;              // tuning knob "auto_small": small launches pick their own workgroup / tile sizes (see mvg_msda_gsamp)
-static int g_gsamp_map = 4;        // tuning knob "gsamp_map": 0 = head per XCD (159 us), n > 0 = chunks of n slot blocks per
-                                   // XCD with their 8 heads back to back (1..4: 155 us, 8: 159, 16: 168, 64: 243)
-static int g_gfused_chunk = 4;     // tuning knob "gfused_chunk": hp kernel, 0 = one head per XCD (270 us at cfg-2), n > 0 = chunks of n pair blocks per XCD with their 8 heads back to back (1..4: 252 us, 16: 263)
-static int g_gsamp_lds_pad = 0;    // probe knob "gsamp_lds_pad": bytes of unused dynamic LDS per workgroup (caps the workgroups per CU)
-static int g_gsamp_threads = 256;  // tuning knob "gsamp_threads": workgroup size of msda_gsamp_kernel (256 | 512 | 1024)
 
 template <typename T, int CPL, int NB>
 static int launch_msda_fused_cpl(const T* value, const float* oa, const float* r, const LevelTable& lv, T* samp,
@@ -1212,9 +1174,9 @@ int mvg_msda_gsamp(const void* vp, const void* G, const float* xw, const float* 
   // Infinity-Cache hits) the half batches pay at full size -- cfg-2 -0.8 %, all pairs inside -1.6 %, cfg-5 -1.4 % per forward -- and cost
   // a rank's shard +1 % (128 queries); 2 samples per forward +-0.4 % (profiles/r05_experiments.txt section 13; before that schedule:
   // -1.1 % at 31 views, +1 % at 5-10 images)
-  const bool pipe = g_gsamp_pipe == 1 || (g_gsamp_pipe == 0 && (long)N_img * Lq >= 32768);
-  int nthreads = g_gsamp_threads, map = g_gsamp_map;
-  if (g_auto_small && Lq <= 8192) {
+  const bool pipe = g_tune.gsamp_pipe == 1 || (g_tune.gsamp_pipe == 0 && (long)N_img * Lq >= 32768);
+  int nthreads = g_tune.gsamp_threads, map = g_tune.gsamp_map;
+  if (g_tune.auto_small && Lq <= 8192) {
     nthreads = 128;
     map = 1;
   }
@@ -1223,11 +1185,11 @@ int mvg_msda_gsamp(const void* vp, const void* G, const float* xw, const float* 
     int npb = (int)((pairs + NT / 4 - 1) / (NT / 4));                                                             \
     if (map > 0) npb = (npb + 8 * map - 1) / (8 * map) * (8 * map);                                               \
     if (pipe)                                                                                                 \
-      hipLaunchKernelGGL((msda_gsamp_pipe_kernel<LL, NT>), dim3(8 * npb), dim3(NT), g_gsamp_lds_pad, st, (const bf16_t*)vp,     \
+      hipLaunchKernelGGL((msda_gsamp_pipe_kernel<LL, NT>), dim3(8 * npb), dim3(NT), g_tune.gsamp_lds_pad, st, (const bf16_t*)vp,     \
                          (const bf16_t*)G, xw, ref_lvl, lv, (bf16_t*)samp, pair_mask, order, (int)pairs, Lq, S,   \
                          B, map);                                                                                 \
     else                                                                                                          \
-      hipLaunchKernelGGL((msda_gsamp_kernel<LL, NT>), dim3(8 * npb), dim3(NT), g_gsamp_lds_pad, st, (const bf16_t*)vp,          \
+      hipLaunchKernelGGL((msda_gsamp_kernel<LL, NT>), dim3(8 * npb), dim3(NT), g_tune.gsamp_lds_pad, st, (const bf16_t*)vp,          \
                          (const bf16_t*)G, xw, ref_lvl, lv, (bf16_t*)samp, pair_mask, order, (int)pairs, Lq, S,   \
                          B, map);                                                                                 \
   }
@@ -1247,33 +1209,6 @@ int mvg_msda_gsamp(const void* vp, const void* G, const float* xw, const float* 
   return 0;
 }
 
-extern int g_chain_rm;
-extern int g_chain_a_lds_pad;
-extern int g_linear_tiles;
-extern int g_f32_split;
-extern int g_wreg_grid;
-extern int g_f32h_rows;
-extern int g_bin_multi;
-
-int mvg_set_tuning(const char* key, int value) {
-  if (!key) return MVG_E_BADARG;
-  if (!strcmp(key, "linear_tiles") && value >= 0 && value <= 2) { g_linear_tiles = value; return 0; }
-  if (!strcmp(key, "f32_split") && (value == 0 || value == 1)) { g_f32_split = value; return 0; }
-  if (!strcmp(key, "f32h_rows") && (value == 0 || value == 32 || value == 64)) { g_f32h_rows = value; return 0; }
-  if (!strcmp(key, "chain_rm") && (value == 64 || value == 128 || value == 256)) { g_chain_rm = value; return 0; }
-  if (!strcmp(key, "wreg_grid") && value > 0) { g_wreg_grid = value; return 0; }
-  if (!strcmp(key, "bin_multi") && (value == 0 || value == 1)) { g_bin_multi = value; return 0; }
-  if (!strcmp(key, "auto_small") && (value == 0 || value == 1)) { g_auto_small = value; return 0; }
-  if (!strcmp(key, "gsamp_map") && value >= 0 && value <= 4096) { g_gsamp_map = value; return 0; }
-  if (!strcmp(key, "fwd_map") && (value >= 0 && value <= 2)) { g_fwd_map = value; return 0; }
-  if (!strcmp(key, "gfused_chunk") && value >= 0 && value <= 4096) { g_gfused_chunk = value; return 0; }
-  if (!strcmp(key, "gsamp_pipe") && value >= 0 && value <= 2) { g_gsamp_pipe = value; return 0; }
-  if (!strcmp(key, "chain_a_lds_pad") && value >= 0 && value <= 120 * 1024) { g_chain_a_lds_pad = value; return 0; }
-  if (!strcmp(key, "gsamp_lds_pad") && value >= 0 && value <= 120 * 1024) { g_gsamp_lds_pad = value; return 0; }
-  if (!strcmp(key, "gsamp_threads") && (value == 128 || value == 256 || value == 512 || value == 1024)) { g_gsamp_threads = value; return 0; }
-  return MVG_E_BADARG;
-}
-
 int mvg_msda_gfused_f32(const float* value, const float* G, const float* xw, const float* ref_lvl, const int64_t* shapes_host,
                         const int64_t* starts_host, float* samp, const uint8_t* pair_mask, const int32_t* order, int N_img,
                         int Lq, int L, int S, int B, void* stream) {
@@ -1287,7 +1222,7 @@ int mvg_msda_gfused_f32(const float* value, const float* G, const float* xw, con
   hipStream_t st = (hipStream_t)stream;
   {
     int npb = (int)((pairs + 31) / 32);
-    const int mc = g_gfused_chunk;
+    const int mc = g_tune.gfused_chunk;
     if (mc > 0) npb = (npb + 8 * mc - 1) / (8 * mc) * (8 * mc);
     const int grid_hp = 8 * npb;
     switch (L) {

@@ -17,18 +17,19 @@
 // one line per corner pair and perm-free dot2 operands, but twice the bytes -- with the pairs processed in
 // image-space order the smaller footprint wins: sampler 153 -> 145 us, this GEMM 59 -> 40 us.)
 #include "common.h"
+#include "stamps.h"
+#include "tuning.h"
 #include <type_traits>
 
-int g_wreg_grid = 512;   // tuning knob (mvg_set_tuning "wreg_grid"): persistent workgroups
 
 // measurement builds (tools/probes/stamps_wreg.py): s_memtime per wavefront at the phase boundaries of one steady-state tile
 #ifdef WREG_STAMPS
-__device__ unsigned long long wreg_stamps[1024 * 4 * 16];
+MVG_STAMP_GRID(wreg_stamps, 1024, 4, mvg_wreg_read_stamps)
 #define W2STAMP_ALWAYS(i, val)                                                                                            \
   do {                                                                                                                    \
     if (lane == 0 && blockIdx.x < 1024) {                                                                                 \
       asm volatile("" ::: "memory");                                                                                      \
-      wreg_stamps[(blockIdx.x * 4 + wn) * 16 + (i)] = (val);                                                              \
+      wreg_stamps_at(wn, (i)) = (val);                                                                                    \
       asm volatile("" ::: "memory");                                                                                      \
     }                                                                                                                     \
   } while (0)
@@ -36,13 +37,10 @@ __device__ unsigned long long wreg_stamps[1024 * 4 * 16];
   do {                                                                                                                    \
     if (it == WREG_STAMPS && lane == 0 && blockIdx.x < 1024) {                                                            \
       asm volatile("" ::: "memory");                                                                                      \
-      wreg_stamps[(blockIdx.x * 4 + wn) * 16 + (i)] = __builtin_amdgcn_s_memtime();                                       \
+      wreg_stamps_at(wn, (i)) = __builtin_amdgcn_s_memtime();                                                             \
       asm volatile("" ::: "memory");                                                                                      \
     }                                                                                                                     \
   } while (0)
-extern "C" int mvg_wreg_read_stamps(unsigned long long* host, int n_blocks) {
-  return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(wreg_stamps), sizeof(unsigned long long) * 64 * n_blocks);
-}
 #else
 #define W2STAMP(i)
 #define W2STAMP_ALWAYS(i, val)
@@ -379,7 +377,7 @@ extern "C" int mvg_pyramid_group_ws(const void* feat, int n_img, int S, int njob
   }
   // slots per XCD in proportion to the jobs' work; never more than the 64 resident workgroups of an XCD
   const int ntiles = (gp.M + RM - 1) / RM;
-  int budget = slots_per_xcd > 0 ? slots_per_xcd : g_wreg_grid / 8;
+  int budget = slots_per_xcd > 0 ? slots_per_xcd : g_tune.wreg_grid / 8;
   if (budget > WREG_MAX_SLOTS) budget = WREG_MAX_SLOTS;
   if (budget > (ntiles + 7) / 8 * njobs) budget = (ntiles + 7) / 8 * njobs;
   if (budget < njobs) budget = njobs;

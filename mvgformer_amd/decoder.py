@@ -364,7 +364,8 @@ class DQDecoderLayer(MvPDecoderLayer):
             return torch.stack(rows)
         # keyed on the active GEMM form as well: the rows must come from the form that computes the unmasked tiles
         from . import _lib
-        return self._w("pose_masked_rows/f32_split=%d" % _lib.TUNING.get("f32_split", 1), params, f32, build)
+        _lib.load()         # fills TUNING
+        return self._w("pose_masked_rows/f32_split=%d" % _lib.TUNING["f32_split"], params, f32, build)
 
     def _chain_b_operands(self, path, dt):
         """(Wu, bu, g2, b2, W1, b1, W2, bb2, g3, b3, Wc, bc): feature update, FFN (None without open_forward_ffn) and class head, the

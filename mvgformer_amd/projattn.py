@@ -33,8 +33,8 @@ def ops_host_levels_pair(spatial_shapes, level_start_index):
 def f32_split_on():
     """the library's f32_split knob selects the split fp32 GEMMs (default); 0 (bench.py --f32-gemm exact): reference arithmetic"""
     from . import _lib
-    _lib.load()         # applies MVG_TUNE: before that TUNING reads as the library's defaults
-    return _lib.TUNING.get("f32_split", 1) != 0
+    _lib.load()         # fills TUNING and applies MVG_TUNE
+    return _lib.TUNING["f32_split"] != 0
 
 
 def _is_power_of_2(n):

@@ -50,6 +50,7 @@ def test_parsed_signatures_equal_the_ones_written_out_here():
     pinned = {
         "mvg_device_info": [ctypes.c_char_p, i, P],
         "mvg_set_tuning": [ctypes.c_char_p, i],
+        "mvg_tuning_knob": [i, P, P],
         "mvg_class_head": [P, P, P, f, P, P, P, P, i, i, i, i, P],
         "mvg_pose_nms": [P, i, i, i, d, i, i, P, z, P, P, P, i, P],
         "mvg_pyramid_f32h": [P, P, i, P, P, i, P, P, ctypes.c_int64, i, P],

@@ -174,13 +174,10 @@ def test_pyramid_products_do_not_depend_on_the_split(n_img, S):
     for slots in (1, 2, 32, 64):
         for a, b in zip(base, _group(feat, n_img, S, jobs, slots)):
             assert torch.equal(_bits(a), _bits(b)), slots
-    try:
-        for grid in (64, 256, 512):
-            assert L.load().mvg_set_tuning(b"wreg_grid", grid) == 0
+    for grid in (64, 256, 512):
+        with L.tuning(wreg_grid=grid):
             for a, b in zip(base, _group(feat, n_img, S, jobs, 0)):
                 assert torch.equal(_bits(a), _bits(b)), grid
-    finally:
-        assert L.load().mvg_set_tuning(b"wreg_grid", 512) == 0
 
 
 @pytest.mark.parametrize("n_img,S", [(3, 277), (51, 5)])
@@ -307,14 +304,11 @@ def _linear(a, a2, w, b, mask, relu, o_dt, strided=False, tiles=1, expect=0, **r
     out = flat.view(max(M, 1), ldc)
     out[:, N:] = SENT
     off = lambda t, k: None if t is None else C.c_void_p(t.data_ptr() + raw.get(k, 0))
-    try:
-        assert L.load().mvg_set_tuning(b"linear_tiles", tiles) == 0
+    with L.tuning(linear_tiles=tiles):
         rc = L.load().mvg_linear_sum(off(a, "off_a"), L.ptr(a2), L.dtype_code(a.dtype), raw.get("lda", a.stride(0)), off(w, "off_w"),
                                      L.dtype_code(w.dtype), L.ptr(b), off(out, "off_out"), L.dtype_code(odt), raw.get("ldc", ldc), L.ptr(mask),
                                      1 if relu else 0, raw.get("M", M), raw.get("N", N), raw.get("K", K), L.stream_ptr())
         torch.cuda.synchronize()
-    finally:
-        assert L.load().mvg_set_tuning(b"linear_tiles", 1) == 0
     assert rc == expect, rc
     assert _guard_ok(buf, flat.numel())
     assert bool((out[:, N:] == _sent(odt)).all())

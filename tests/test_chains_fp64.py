@@ -95,11 +95,6 @@ def _bf_next(x, up):
     return n.to(torch.int16).view(torch.bfloat16).double()
 
 
-def _set_knobs(rm, small):
-    lib = _lib().load()
-    assert lib.mvg_set_tuning(b"chain_rm", rm) == 0 and lib.mvg_set_tuning(b"auto_small", small) == 0
-
-
 @pytest.mark.parametrize("rows", [1, 63, 64, 65, 127, 128, 129, 40960, 40961, 76800])
 @pytest.mark.parametrize("mask", ["mixed", "all_in", "all_masked"])
 def test_chain_a_against_fp64(rows, mask):
@@ -121,14 +116,11 @@ def test_chain_a_against_fp64(rows, mask):
     wl = [W[k] for k in ("Wp", "bp", "W0", "b0", "W1", "b1", "W2", "b2")]
     sw = [R_swz(W["Wp"]), W["bp"], R_swz(W["W0"]), W["b0"], R_swz(W["W1"]), W["b1"], W["W2"], W["b2"]]
     res = {}
-    try:
-        for rm, small in ((128, 1), (128, 0), (64, 1), (256, 1)):
-            _set_knobs(rm, small)
+    for rm, small in ((128, 1), (128, 0), (64, 1), (256, 1)):
+        with _lib().tuning(chain_rm=rm, auto_small=small):
             o_masked = ops.chain_masked_row_output(*sw)
             for ordered in (False, True):
                 res[(rm, small, ordered)] = _run_chain_a(samp, inside, W, order if ordered else None, o_masked if ordered else None)
-    finally:
-        _set_knobs(128, 1)
     keep = inside != 0
     for key, (attn, o) in res.items():
         ref = R.chain_a(samp, inside, *wl, bf16=True, attn=attn)

@@ -446,11 +446,7 @@ def test_weight_cache_refuses_to_build_inside_a_graph_capture(dt, knob, configur
         dec.overlap_pyramid = False     # the side-stream fork prepares the caches itself; here nothing does (and the graph has no parallel branches)
         configure(dec)
         return dec
-    lib = _lib.load()
-    before = _lib.TUNING.get("f32_split", 1)
-    try:
-        if knob is not None:
-            assert lib.mvg_set_tuning(b"f32_split", knob) == 0
+    with _lib.tuning(**({} if knob is None else {"f32_split": knob})):
         cold = build()
         graph = torch.cuda.CUDAGraph()
         with torch.no_grad():
@@ -468,8 +464,6 @@ def test_weight_cache_refuses_to_build_inside_a_graph_capture(dt, knob, configur
                 got = fwd(warm)
             graph.replay()
             torch.cuda.synchronize()
-    finally:
-        assert lib.mvg_set_tuning(b"f32_split", before) == 0
     for a, b in zip(got[:4] + (torch.stack(got[4]),), want[:4] + (torch.stack(want[4]),)):
         assert torch.equal(a, b)
 

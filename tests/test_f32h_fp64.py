@@ -48,10 +48,6 @@ def _check(name, got, ref, bound):
     assert bool((err <= bound).all()), (name, ratio)          # NaN (an element never written) fails too
 
 
-def _set_rows(v):
-    assert _lib().load().mvg_set_tuning(b"f32h_rows", v) == 0
-
-
 _PLANES = {}
 
 
@@ -151,14 +147,11 @@ def test_chain_a_against_fp64(ri, mask):
               "random": torch.randperm(rows, generator=gen).to(torch.int32).to(DEV)}
     om = _o_masked(W)
     res = {}
-    try:
-        for r in (0, 32, 64):
-            _set_rows(r)
+    for r in (0, 32, 64):
+        with _lib().tuning(f32h_rows=r):
             for oname, order in orders.items():
                 for given in (False, True):
                     res[(r, oname, given)] = _run_a(samp, inside, W, order, om if given else None)
-    finally:
-        _set_rows(0)
     base = res[(0, "none", False)]
     _check_a("rows %d %s" % (rows, mask), base[0], base[1], samp, inside, W, om)
     for key, (attn, o) in res.items():
@@ -200,9 +193,8 @@ def test_chain_a_non_finite_inputs_stay_in_their_rows():
     zero = samp.clone()
     zero[[5, 40]] = 0
     om = _o_masked(W)
-    try:
-        for r in (32, 64):
-            _set_rows(r)
+    for r in (32, 64):
+        with _lib().tuning(f32h_rows=r):
             a1, o1 = _run_a(bad, inside, W, None, om)
             a0, o0 = _run_a(zero, inside, W, None, om)
             for row in (5, 40):
@@ -212,8 +204,6 @@ def test_chain_a_non_finite_inputs_stay_in_their_rows():
             assert torch.equal(a1[others], a0[others]) and torch.equal(o1[others], o0[others]), r
             for row in (3, 50, 64):
                 assert bool((a1[row] == 0).all()) and torch.equal(o1[row], om), (r, row)
-    finally:
-        _set_rows(0)
 
 
 def test_chain_a_argument_checks():
@@ -294,12 +284,9 @@ def _run_check_b(name, c, W, has_ffn, any0=0, thr=None):
     c = _case_dev(c)
     ref = F.chain_b_ref(c, W, has_ffn, thr)
     outs = {}
-    try:
-        for r in (0, 32, 64):
-            _set_rows(r)
+    for r in (0, 32, 64):
+        with _lib().tuning(f32h_rows=r):
             outs[r] = _run_b(c, W, ref["thr"], has_ffn, any0)
-    finally:
-        _set_rows(0)
     _check_b(name, outs[0], ref, any0)
     assert _same(outs[32], outs[0]) and _same(outs[64], outs[0]), name
     return c, ref, outs[0]
@@ -353,9 +340,8 @@ def test_chain_b_non_finite_inputs_stay_in_their_rows():
     rows_ok[[ra, rt]] = False
     pers_ok = torch.ones(7, dtype=torch.bool, device=DEV)
     pers_ok[[1, 4]] = False
-    try:
-        for r in (32, 64):
-            _set_rows(r)
+    for r in (32, 64):
+        with _lib().tuning(f32h_rows=r):
             clean, got = _run_b(c, W, 0.0), _run_b(bad, W, 0.0)        # threshold 0: every clean person is valid
             assert bool(clean["valid"].all())
             for k in ("tgt", "xw"):
@@ -363,8 +349,6 @@ def test_chain_b_non_finite_inputs_stay_in_their_rows():
                 assert torch.equal(got[k][rows_ok], clean[k][rows_ok]), (r, k)
             assert bool(torch.isnan(got["prob"][[1, 4]]).all()) and got["valid"][[1, 4]].tolist() == [0, 0], r
             assert torch.equal(got["prob"][pers_ok], clean["prob"][pers_ok]) and torch.equal(got["valid"][pers_ok], clean["valid"][pers_ok])
-    finally:
-        _set_rows(0)
 
 
 def test_chain_b_person_permutation():

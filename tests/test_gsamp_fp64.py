@@ -21,9 +21,6 @@ GUARD = 1024
 SENT = -65536.0
 F32, BF16 = torch.float32, torch.bfloat16
 KERNELS = ("gsamp_bf16", "gfused_f32", "fused_f32", "fused_bf16")
-KNOB_DEFAULTS = dict(gsamp_pipe=0, auto_small=1, gsamp_threads=256, gsamp_map=4, gfused_chunk=4)
-
-
 def _lm():
     from mvgformer_amd import _lib as L
     return L
@@ -101,11 +98,6 @@ def _reference(kernel, name):
     return ref, k, GR.bar(ref, k, "gsamp_bf16" if mode == "bf16" else "f32"), None
 
 
-def _set(lib, **knobs):
-    for key, v in knobs.items():
-        assert lib.mvg_set_tuning(key.encode(), v) == 0, (key, v)
-
-
 # ------------------------------------------------------------------------------------------------------- against the fp64 statement
 @pytest.mark.parametrize("kernel", KERNELS)
 @pytest.mark.parametrize("name", list(GC.CASES))
@@ -151,20 +143,13 @@ def test_variants_are_bit_identical_on_the_edge_cases(name):
     """gsamp_pipe 1 / 2, auto_small 0, gsamp_threads 128 / 256 / 512 / 1024, gsamp_map 0 / 1 / 4 / 8 (msda_gsamp) and gfused_chunk
     0 / 1 / 4 / 16 (msda_gfused_f32): the rows of the default variant, bit for bit, on inputs that reach the edge branches."""
     c = GC.case(name)
-    lib = _lm().load()
-    try:
-        _set(lib, **KNOB_DEFAULTS)
-        base16, base32 = _bits(_run("gsamp_bf16", c)), _bits(_run("gfused_f32", c))
-        for knobs in GSAMP_VARIANTS:
-            _set(lib, **KNOB_DEFAULTS)
-            _set(lib, **knobs)
+    base16, base32 = _bits(_run("gsamp_bf16", c)), _bits(_run("gfused_f32", c))
+    for knobs in GSAMP_VARIANTS:
+        with _lm().tuning(**knobs):
             assert torch.equal(_bits(_run("gsamp_bf16", c)), base16), knobs
-        for knobs in GFUSED_VARIANTS:
-            _set(lib, **knobs)
+    for knobs in GFUSED_VARIANTS:
+        with _lm().tuning(**knobs):
             assert torch.equal(_bits(_run("gfused_f32", c)), base32), knobs
-    finally:
-        for key, v in KNOB_DEFAULTS.items():
-            lib.mvg_set_tuning(key.encode(), v)
 
 
 # ------------------------------------------------------------------------------------------------------------------ batch independence

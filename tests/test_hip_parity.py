@@ -229,9 +229,9 @@ def test_linear_mfma_fp32_and_bf16():
 
 
 def _f32_gemm(form):
-    """select the fp32 GEMM form of csrc/gemm.hip: "split" (default) or "exact" """
+    """with _f32_gemm(form): the body runs on that fp32 GEMM form of csrc/gemm.hip, "split" (default) or "exact" """
     from mvgformer_amd import _lib
-    assert _lib.load().mvg_set_tuning(b"f32_split", 1 if form == "split" else 0) == 0
+    return _lib.tuning(f32_split=1 if form == "split" else 0)
 
 
 @pytest.mark.parametrize("M,N,K", [(1000, 200, 256), (128, 256, 32), (4097, 192, 1024), (77, 8, 64), (20000, 256, 256)])
@@ -243,28 +243,25 @@ def test_linear_f32_split_form_is_as_close_to_fp64_as_the_exact_form(M, N, K):
     from mvgformer_amd import ops
     g = torch.Generator(device=DEV)
     g.manual_seed(M + N + K)
-    try:
-        for kind in ("normal", "positive", "wide"):
-            a = torch.randn(M, K, device=DEV, generator=g)
-            w = torch.randn(N, K, device=DEV, generator=g) / K ** 0.5
-            if kind == "wide":
-                a = a * torch.exp2(torch.randint(-20, 21, (M, K), device=DEV, generator=g).float())
-                w = w * torch.exp2(torch.randint(-20, 21, (N, K), device=DEV, generator=g).float())
-            elif kind == "positive":
-                a, w = a.abs(), w.abs()
-            b = torch.randn(N, device=DEV, generator=g)
-            ref = a.double() @ w.double().t() + b.double()
-            unit = a.double().abs() @ w.double().abs().t() + b.double().abs()
-            err = {}
-            for form in ("exact", "split"):
-                _f32_gemm(form)
+    for kind in ("normal", "positive", "wide"):
+        a = torch.randn(M, K, device=DEV, generator=g)
+        w = torch.randn(N, K, device=DEV, generator=g) / K ** 0.5
+        if kind == "wide":
+            a = a * torch.exp2(torch.randint(-20, 21, (M, K), device=DEV, generator=g).float())
+            w = w * torch.exp2(torch.randint(-20, 21, (N, K), device=DEV, generator=g).float())
+        elif kind == "positive":
+            a, w = a.abs(), w.abs()
+        b = torch.randn(N, device=DEV, generator=g)
+        ref = a.double() @ w.double().t() + b.double()
+        unit = a.double().abs() @ w.double().abs().t() + b.double().abs()
+        err = {}
+        for form in ("exact", "split"):
+            with _f32_gemm(form):
                 e = (ops.linear(a, w, b).double() - ref).abs() / unit
-                err[form] = (float(e.max()), float(e.mean()))
-            assert err["split"][0] <= 1.5 * err["exact"][0] + 2.0 ** -24, (kind, err)
-            assert err["split"][1] <= 1.25 * err["exact"][1] + 2.0 ** -28, (kind, err)
-            assert err["split"][0] < 2.0 ** -24 * (8 + K ** 0.5), (kind, err)        # a few units of fp32 rounding, growing like a random walk
-    finally:
-        _f32_gemm("split")
+            err[form] = (float(e.max()), float(e.mean()))
+        assert err["split"][0] <= 1.5 * err["exact"][0] + 2.0 ** -24, (kind, err)
+        assert err["split"][1] <= 1.25 * err["exact"][1] + 2.0 ** -28, (kind, err)
+        assert err["split"][0] < 2.0 ** -24 * (8 + K ** 0.5), (kind, err)        # a few units of fp32 rounding, growing like a random walk
 
 
 def test_linear_f32_random_shapes_both_forms():
@@ -274,33 +271,30 @@ def test_linear_f32_random_shapes_both_forms():
     rs = np.random.RandomState(2024)
     g = torch.Generator(device=DEV)
     g.manual_seed(7)
-    try:
-        for it in range(40):
-            M = int(rs.choice([1, 7, 63, 64, 65, 127, 129, 500, 1000, 2999, 8191]))
-            N = int(rs.choice([8, 24, 64, 128, 136, 192, 256, 320, 384, 576, 1024]))
-            K = int(rs.choice([32, 64, 96, 256, 512, 1024]))
-            a = torch.randn(M, K, device=DEV, generator=g)
-            a2 = torch.randn(M, K, device=DEV, generator=g) if rs.rand() < 0.3 else None
-            w = torch.randn(N, K, device=DEV, generator=g) / K ** 0.5
-            b = torch.randn(N, device=DEV, generator=g) if rs.rand() < 0.8 else None
-            relu = bool(rs.rand() < 0.5)
-            mask = (torch.rand(M, device=DEV, generator=g) > 0.3).to(torch.uint8) if rs.rand() < 0.5 else None
-            x = a if a2 is None else a + a2
-            ref = x.double() @ w.double().t() + (0 if b is None else b.double())
-            unit = x.double().abs() @ w.double().abs().t() + (0 if b is None else b.double().abs()) + 1e-30
-            if relu:
-                ref = torch.relu(ref)
-            if mask is not None:
-                ref = ref * mask[:, None].double()
-            for form in ("split", "exact"):
-                _f32_gemm(form)
+    for it in range(40):
+        M = int(rs.choice([1, 7, 63, 64, 65, 127, 129, 500, 1000, 2999, 8191]))
+        N = int(rs.choice([8, 24, 64, 128, 136, 192, 256, 320, 384, 576, 1024]))
+        K = int(rs.choice([32, 64, 96, 256, 512, 1024]))
+        a = torch.randn(M, K, device=DEV, generator=g)
+        a2 = torch.randn(M, K, device=DEV, generator=g) if rs.rand() < 0.3 else None
+        w = torch.randn(N, K, device=DEV, generator=g) / K ** 0.5
+        b = torch.randn(N, device=DEV, generator=g) if rs.rand() < 0.8 else None
+        relu = bool(rs.rand() < 0.5)
+        mask = (torch.rand(M, device=DEV, generator=g) > 0.3).to(torch.uint8) if rs.rand() < 0.5 else None
+        x = a if a2 is None else a + a2
+        ref = x.double() @ w.double().t() + (0 if b is None else b.double())
+        unit = x.double().abs() @ w.double().abs().t() + (0 if b is None else b.double().abs()) + 1e-30
+        if relu:
+            ref = torch.relu(ref)
+        if mask is not None:
+            ref = ref * mask[:, None].double()
+        for form in ("split", "exact"):
+            with _f32_gemm(form):
                 got = ops.linear(a, w, b, relu=relu, rowmask=mask, add=a2)
-                err = float(((got.double() - ref).abs() / unit).max())
-                assert err < 2.0 ** -24 * (8 + K ** 0.5), (it, M, N, K, form, err)
-                if mask is not None:
-                    assert float(got[mask == 0].abs().max() if (mask == 0).any() else 0.0) == 0.0
-    finally:
-        _f32_gemm("split")
+            err = float(((got.double() - ref).abs() / unit).max())
+            assert err < 2.0 ** -24 * (8 + K ** 0.5), (it, M, N, K, form, err)
+            if mask is not None:
+                assert float(got[mask == 0].abs().max() if (mask == 0).any() else 0.0) == 0.0
 
 
 def test_linear_f32_split_form_edges():
@@ -350,14 +344,11 @@ def test_fp32_decoder_on_split_gemms_vs_exact_gemms(cname):
     gc = case_to_device(case, DEV)
     run = lambda: dec(gc.tgt, gc.reference_points, gc.src_views, gc.meta, gc.spatial_shapes, gc.level_start_index, None,
                       query_pos=gc.query_pos, threshold=0.1)
-    try:
-        with torch.no_grad():
-            _f32_gemm("exact")
+    with torch.no_grad():
+        with _f32_gemm("exact"):
             hs0, refs0, r2d0, p2d0, cls0 = run()
-            _f32_gemm("split")
+        with _f32_gemm("split"):
             hs1, refs1, r2d1, p2d1, cls1 = run()
-    finally:
-        _f32_gemm("split")
     assert _relerr(hs1, hs0) < 2e-5
     assert float((torch.stack(cls1) - torch.stack(cls0)).abs().max()) < 2e-6
     valid = (refs0[1:].abs().sum(-1) > 0) & (refs1[1:].abs().sum(-1) > 0)
@@ -1662,14 +1653,10 @@ def test_bin_pairs_all_variants_against_a_stable_sort(n_img, Lq):
     for bit in range(6):
         key |= ((cx >> bit) & 1) << (2 * bit) | ((cy >> bit) & 1) << (2 * bit + 1)
     key = torch.where(inside.bool(), key, torch.full_like(key, 4096))
-    lib = _lib.load()
     got = {}
     for multi in (0, 1):
-        lib.mvg_set_tuning(b"bin_multi", multi)
-        try:
+        with _lib.tuning(bin_multi=multi):
             order = _per_image_order(ops.bin_pairs(ref, inside.view(-1), levels), inside)
-        finally:
-            lib.mvg_set_tuning(b"bin_multi", 1)
         base = torch.arange(n_img, device=DEV).view(-1, 1) * Lq
         local = order - base
         assert int(local.min()) >= 0 and int(local.max()) < Lq
@@ -1726,7 +1713,6 @@ def test_differentiable_dlt_matches_svd_autograd():
 _KNOBS = [("gsamp_pipe", 1, True), ("linear_tiles", 0, True), ("linear_tiles", 2, True), ("gsamp_threads", 128, True), ("gsamp_threads", 512, True),
           ("gsamp_threads", 1024, True), ("gsamp_map", 0, True), ("gsamp_map", 8, True), ("bin_multi", 0, True), ("auto_small", 0, False),
           ("wreg_grid", 256, True), ("wreg_grid", 64, True), ("chain_rm", 64, True), ("chain_rm", 256, False), ("gsamp_lds_pad", 22528, True)]
-_KNOB_DEFAULTS = dict(gsamp_pipe=0, linear_tiles=1, gsamp_threads=256, gsamp_map=4, bin_multi=1, auto_small=1, wreg_grid=512, chain_rm=128, gsamp_lds_pad=0)
 
 
 @pytest.mark.parametrize("key,value,exact", _KNOBS, ids=["%s=%d" % (k, v) for k, v, _ in _KNOBS])
@@ -1745,11 +1731,8 @@ def test_every_kernel_variant_behind_a_tuning_knob(key, value, exact):
                                                   gc.level_start_index, None, query_pos=gc.query_pos, threshold=0.1)[:4]]
     with torch.no_grad():
         ref = run()
-        assert lib.mvg_set_tuning(key.encode(), value) == 0
-        try:
+        with _lib.tuning(**{key: value}):
             got = run()
-        finally:
-            assert lib.mvg_set_tuning(key.encode(), _KNOB_DEFAULTS[key]) == 0
         again = run()
     for a, b in zip(ref, again):
         assert torch.equal(a, b)                                     # the knob was restored
@@ -1771,7 +1754,6 @@ def test_forward_operator_mappings_agree_bit_for_bit(N, Lq, M, D, L, P, dt):
     with locations that leave the maps, L * P not a multiple of the batch and query counts that do not fill the last workgroup."""
     from mvgformer_amd import _lib
     from mvgformer_amd import deformable as DF
-    lib = _lib.load()
     gen = torch.Generator().manual_seed(N * 1000 + Lq)
     shapes = torch.tensor([[20, 31], [11, 16], [5, 8]][:L], dtype=torch.long)
     starts = torch.cat([shapes.new_zeros(1), (shapes[:, 0] * shapes[:, 1]).cumsum(0)[:-1]])
@@ -1780,12 +1762,9 @@ def test_forward_operator_mappings_agree_bit_for_bit(N, Lq, M, D, L, P, dt):
     loc = (torch.rand(N, Lq, M, L, P, 2, generator=gen) * 1.3 - 0.15).to(DEV)
     attn = torch.softmax(torch.randn(N, Lq, M, L * P, generator=gen), -1).view(N, Lq, M, L, P).to(DEV)
     out = {}
-    try:
-        for mp in (1, 2, 0):
-            assert lib.mvg_set_tuning(b"fwd_map", mp) == 0
+    for mp in (1, 2, 0):
+        with _lib.tuning(fwd_map=mp):
             out[mp] = DF.deform_forward(value, shapes.to(DEV), starts.to(DEV), loc, attn, 64).clone()
-    finally:
-        assert lib.mvg_set_tuning(b"fwd_map", 1) == 0
     assert torch.equal(out[0], out[1]) and torch.equal(out[0], out[2])
 
 
@@ -1797,7 +1776,6 @@ def test_fp32_sampler_mappings_agree_bit_for_bit(cfg, kw):
     also for a launch whose last wavefronts are partly out of range (3 queries)."""
     from mvgformer_amd import _lib
     from mvgformer_amd.factory import build_decoder_for_case, case_to_device
-    lib = _lib.load()
     case = build_case(cfg, seed=5, **kw)
     dec = build_decoder_for_case(case, DEV, dtype=torch.float32)
     gc = case_to_device(case, DEV)
@@ -1805,14 +1783,11 @@ def test_fp32_sampler_mappings_agree_bit_for_bit(cfg, kw):
                                                   gc.level_start_index, None, query_pos=gc.query_pos, threshold=0.1)[:4]]
     with torch.no_grad():
         ref = run()
-        for key, value, default in ((b"gfused_chunk", 0, 4), (b"gfused_chunk", 1, 4), (b"gfused_chunk", 16, 4)):
-            assert lib.mvg_set_tuning(key, value) == 0
-            try:
+        for value in (0, 1, 16):
+            with _lib.tuning(gfused_chunk=value):
                 got = run()
-            finally:
-                assert lib.mvg_set_tuning(key, default) == 0
             for a, b in zip(ref, got):
-                assert torch.equal(a, b), (key, value)
+                assert torch.equal(a, b), ("gfused_chunk", value)
 
 
 @pytest.mark.parametrize("rows,N,K", [(76800, 256, 256), (1000, 192, 256), (15360, 1024, 256), (777, 256, 1024), (33, 64, 32)])
@@ -1971,11 +1946,8 @@ def test_fp32_chains_on_two_part_fp16_operands():
     assert torch.equal(res["plain"][0], res["ordered"][0]) and torch.equal(res["plain"][1], res["ordered"][1])   # tile membership does not matter
     from mvgformer_amd import _lib
     for r in (32, 64):                                            # nor does the tile size (the launcher picks it by the row count)
-        try:
-            assert _lib.load().mvg_set_tuning(b"f32h_rows", r) == 0
+        with _lib.tuning(f32h_rows=r):
             attn, o = ops.chain_attn_pose_f32h(samp, inside, *wts, order=order, o_masked=o_masked)
-        finally:
-            assert _lib.load().mvg_set_tuning(b"f32h_rows", 0) == 0
         assert torch.equal(attn, res["ordered"][0]) and torch.equal(o, res["ordered"][1])
     # ---- chain B
     B, NQ, J, V = 1, 41, 15, 3
@@ -1995,13 +1967,9 @@ def test_fp32_chains_on_two_part_fp16_operands():
     assert float((out[4].double() - lin64(y + qpos.double(), Wn, bn)).abs().max()) < 3e-5
     assert bool((out[2].bool() == (pr[..., 1] > 0.5)).all())
     # both tile sizes (the launcher picks by the row count): identical
-    from mvgformer_amd import _lib as _l
     for r in (32, 64):
-        try:
-            assert _l.load().mvg_set_tuning(b"f32h_rows", r) == 0
+        with _lib.tuning(f32h_rows=r):
             outr = ops.chain_update_ffn_class_f32h(attn, V, tgt, *args, 0.5, B, NQ, J, next_query_proj=nxt)
-        finally:
-            assert _l.load().mvg_set_tuning(b"f32h_rows", 0) == 0
         assert all(torch.equal(a, b) for a, b in zip(outr, out))
     # the persons in another order: every person's rows are unchanged (a tile is 2 or 4 persons)
     perm = torch.randperm(NQ, generator=gen).to(DEV)

@@ -1,7 +1,5 @@
 """DQDecoderLayer.plan: the one place where a layer's sampler form, its fused chains, the pair binning, the masked-tile skipping
 and the hand-offs to its neighbours are decided -- as a table over the switches (no GPU: the plan is host logic)."""
-import contextlib
-
 import pytest
 import torch
 
@@ -22,18 +20,10 @@ def _layer(dt, attrs=(), **kw):
     return layer
 
 
-@contextlib.contextmanager
 def _f32_split(value):
-    """the library's f32_split knob (bench.py --f32-gemm exact sets 0), restored on the way out"""
+    """the library's f32_split knob (bench.py --f32-gemm exact sets 0), restored on the way out; None = as it is"""
     from mvgformer_amd import _lib
-    lib = _lib.load()
-    before = _lib.TUNING.get("f32_split", 1)
-    try:
-        if value is not None:
-            assert lib.mvg_set_tuning(b"f32_split", value) == 0
-        yield
-    finally:
-        assert lib.mvg_set_tuning(b"f32_split", before) == 0
+    return _lib.tuning(**({} if value is None else {"f32_split": value}))
 
 
 # (id, dtype, layer arguments, attributes set afterwards, f32_split knob, levels) ->

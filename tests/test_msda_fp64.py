@@ -214,12 +214,8 @@ def test_forward_against_fp64(name, dtype):
         bar = bar + 2.0 ** -8 * ref["out"].abs()
     lt = F64 if dtype == F64 else F32
     args = (c["value"].to(DEV, dtype), c["shapes"].to(DEV), c["starts"].to(DEV), c["loc"].to(DEV, lt), c["weight"].to(DEV, lt))
-    lib = _lib().load()
-    try:
-        for fwd_map in (0, 1, 2):
-            assert lib.mvg_set_tuning(b"fwd_map", fwd_map) == 0
+    for fwd_map in (0, 1, 2):
+        with _lib().tuning(fwd_map=fwd_map):
             y = ops.msda_forward(*args)
             assert y.dtype == dtype
             _check("%s forward %s fwd_map=%d (k %.2f)" % (name, str(dtype).split(".")[1], fwd_map, k["out"]), y, ref["out"], bar)
-    finally:
-        lib.mvg_set_tuning(b"fwd_map", 1)

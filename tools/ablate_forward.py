@@ -57,7 +57,7 @@ with torch.no_grad():
     torch.cuda.synchronize()
 full = capture()
 calls = {}
-names = [n for n in _lib.SIGNATURES if n not in ("mvg_device_info", "mvg_set_tuning", "mvg_bin_pairs_workspace", "mvg_msda_backward_det_workspace")]
+names = [n for n in _lib.SIGNATURES if n not in ("mvg_device_info", "mvg_set_tuning", "mvg_tuning_knob", "mvg_bin_pairs_workspace", "mvg_msda_backward_det_workspace")]
 # which entry points does the forward use, and how often?
 orig = {n: getattr(lib, n) for n in names}
 for n in names:

@@ -9,7 +9,6 @@ import torch  # noqa: E402
 
 from mvgformer_amd import _lib, ops  # noqa: E402
 
-lib = _lib.load()
 n_img = int(sys.argv[1]) if len(sys.argv) > 1 else 5
 layers = int(sys.argv[2]) if len(sys.argv) > 2 else 4
 S = 40320
@@ -55,7 +54,6 @@ for nl in (1, 2, 3, 4):
     line += "  %d layer%s %6.1f us (%4.0f GB/s min traffic)" % (nl, "s" if nl > 1 else " ", us, mb(2 * nl) / us * 1e3 / 1e3)
 print(line)
 for grid in (384, 448, 512):
-    lib.mvg_set_tuning(b"wreg_grid", grid)
-    us1, us3 = t(lambda: ops.pyramid_group_ws(feat, jobs[:2])), t(lambda: ops.pyramid_group_ws(feat, jobs[2:8]))
+    with _lib.tuning(wreg_grid=grid):
+        us1, us3 = t(lambda: ops.pyramid_group_ws(feat, jobs[:2])), t(lambda: ops.pyramid_group_ws(feat, jobs[2:8]))
     print("wreg_grid %d: 1 layer %6.1f us, 3 layers %6.1f us" % (grid, us1, us3))
-lib.mvg_set_tuning(b"wreg_grid", 512)

@@ -9,7 +9,6 @@ import torch  # noqa: E402
 
 from mvgformer_amd import _lib, ops  # noqa: E402
 
-lib = _lib.load()
 n_img, S = 5, 40320
 feat = torch.randn(n_img, S, 256, device="cuda").to(torch.bfloat16)
 Wv = (torch.randn(256, 256, device="cuda") / 16).to(torch.bfloat16)
@@ -32,9 +31,8 @@ def t(fn, n=20):
 
 
 for grid in (256, 512, 768, 1024):
-    lib.mvg_set_tuning(b"wreg_grid", grid)
-    a = t(lambda: ops.value_proj_planes_ws(feat, Wf, bv, vp))
-    b = t(lambda: ops.feat_linear_ws(feat, Wf, 192))
+    with _lib.tuning(wreg_grid=grid):
+        a = t(lambda: ops.value_proj_planes_ws(feat, Wf, bv, vp))
+        b = t(lambda: ops.feat_linear_ws(feat, Wf, 192))
     print("grid %4d  value->planes %7.1f us (%5.0f GB/s)   G %7.1f us (%5.0f GB/s)"
           % (grid, a, 206e6 / a / 1e3, b, 180e6 / b / 1e3))
-lib.mvg_set_tuning(b"wreg_grid", 512)
