@@ -144,12 +144,12 @@ class DecoderHead(nn.Module):
         ctx = context
         if ctx is None:
             ctx = DecoderContext.prepare(spatial_shapes, level_start_index, meta, layer0.img_size, layer0.compute_dtype, batch, dev)
-        ref = getattr(ctx, "_train_ref", None) if context is not None else None
+        ref = None if context is None else ctx.train_ref
         if ref is None or ref.shape[0] != batch or ref.device != dev:
             ref = sample_space_reference_points(self.num_instance, self.space_size, self.space_center, batch, dev,
                                                 t_pose=self.t_pose)
             if context is not None:
-                ctx._train_ref = ref        # a function of the head's constants alone; nobody writes to it
+                ctx.train_ref = ref         # a function of the head's constants alone; nobody writes to it
         jmap = self.convert_joint_format_indices
         pairs = self.criterion.matcher.match(ref, meta, joint_map=jmap, num_joints=self.num_joints)
         hs, refs, refs2d, projs2d, classes = self.decoder(

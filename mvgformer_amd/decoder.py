@@ -24,7 +24,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import ops
-from .projattn import ProjAttn, WeightCache, f32_split_on
+from .projattn import ProjAttn, PyramidProducts, WeightCache, f32_split_on
 
 # backend of the init_self_attention block under autograd, read once: "torch" | "native" (DQDecoderLayer.set_self_attention_training)
 SELF_ATTN_TRAIN = os.environ.get("MVG_SELF_ATTN_TRAIN", "torch")
@@ -105,10 +105,14 @@ class DecoderContext:
     ``prepare`` touches host memory (it reads the small camera tensors of ``meta``), ``pack`` only
     enqueues kernels -- so a HIP-graph capture can call ``pack`` with a prepared context."""
 
-    def __init__(self, levels, cams, V, B, dtype):
+    def __init__(self, levels=None, cams=None, V=0, B=0, dtype=torch.float32):
         self.levels, self.cams, self.V, self.B, self.dtype = levels, cams, V, B, dtype
         self.feat = None
         self._buffer = None    # producer-owned packed pyramid (pyramid_buffers)
+        self.packed_event = None    # recorded behind a pack on the decoder's side stream (DQDecoder.pack_pyramid), else None
+        # training constants of a context that outlives its forward (training.GraphedTrainStep): the projection matrices of the camera
+        # records, the (pointer, version) of the records they were built from, the head's initial reference points
+        self.train_Pm = self.train_key = self.train_ref = None
 
     @classmethod
     def prepare(cls, spatial_shapes, level_start_index, meta, img_size, dtype, batch_size, device):
@@ -133,6 +137,32 @@ class DecoderContext:
         self._buffer = torch.empty((self.V * self.B, self.levels.S, channels), dtype=self.dtype, device=dev)
         return ops.pyramid_level_views(self._buffer, self.levels)
 
+    def proj_matrices(self):
+        """training path: the projection matrices of the camera records, rebuilt when the records were replaced or rewritten"""
+        key = (self.cams.data_ptr(), self.cams._version)
+        if self.train_key != key:
+            from . import geometry_torch as G
+            self.train_Pm, self.train_key = G.proj_matrices_from_records(self.cams, self.V, self.B), key
+        return self.train_Pm
+
+    def set_cameras(self, meta, img_size):
+        """new calibration / crop for the same number of images: refills the packed camera records in place (host packing + one small
+        H2D copy) and, from them, the training path's projection matrices; a captured graph reads both through the same pointers"""
+        fresh = ops.pack_cameras(meta, img_size, self.cams.device)
+        if fresh.shape != self.cams.shape:
+            raise RuntimeError("set_cameras: %s camera records, the runner was built for %s" % (tuple(fresh.shape), tuple(self.cams.shape)))
+        with torch.no_grad():
+            self.cams.copy_(fresh)
+            if self.train_Pm is not None:       # same tensor, new values, stamped current
+                from . import geometry_torch as G
+                self.train_Pm.copy_(G.proj_matrices_from_records(self.cams, self.V, self.B))
+                self.train_key = (self.cams.data_ptr(), self.cams._version)
+        return self
+
+    def tensors(self):
+        """the device tensors the context holds (what a captured graph addresses and does not own)"""
+        return [t for t in (self.cams, self.feat, self._buffer, self.train_Pm, self.train_ref) if t is not None]
+
     @classmethod
     def build(cls, src_views, spatial_shapes, level_start_index, meta, img_size, dtype, batch_size):
         return cls.prepare(spatial_shapes, level_start_index, meta, img_size, dtype, batch_size,
@@ -150,6 +180,7 @@ class DecoderRun:
         # consumed once, by position: the query term (B*Lq,192) f32 from the previous layer's chain B, (new_ref, (r, ref_lvl, inside))
         # from the previous layer's triangulation launch, the callable that issues the NEXT layer's pyramid products
         self.xw_in, self.proj_in, self.after_chain_b = {}, {}, {}
+        self.order = None       # "first" binning: the pairs' processing order from the first layer's projections
 
     def __enter__(self):
         for layer in self.layers:
@@ -599,21 +630,17 @@ class DQDecoderLayer(MvPDecoderLayer):
         # Per-forward constants of the geometry (packed camera records, level table, projection matrices): built once and kept on the
         # DecoderContext when the layer runs inside DQDecoder.forward -- as torch ops per layer they were ~40 launches each.
         ctx = (self._run or _NO_RUN).ctx
-        tc = getattr(ctx, "_train_cache", None) if ctx is not None else None
-        if tc is not None and tc["key"] != (ctx.cams.data_ptr(), ctx.cams._version):
-            tc = None           # the context was given new camera records: projection matrices and records are rebuilt
-        if tc is None:
-            cams = ctx.cams if ctx is not None else ops.pack_cameras(meta, self.img_size, dev)
-            tc = dict(cams=cams, levels=ctx.levels if ctx is not None else ops.Levels(src_spatial_shapes, level_start_index),
-                      Pm=G.proj_matrices_from_records(cams, V, B), key=(cams.data_ptr(), cams._version))
-            if ctx is not None:
-                ctx._train_cache = tc
+        if ctx is not None:
+            cams, levels, Pm = ctx.cams, ctx.levels, ctx.proj_matrices()
+        else:
+            cams, levels = ops.pack_cameras(meta, self.img_size, dev), ops.Levels(src_spatial_shapes, level_start_index)
+            Pm = G.proj_matrices_from_records(cams, V, B)
         # all V views as ONE batch of V*B images (image n = v*B + b, the order of src_views): one projection, one ProjAttn
         # call and one pose MLP instead of V of each -- the training step is launch-bound (5 800 launches per step at cfg-2)
         if not X.requires_grad:
             # the reference points do not carry a gradient into the projection (detach_refpoints_cameraprj, every shipped YAML):
             # the inference kernel projects them (one launch, same arithmetic: tests/test_hip_parity.py)
-            r_all, ref_lvl, inside_u8 = ops.project(X.float().contiguous(), tc["cams"], tc["levels"], V, B)
+            r_all, ref_lvl, inside_u8 = ops.project(X.float().contiguous(), cams, levels, V, B)
             inside_all = inside_u8.bool()
         else:
             cam_all = {k: torch.cat([meta[v]["camera"][k].to(dev) for v in range(V)], 0)
@@ -622,11 +649,8 @@ class DQDecoderLayer(MvPDecoderLayer):
             A_crop = torch.cat([G.crop_affine(meta[v]["center"], meta[v]["scale"], self.img_size, dev) for v in range(V)], 0)
             r_all, inside_all = G.project_points(X.repeat(V, 1, 1), cam_all, center_all, A_crop, self.img_size, views=V)
             ref_lvl = r_all.unsqueeze(2) * WH / (WH - 1)                           # dq_decoder.py:570-573
-        self.proj_attn._packed_feat = ctx.feat if (ctx is not None and ctx.feat is not None) else None
-        try:
-            a_all = self.proj_attn(x.repeat(V, 1, 1), ref_lvl, src_views, None, src_spatial_shapes, level_start_index)
-        finally:
-            self.proj_attn._packed_feat = None
+        a_all = self.proj_attn(x.repeat(V, 1, 1), ref_lvl, src_views, None, src_spatial_shapes, level_start_index,
+                               packed=None if ctx is None else ctx.feat)
         a_all = inside_all.unsqueeze(-1).to(a_all.dtype) * a_all                   # dq_decoder.py:585-586
         from .functions import linear as lin
         if self.training_dtype == torch.bfloat16:
@@ -657,8 +681,8 @@ class DQDecoderLayer(MvPDecoderLayer):
         # Triangulation (dq_decoder.py:929-967): one launch each way over the dense token grid (geometry_torch.DenseDLT).  Only the
         # matched queries are triangulated, like the reference: an unmatched query with a degenerate DLT (homogeneous w == 0, an
         # Inf 2D point) would otherwise put 0 * inf = NaN into the gradients of the parameters all queries share.
-        ud = G.UncropUndistort.apply(ref2d, tc["cams"], V, B)
-        new_ref = G.DenseDLT.apply(ud, conf, tc["Pm"], valid.to(torch.uint8), J)
+        ud = G.UncropUndistort.apply(ref2d, cams, V, B)
+        new_ref = G.DenseDLT.apply(ud, conf, Pm, valid.to(torch.uint8), J)
         vm2 = valid.view(B, 1, NQ, 1, 1)
         zero = torch.zeros((), device=dev)
         ref2d_o = torch.where(vm2, ref2d.view(B, V, NQ, J, 2), zero).reshape(B, V, Lq, 2)
@@ -736,19 +760,21 @@ class DQDecoderLayer(MvPDecoderLayer):
         xw_in = run.xw_in.pop(run.i, None)     # query term computed by the previous layer's chain B (or None)
         if xw_in is not None and (tuple(xw_in.shape) != (B * Lq, 192) or query_tgt is not None):
             xw_in = None                        # (computed from tgt + query_pos: not this layer's query)
-        if self.proj_attn._vp_event is None and getattr(ctx, "_packed_event", None) is not None:
+        if ctx.packed_event is not None and not self.proj_attn.products.pending(self.proj_attn):
             # this layer's pyramid products run inline on THIS stream (no side-stream launch reached it) while the pyramid was packed
             # on the side stream (DQDecoder.pack_pyramid): order the read behind the pack and keep the allocator informed
-            torch.cuda.current_stream().wait_event(ctx._packed_event)
+            torch.cuda.current_stream().wait_event(ctx.packed_event)
             ctx.feat.record_stream(torch.cuda.current_stream())
         # processing order of the pairs, shared by the sampler (L1 locality, masked pairs skipped or zero-filled) and what reads its
         # output (all-masked tiles skipped); a G-sampler on its own bins for itself (ProjAttn.native_sample)
         order = None
         if plan.chain_a is not None or plan.skip_masked:
-            if plan.binning == "first":
-                if getattr(ctx, "order", None) is None or ctx.order.numel() != V * B * Lq:
-                    ctx.order = ops.bin_pairs(ref_lvl, None, ctx.levels)
-                order = ctx.order
+            if plan.binning == "first":         # binned once per forward; a layer called without a run bins per call
+                order = run.order
+                if order is None or order.numel() != V * B * Lq:
+                    order = ops.bin_pairs(ref_lvl, None, ctx.levels)
+                    if run is not _NO_RUN:
+                        run.order = order
             elif plan.binning:
                 order = ops.bin_pairs(ref_lvl, inside.view(-1), ctx.levels)
         if plan.chain_a is not None:
@@ -858,7 +884,10 @@ class DQDecoder(MvPDecoder):
         # cfg-2 bf16 1.43 -> 1.30 ms per sample on MI355X.  MVG_OVERLAP_PYRAMID=0 runs them inline.
         self.overlap_pyramid = os.environ.get("MVG_OVERLAP_PYRAMID", "1") != "0"
         self.overlap_pyramid_f32 = os.environ.get("MVG_OVERLAP_PYRAMID_F32", "1") != "0"
-        self._side_stream = None
+        # ONE owner of the layers' product buffers, their ready state and the side stream (a deep copy of the decoder shares a fresh one)
+        self.products = PyramidProducts()
+        for layer in self.layers:
+            layer.proj_attn.products = self.products
         # layer l's fused chain B also computes layer l+1's query term xw = (tgt' + query_pos) W^T + b (bf16 path)
         self.fuse_next_query_term = True
         # bf16: layers per grouped launch of the pyramid products behind layer 0's own (0 = one launch per product, rounds 1-4)
@@ -872,24 +901,6 @@ class DQDecoder(MvPDecoder):
         # per forward (profiles/r05_experiments.txt section 10).  MVG_PYRAMID_JIT = 0 | 1 overrides the choice.
         self.pyramid_jit = os.environ.get("MVG_PYRAMID_JIT", "auto")
         self.pyramid_jit_slots = int(os.environ.get("MVG_PYRAMID_JIT_SLOTS", "32"))
-        self._share_f32_pool()
-
-    def _share_f32_pool(self):
-        """the inline fp32 pyramid products share one (value, G) pair per stream -- of THIS decoder (a ProjAttn used on its own, or a
-        deep copy of one, has a private, empty pool: ProjAttn.__deepcopy__)"""
-        pool = {}
-        for layer in self.layers:
-            layer.proj_attn._f32_pool = pool
-
-    def __deepcopy__(self, memo):
-        cls = self.__class__
-        new = cls.__new__(cls)
-        memo[id(self)] = new
-        for k, v in self.__dict__.items():
-            # the side stream of an earlier GPU forward is run-time state (and not copyable): the copy forks its own
-            new.__dict__[k] = None if k == "_side_stream" else copy.deepcopy(v, memo)
-        new._share_f32_pool()           # the copy's layers share ONE fresh pool again, not one each
-        return new
 
     def set_compute_dtype(self, dtype):
         for layer in self.layers:
@@ -930,13 +941,10 @@ class DQDecoder(MvPDecoder):
         if not (self.overlap_pyramid and distinct and device.type == "cuda" and not torch.is_grad_enabled()
                 and all(ahead(l) for l in self.layers)):
             return None
-        if self._side_stream is None:
-            self._side_stream = torch.cuda.Stream()
         if not torch.cuda.is_current_stream_capturing():
             for l in self.layers:   # cached operands are built here, on the forking stream, never on the side stream
                 l.prepare_caches()
-        self._side_stream.wait_stream(torch.cuda.current_stream())
-        return self._side_stream
+        return self.products.fork()
 
     def launch_pyramid_projections(self, ctx, side=None, forked=False, jit=False):
         """Issue every layer's query-independent GEMMs (ProjAttn.project_pyramid) on the side stream, each followed
@@ -971,10 +979,7 @@ class DQDecoder(MvPDecoder):
                         for layer in group:
                             jobs += layer.proj_attn.pyramid_jobs(ctx.feat)
                         ops.pyramid_group_ws(ctx.feat, jobs, slots=slots)
-                        ev = torch.cuda.Event()
-                        ev.record()
-                        for layer in group:
-                            layer.proj_attn._vp_event = ev
+                        self.products.produced([layer.proj_attn for layer in group])
                     if use_jit and gi > 0:
                         def hook(issue=issue):
                             side.wait_stream(torch.cuda.current_stream())     # behind the previous layer's chain B
@@ -989,14 +994,14 @@ class DQDecoder(MvPDecoder):
         """ctx.pack(src_views) -- on the side stream (forked from the current one) when every consumer of the packed pyramid runs
         there (bf16: the pyramid products), so that the first layer's prologue does not queue behind the 46-us pack; follow it
         with launch_pyramid_projections(ctx, side, forked=True)."""
-        ctx._packed_event = None
+        ctx.packed_event = None
         if side is not None and self.pack_on_side and ctx.dtype == torch.bfloat16:
             with torch.cuda.stream(side):
                 ctx.pack(src_views)
                 # a consumer on ANOTHER stream (ProjAttn.native_sample's inline products, when a layer's just-in-time hook did not
                 # fire) waits on this event; ctx.feat was allocated on `side`
-                ctx._packed_event = torch.cuda.Event()
-                ctx._packed_event.record()
+                ctx.packed_event = torch.cuda.Event()
+                ctx.packed_event.record()
         else:
             ctx.pack(src_views)
             if side is not None:
@@ -1038,11 +1043,7 @@ class DQDecoder(MvPDecoder):
     def join_pyramid_projections(self, side, keep_results=False):
         """The current stream waits for the side stream.  keep_results: projections not consumed yet stay valid for
         the layers that follow on this stream (the segmented graphs of mvgformer_amd.dist); else they are dropped."""
-        if side is not None:
-            torch.cuda.current_stream().wait_stream(side)
-        for layer in self.layers:
-            pa = layer.proj_attn
-            pa._vp_event = True if (keep_results and pa._vp_event is not None) else None
+        self.products.join(side, keep_results)
 
     def forward(self, tgt, reference_points, src_views, meta, src_spatial_shapes, src_level_start_index,
                 src_valid_ratios, query_pos=None, src_padding_mask=None, rgb_views=None, output_dir="./",
@@ -1073,7 +1074,6 @@ class DQDecoder(MvPDecoder):
                 deferred_pack = src_views
             elif ctx.feat is None:
                 raise RuntimeError("DQDecoder.forward: context without a packed pyramid and no src_views")
-            ctx.order = None
             inter, inter_ref, inter_2d, inter_proj, classes = [], [], [], [], []
             ref_points_2d = None
             with DecoderRun(self.layers, ctx, self.fuse_next_query_term) as run:

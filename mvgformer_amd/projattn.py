@@ -114,6 +114,88 @@ class WeightCache:
         self._store[key] = (stamp, out)
         return out
 
+    def tensors(self):
+        """the cached operand tensors (what a captured graph addresses and does not own)"""
+        return [t for _, out in self._store.values() for t in (out if isinstance(out, tuple) else (out,)) if torch.is_tensor(t)]
+
+
+class PyramidProducts:
+    """The per-layer pyramid products (value planes and G) of ONE decoder: where they live, whether they are ready, and the side
+    stream that makes them ahead of their layers.  DQDecoder creates one and hands it to every layer's ProjAttn; a ProjAttn used on
+    its own has a private one.  Run-time state only: a deep copy is a fresh, empty instance (one per copied decoder, through the memo).
+    Buffers are kept across calls -- the same key and shape return the same tensors, so nothing is allocated inside a graph capture
+    after the warm-up forwards -- in two tables that never share a tensor:
+      per layer    bf16 planes (n_img, 8, S, 32) + G (n_img*S, 192), and the fp32 pair (n_img, S, C) + (n_img*S, 192) made AHEAD on
+                   the side stream, where every layer's products are alive at once
+      per stream   the fp32 pair made INLINE: a layer's products are dead once its sampler ran and the next layer's are written
+                   behind it on the same stream -> one pair per (device, stream) for all layers (0.36 GB at cfg-2 instead of 0.36 GB
+                   per layer); streams do not share (decoders in flight)
+    Ready state of a layer's products: not produced (absent), produced (the event its consumer waits on) or joined (None: the
+    consumer's stream has waited for the side stream already)."""
+
+    def __init__(self):
+        self._per_layer, self._per_stream, self._ready, self._side = {}, {}, {}, None
+
+    def __deepcopy__(self, memo):
+        return PyramidProducts()
+
+    def buffers(self, proj_attn, dtype, n_img, S, C, device, ahead=False, stream=None):
+        """(value, G) for one layer's products, allocated or reused.  ahead: made on the side stream (read by the fp32 form alone);
+        stream: the key of the inline fp32 pair (default: the current stream of `device`)"""
+        if dtype == torch.float32 and not ahead:
+            table, key = self._per_stream, (device, torch.cuda.current_stream(device).cuda_stream if stream is None else stream)
+        else:
+            table, key = self._per_layer, proj_attn
+        shape = (n_img, 8, S, 32) if dtype == torch.bfloat16 else (n_img, S, C)
+        pair = table.get(key)
+        if pair is None or pair[0].dtype != dtype or tuple(pair[0].shape) != shape or pair[0].device != device:
+            pair = table[key] = (torch.empty(shape, dtype=dtype, device=device), torch.empty((n_img * S, 192), dtype=dtype, device=device))
+        return pair
+
+    def produced(self, proj_attns, event=None):
+        """these layers' products are written behind `event` (None: recorded here, on the current stream) into their per-layer buffers"""
+        if event is None:
+            event = torch.cuda.Event()
+            event.record()
+        for pa in proj_attns:
+            self._ready[pa] = event
+
+    def take(self, proj_attn):
+        """(value, G) made ahead for this layer, behind a wait on their event where the stream has not joined yet -- the state stays
+        until join() --; None: the layer computes them inline"""
+        if proj_attn not in self._ready:
+            return None
+        event = self._ready[proj_attn]
+        if event is not None:
+            event.wait()        # the current stream
+        return self._per_layer[proj_attn]
+
+    def join(self, side=None, keep=False):
+        """The current stream waits for the side stream.  keep: products not consumed yet stay valid, without a further wait, for the
+        layers that follow on this stream (the segmented graphs of mvgformer_amd.dist); else they are dropped."""
+        if side is not None:
+            torch.cuda.current_stream().wait_stream(side)
+        self._ready = dict.fromkeys(self._ready) if keep else {}
+
+    def pending(self, proj_attn=None):
+        """this layer's (None: some layer's) products are produced or joined, and not dropped yet"""
+        return bool(self._ready) if proj_attn is None else proj_attn in self._ready
+
+    def fork(self):
+        """the side stream (created on first use), waiting for the current one"""
+        if self._side is None:
+            self._side = torch.cuda.Stream()
+        self._side.wait_stream(torch.cuda.current_stream())
+        return self._side
+
+    def tensors(self):
+        """every live buffer, once (what a captured graph addresses and does not own)"""
+        return [t for table in (self._per_layer, self._per_stream) for pair in table.values() for t in pair]
+
+    def signature(self):
+        """(pointer, dtype, shape) of every buffer: changes exactly when one is added or replaced"""
+        return tuple((t.data_ptr(), t.dtype, tuple(t.shape)) for t in self.tensors())
+
 
 class ProjAttn(nn.Module):
     def __init__(self, d_model=256, n_levels=4, n_heads=8, n_points=4, projattn_posembed_mode="use_rayconv"):
@@ -163,29 +245,7 @@ class ProjAttn(nn.Module):
         self._wc = WeightCache()
         # precision of the autograd path (the layer's set_training_dtype): float32, or bfloat16 operands with fp32 accumulation
         self.training_dtype = torch.float32
-        self._vp = None
-        self._vp_event = None
-        self._G = None
-        # inline fp32 pyramid products: one (value, G) pair per (device, stream) shared by the layers of ONE decoder (DQDecoder
-        # hands its layers a common dict); it dies with its owner
-        self._f32_pool = {}
-
-    def __deepcopy__(self, memo):
-        """copies (EMA / checkpoint copies of a decoder) get fresh, empty run-time state: the pooled fp32 (value, G) buffers
-        (0.36 GB per pair at cfg-2), the weight cache and the side-stream hand-off are not part of the module's state"""
-        import copy
-        cls = self.__class__
-        new = cls.__new__(cls)
-        memo[id(self)] = new
-        skip = {"_f32_pool": dict, "_wc": WeightCache}
-        for k, v in self.__dict__.items():
-            if k in skip:
-                new.__dict__[k] = skip[k]()
-            elif k in ("_vp", "_G", "_vp_event"):
-                new.__dict__[k] = None
-            else:
-                new.__dict__[k] = copy.deepcopy(v, memo)
-        return new
+        self.products = PyramidProducts()   # buffers and ready state of the pyramid products; DQDecoder hands its layers a common one
 
     def _reset_parameters(self):
         constant_(self.sampling_offsets.weight.data, 0.)
@@ -284,84 +344,46 @@ class ProjAttn(nn.Module):
         return (wc.get("Wp", (self.output_proj.weight,), dt), wc.get("bp", (bias,), torch.float32),
                 wc.get("zero_row", (bias,), torch.float32, lambda b: torch.zeros_like(b)) if skip_masked else None)
 
-    def _plane_buffer(self, n_img, S, device):
-        """value planes buffer (every line is fully rewritten by each projection); kept across calls."""
-        shape = (n_img, 8, S, 32)
-        if self._vp is None or self._vp.dtype != torch.bfloat16 or tuple(self._vp.shape) != shape or self._vp.device != device:
-            self._vp = torch.empty(shape, dtype=torch.bfloat16, device=device)
-        return self._vp
-
-    def _wait_pyramid(self):
-        """both pyramid projections were produced ahead of time on a side stream (DQDecoder.launch_pyramid_projections)."""
-        if self._vp_event is not True:          # True: already joined into this stream (segmented graphs)
-            torch.cuda.current_stream().wait_event(self._vp_event)
-        # the event stays armed until the end of the forward (DQDecoder.join_pyramid_projections clears it)
-        return self._vp, self._G
-
     def project_pyramid(self, feat, record_event=False):
         """The two query-independent GEMMs of a layer: value planes (projattn.py:169) and G = feat @ [Wo; Wa]^T
         (the pyramid side of projattn.py:180-181).  Neither depends on the queries, so DQDecoder runs them for
         every layer on a side stream next to the latency-bound query-side kernels (record_event=True: the
-        consumer waits on the event); both land in buffers kept across calls."""
+        consumer waits on the event); both land in buffers kept across calls (PyramidProducts)."""
         dt = feat.dtype
         n_img, S, Cc = feat.shape
-        if dt == torch.float32:      # fp32 G-sampling form: plain (rows, 256) / (rows, 192) fp32 products, kept across calls
+        if dt == torch.float32:      # fp32 G-sampling form: plain (rows, 256) / (rows, 192) fp32 products
             f32h = self.f32_fused_active()
             (Wq, _), pyramid = self.sampler_operands("gfused_f32h" if f32h else "gfused_f32", dt)
-            if record_event:
-                # side-stream schedule: every layer's products exist at the same time -> one pair of buffers per layer
-                if (self._vp is None or self._vp.dtype != dt or tuple(self._vp.shape) != (n_img, S, Cc) or self._vp.device != feat.device
-                        or any(self._vp is pair[0] for pair in self._f32_pool.values())):
-                    self._vp = torch.empty((n_img, S, Cc), dtype=dt, device=feat.device)
-                    self._G = torch.empty((n_img * S, 192), dtype=dt, device=feat.device)
-            else:
-                # inline (overlap off, or under autograd): a layer's products are dead once its sampler ran, the next layer's are
-                # written behind it on the same stream -> ONE pair for all layers of this decoder on this stream (0.36 GB at cfg-2
-                # instead of 0.36 GB per layer held for the model's lifetime)
-                slot = (feat.device, torch.cuda.current_stream(feat.device).cuda_stream)      # streams do not share (decoders in flight)
-                cur = self._f32_pool.get(slot)
-                if cur is None or tuple(cur[0].shape) != (n_img, S, Cc):
-                    cur = self._f32_pool[slot] = (torch.empty((n_img, S, Cc), dtype=dt, device=feat.device),
-                                               torch.empty((n_img * S, 192), dtype=dt, device=feat.device))
-                self._vp, self._G = cur
+            vp, G = self.products.buffers(self, dt, n_img, S, Cc, feat.device, ahead=record_event)
             if f32h:
                 # two-part fp16 operands, three products (csrc/f32s.hip: pyramid_ws_f32h_kernel)
                 bv, (Wv_pl, sv), (Wg_pl, sg) = pyramid
-                ops.pyramid_f32h(feat, Wv_pl, sv, bv, Wg_pl, sg, 192, value=self._vp, G=self._G)   # projattn.py:169 + 180-181
+                ops.pyramid_f32h(feat, Wv_pl, sv, bv, Wg_pl, sg, 192, value=vp, G=G)   # projattn.py:169 + 180-181
             else:
-                ops.linear(feat.view(n_img * S, Cc), *pyramid, out=self._vp.view(n_img * S, Cc))     # projattn.py:169
-                ops.linear(feat.view(n_img * S, Cc), Wq, None, out=self._G)
-            if record_event:
-                self._vp_event = torch.cuda.Event()
-                self._vp_event.record()
-            return self._vp, self._G
-        # the 103-MB value write first, G (gathered at random by the sampler) last: G is then the fresher
-        # resident of the 256-MB Infinity Cache when the sampler starts
-        vp = self.project_values(feat)
-        ops.feat_linear_ws(feat, self.sampler_operands("gsamp", dt, query=False)[1][2], 192, out=self._g_buffer(n_img, S, feat.device))
+                ops.linear(feat.view(n_img * S, Cc), *pyramid, out=vp.view(n_img * S, Cc))     # projattn.py:169
+                ops.linear(feat.view(n_img * S, Cc), Wq, None, out=G)
+        else:
+            # the 103-MB value write first, G (gathered at random by the sampler) last: G is then the fresher
+            # resident of the 256-MB Infinity Cache when the sampler starts
+            vp = self.project_values(feat)
+            G = self.products.buffers(self, dt, n_img, S, Cc, feat.device)[1]
+            ops.feat_linear_ws(feat, self.sampler_operands("gsamp", dt, query=False)[1][2], 192, out=G)
         if record_event:
-            self._vp_event = torch.cuda.Event()
-            self._vp_event.record()
-        return vp, self._G
-
-    def _g_buffer(self, n_img, S, device):
-        """G of the bf16 form, kept across calls like the value planes"""
-        shape = (n_img * S, 192)
-        if self._G is None or self._G.dtype != torch.bfloat16 or tuple(self._G.shape) != shape or self._G.device != device:
-            self._G = torch.empty(shape, dtype=torch.bfloat16, device=device)
-        return self._G
+            self.products.produced((self,))
+        return vp, G
 
     def pyramid_jobs(self, feat):
         """this layer's two products as jobs of ops.pyramid_group_ws (value planes, G), into the buffers project_pyramid uses"""
-        n_img, S, _ = feat.shape
+        n_img, S, Cc = feat.shape
         Wv_f, bv, Wg_f = self.sampler_operands("gsamp", feat.dtype, query=False)[1]
-        return [(Wv_f, bv, self._plane_buffer(n_img, S, feat.device), True), (Wg_f, None, self._g_buffer(n_img, S, feat.device), False)]
+        vp, G = self.products.buffers(self, torch.bfloat16, n_img, S, Cc, feat.device)
+        return [(Wv_f, bv, vp, True), (Wg_f, None, G, False)]
 
     def project_values(self, feat):
         """value = rayconv(input_flatten) (projattn.py:169) as bf16 head planes vh[img][head][s][32]."""
-        n_img, S, _ = feat.shape
+        n_img, S, Cc = feat.shape
         Wv_f, bv, _ = self.sampler_operands("gsamp", feat.dtype, query=False)[1]
-        vp = self._plane_buffer(n_img, S, feat.device)
+        vp = self.products.buffers(self, torch.bfloat16, n_img, S, Cc, feat.device)[0]
         ops.value_proj_planes_ws(feat, Wv_f, bv, vp)
         return vp
 
@@ -441,7 +463,7 @@ class ProjAttn(nn.Module):
         if binned and not g16:
             order = ops.bin_pairs(r, pair_mask, levels)
         # the two pyramid products: computed here, or ahead of time on the side stream (DQDecoder.launch_pyramid_projections)
-        vp, G = self.project_pyramid(feat) if self._vp_event is None else self._wait_pyramid()
+        vp, G = self.products.take(self) or self.project_pyramid(feat)
         sample = ops.msda_gsamp if g16 else ops.msda_gfused_f32
         return sample(vp, G, xw, r, levels, B, pair_mask=pair_mask, order=order)   # projattn.py:148-200
 
@@ -468,15 +490,16 @@ class ProjAttn(nn.Module):
         return out.view(n, Lq, nl, C)
 
     def forward(self, query, reference_points, src_views, camera_ray_embeds, input_spatial_shapes,
-                input_level_start_index, input_padding_mask=None):
+                input_level_start_index, input_padding_mask=None, packed=None):
         """Reference signature (projattn.py:115-117).  query (n_views, Lq, C); reference_points
-        (n_views, Lq, n_levels, 2) already rescaled per level; src_views list of (n_views,C,H,W)."""
+        (n_views, Lq, n_levels, 2) already rescaled per level; src_views list of (n_views,C,H,W).
+        packed (beyond the reference signature): the channels-last pyramid (n_views, S, C) the decoder packed from src_views."""
         if not query.is_cuda:
             raise RuntimeError("Not implemented on the CPU")                  # deform.h:49
         if query.device.index != torch.cuda.current_device():
             with torch.cuda.device(query.device):   # kernels go to the current stream of the TENSORS' device
                 return self.forward(query, reference_points, src_views, camera_ray_embeds, input_spatial_shapes,
-                                    input_level_start_index, input_padding_mask)
+                                    input_level_start_index, input_padding_mask, packed)
         n_views, Len_q, c = query.shape
         feat_lvls = len(src_views)
         if self.projattn_posembed_mode != "ablation_not_use_rayconv":
@@ -495,7 +518,6 @@ class ProjAttn(nn.Module):
         # bf16 mixed-precision training (DQDecoderLayer.set_training_dtype): the Linears on LinearBF16, a bf16 value for the
         # sampling op, and a bf16 packed pyramid taken as it is (its consumers round to bf16 anyway)
         bf = self.training_dtype == torch.bfloat16
-        packed = getattr(self, "_packed_feat", None)
         if (packed is not None and (packed.dtype == torch.float32 or (bf and packed.dtype == torch.bfloat16))
                 and packed.shape[0] == n_views and packed.shape[2] == c and not any(s.requires_grad for s in src_views)):
             # the channels-last pyramid the decoder packed once per forward IS cat + permute of the maps (projattn.py:160); only

@@ -6,9 +6,9 @@ triangulation, output stacking -- has static shapes and no host synchronisation,
 one graph launch on the host (what ``bench.py`` times).  The graph holds raw pointers into its input buffers, the decoder's
 weight caches and its per-layer value / G buffers: ``GraphedDecoder`` owns the inputs and, from the capture on, holds a
 reference to every one of those tensors (``_pinned``) -- an eager call of the same decoder with another batch, resolution or
-compute dtype re-allocates ``ProjAttn._vp / _G`` and rebuilds cache entries, and without the references the graph would go on
-reading and writing recycled memory.  ``replay()`` also compares the buffers' addresses with the captured ones and re-captures
-when the decoder has moved on to other buffers.
+compute dtype re-allocates the product buffers (``PyramidProducts``) and rebuilds cache entries, and without the references the
+graph would go on reading and writing recycled memory.  ``replay()`` also compares the buffers' signature with the captured one and
+re-captures when the decoder has moved on to other buffers.
 
     runner = GraphedDecoder(decoder, meta, spatial_shapes, level_start_index, batch=1, num_queries=1024, threshold=0.1)
     for frame in stream:
@@ -75,7 +75,7 @@ class GraphedDecoder:
             self.src_views = [torch.zeros((self.V * batch, C, h, w), dtype=torch.float32, device=dev) for h, w in shapes]
             self.pyramid_views = None
         self.graph, self.outputs = None, None
-        self._pinned, self._captured_ptrs = [], None
+        self._pinned, self._captured = [], None
         # optional device-side post-processing behind the decoder, inside the same graph: one pipeline object owns all of it
         self.post, self.pred, self._graph_pred = None, None, None
         stages = dict(postprocess=postprocess, evaluation=evaluation, tracking=tracking, track_evaluation=track_evaluation,
@@ -109,12 +109,7 @@ class GraphedDecoder:
     def set_cameras(self, meta):
         """new calibration / crop for the same number of images: refills the packed camera records in place (host packing +
         one small H2D copy); the captured graph reads them through the same pointer."""
-        fresh = DecoderContext.prepare(self.spatial_shapes, self.level_start_index, meta, self.dec.layers[0].img_size, self.dtype,
-                                       self.tgt.shape[0], self.dev)
-        if fresh.cams.shape != self.ctx.cams.shape:
-            raise RuntimeError("set_cameras: %s camera records, the runner was built for %s"
-                               % (tuple(fresh.cams.shape), tuple(self.ctx.cams.shape)))
-        self.ctx.cams.copy_(fresh.cams)
+        self.ctx.set_cameras(meta, self.dec.layers[0].img_size)
         if self.post is not None:
             self.post.set_cameras(self.ctx.cams, self.V)
         self.meta = meta
@@ -144,22 +139,16 @@ class GraphedDecoder:
         self._graph_pred = self.pred            # allocated from the graph's pool: static, like the outputs
         # everything the graph addresses by raw pointer and does not own: the per-layer pyramid products and the cached operands
         self._pinned = self._graph_operands()
-        self._captured_ptrs = self._buffer_ptrs()
+        self._captured = self.dec.products.signature()
         return self
 
-    def _buffer_ptrs(self):
-        return tuple((None if t is None else (t.data_ptr(), t.dtype, tuple(t.shape)))
-                     for l in self.dec.layers for t in (l.proj_attn._vp, l.proj_attn._G))
-
     def _graph_operands(self):
-        keep = [self.ctx.cams, self.ctx.feat, getattr(self.ctx, "_buffer", None)]
+        keep = self.ctx.tensors() + self.dec.products.tensors()
         if self.post is not None:
             keep += self.post.tensors()
         for l in self.dec.layers:
-            keep += [l.proj_attn._vp, l.proj_attn._G]
-            for wc in (l._wc, l.proj_attn._wc):
-                keep += [entry[1] for entry in wc._store.values()]
-        return [t for t in keep if t is not None]
+            keep += l._wc.tensors() + l.proj_attn._wc.tensors()
+        return keep
 
     def refresh_weights(self):
         """after the decoder's parameters changed: cached operands are version-checked, the graph is re-captured"""
@@ -168,7 +157,7 @@ class GraphedDecoder:
 
     def replay(self):
         """one decoder forward on the loaded inputs; returns the graph's static output tensors (overwritten by the next replay)"""
-        if self.graph is None or self._buffer_ptrs() != self._captured_ptrs:
+        if self.graph is None or self.dec.products.signature() != self._captured:
             # never captured, or the decoder was run with other shapes / another dtype since (its per-layer buffers were
             # re-allocated): the old graph is still safe to replay (its buffers are pinned) but no longer the decoder's state
             self.capture()

@@ -211,19 +211,8 @@ class GraphedTrainStep:
     def set_cameras(self, meta):
         """new calibration / crop for the same number of images: refills the packed camera records in place (host packing + one
         small H2D copy) and, from them, the projection matrices the captured step reads; no re-capture"""
-        from . import geometry_torch as G
-        layer0 = self.head.decoder.layers[0]
-        fresh = DecoderContext.prepare(self.spatial_shapes, self.level_start_index, meta, layer0.img_size, self.ctx.dtype,
-                                       self.batch, self.dev)
-        if fresh.cams.shape != self.ctx.cams.shape:
-            raise RuntimeError("set_cameras: %s camera records, the runner was built for %s"
-                               % (tuple(fresh.cams.shape), tuple(self.ctx.cams.shape)))
+        self.ctx.set_cameras(meta, self.head.decoder.layers[0].img_size)
         with torch.no_grad():
-            self.ctx.cams.copy_(fresh.cams)
-            tc = getattr(self.ctx, "_train_cache", None)
-            if tc is not None:      # forward_autograd's per-context constants: same tensors, new values, stamped current
-                tc["Pm"].copy_(G.proj_matrices_from_records(self.ctx.cams, self.V, self.batch))
-                tc["key"] = (self.ctx.cams.data_ptr(), self.ctx.cams._version)
             for mine, m in zip(self.meta, meta):        # what the eager path may read from the meta dicts themselves
                 for k in ("camera", "center", "scale", "rotation"):
                     if k not in m or k not in mine:
@@ -297,12 +286,10 @@ class GraphedTrainStep:
         return self
 
     def _graph_operands(self):
-        keep = [self.ctx.cams, self.ctx.feat, getattr(self.ctx, "_buffer", None), getattr(self.ctx, "_train_ref", None)]
-        keep += [v for v in (getattr(self.ctx, "_train_cache", None) or {}).values() if torch.is_tensor(v)]
+        keep = self.ctx.tensors() + self.head.decoder.products.tensors()
         keep += self.src_views + [self.spatial_shapes, self.level_start_index]
         for layer in self.head.decoder.layers:
-            for wc in (layer._wc, layer.proj_attn._wc):
-                keep += [entry[1] for entry in wc._store.values()]
+            keep += layer._wc.tensors() + layer.proj_attn._wc.tensors()
             keep += list(layer.__dict__.get("_img_dev", {}).values())
         if self.operands is not None:
             keep += self.operands.tensors()

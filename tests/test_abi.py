@@ -239,24 +239,33 @@ def test_only_the_product_and_checker_libraries_ship():
 
 
 def test_deepcopy_of_a_decoder_does_not_copy_run_time_buffers():
-    """copy.deepcopy(decoder) (EMA / checkpoint copies): parameters are copied, the pooled fp32 (value, G) buffers, weight caches and
-    side-stream hand-offs are not; the copy's layers share ONE fresh pool again."""
+    """copy.deepcopy(decoder) (EMA / checkpoint copies): parameters are copied, the product buffers (ahead and inline pairs), their
+    ready state, weight caches and side-stream hand-offs are not; the copy's layers share ONE fresh, empty owner again --
+    by PyramidProducts.__deepcopy__ alone, without a __deepcopy__ on the modules."""
     import copy
+    from mvgformer_amd.decoder import DQDecoder
     from mvgformer_amd.factory import build_decoder_for_case
+    from mvgformer_amd.projattn import ProjAttn
     from mvgformer_amd.synthetic import build_case
     dec = build_decoder_for_case(build_case("cfg1", seed=0, layers=2), "cpu", torch.float32)
-    pa0 = dec.layers[0].proj_attn
-    pa0._f32_pool["slot"] = (torch.zeros(4), torch.zeros(4))
-    pa0._vp, pa0._G = torch.zeros(3), torch.zeros(3)
+    pa0, cpu = dec.layers[0].proj_attn, torch.device("cpu")
+    assert all(l.proj_attn.products is dec.products for l in dec.layers)
+    inline = dec.products.buffers(pa0, torch.float32, 1, 4, 256, cpu, ahead=False, stream=0)
+    ahead = dec.products.buffers(pa0, torch.float32, 1, 4, 256, cpu, ahead=True)
+    dec.products.produced([pa0], event=object())
+    assert len(dec.products.tensors()) == 4 and dec.products.pending() and inline[0] is not ahead[0]
     dec.layers[0]._run = None
     cp = copy.deepcopy(dec)
     assert all(l._run is None for l in cp.layers)
-    assert cp.layers[0].proj_attn._f32_pool == {} and cp.layers[0].proj_attn._f32_pool is cp.layers[1].proj_attn._f32_pool
-    assert cp.layers[0].proj_attn._f32_pool is not pa0._f32_pool and cp.layers[0].proj_attn._vp is None
+    assert cp.products.tensors() == [] and cp.products.signature() == () and not cp.products.pending()
+    assert all(l.proj_attn.products is cp.products for l in cp.layers) and cp.products is not dec.products
+    assert len(dec.products.tensors()) == 4 and dec.products.pending()         # the original keeps its own
     a, b = dec.state_dict(), cp.state_dict()
     assert list(a) == list(b) and all(torch.equal(a[k], b[k]) and a[k].data_ptr() != b[k].data_ptr() for k in a)
     single = copy.deepcopy(pa0)
-    assert single._f32_pool == {} and single._f32_pool is not pa0._f32_pool
+    assert single.products.tensors() == [] and not single.products.pending()
+    assert single.products is not dec.products and single.products is not cp.products
+    assert "__deepcopy__" not in vars(ProjAttn) and "__deepcopy__" not in vars(DQDecoder)
 
 
 def test_a_forward_that_raises_leaves_no_run_attached():

@@ -40,7 +40,7 @@ def _setup(dtype):
                 print("fp32: the case does not take the G form -- the pyramid products run inline")
         torch.cuda.synchronize()
 
-        def forward():
+        def forward(dec=dec):
             with torch.no_grad():
                 out = dec(gc.tgt, gc.reference_points, gc.src_views, gc.meta, gc.spatial_shapes, gc.level_start_index, None,
                           query_pos=gc.query_pos, threshold=0.1)
@@ -75,7 +75,36 @@ def test_forward_that_raises_leaves_no_state_behind(dtype, where):
         delattr(obj, name)
     torch.cuda.synchronize()
     assert all(l._run is None for l in dec.layers)
-    assert all(l.proj_attn._vp_event is None for l in dec.layers)
+    assert not dec.products.pending() and all(l.proj_attn.products is dec.products for l in dec.layers)
     got = forward()
     for x, y in zip(ref, got[:4]):
+        assert torch.equal(x, y)
+
+
+def test_fp32_ahead_products_never_alias_the_inline_pair():
+    """fp32 forwards with the products inline (ONE pair per stream for all layers), then ahead on the side stream (one pair per layer,
+    all alive at once), then inline again, on a decoder whose owner starts empty -- so the inline pair exists first and an ahead
+    buffer that reused it would be shared by both layers.  Each forward is bit-identical to the first of its kind, nothing is pending
+    afterwards, and the ahead buffers are other tensors than the inline pair, which survives them."""
+    import copy
+    dec0, forward, ref = _setup(torch.float32)
+    dec = copy.deepcopy(dec0)       # the same weights, a fresh and empty owner
+    assert dec.products.tensors() == [] and dec.overlap_pyramid and dec.overlap_pyramid_f32
+    outs, held = [], []
+    try:
+        for overlap in (False, True, False):
+            dec.overlap_pyramid = overlap
+            outs.append([t.clone() for t in forward(dec)[:4]])
+            assert not dec.products.pending()
+            held.append(dec.products.tensors())
+    finally:
+        dec.overlap_pyramid = True
+    inline, both = held[0], held[1]
+    assert len(inline) == 2 and len(both) == 2 + 2 * len(dec.layers)        # (the case takes the G-sampling form: there are products)
+    ids = lambda ts: {id(t) for t in ts}
+    assert ids(inline) < ids(both) and ids(held[2]) == ids(both)            # the pair survives; the third forward allocates nothing
+    assert len(ids(both)) == len(both) == len({t.data_ptr() for t in both})     # ahead buffers: other tensors, other memory
+    for x, y in zip(outs[0], outs[2]):
+        assert torch.equal(x, y)
+    for x, y in zip(ref, outs[1]):          # ahead is what the shared decoder's untouched forward ran
         assert torch.equal(x, y)

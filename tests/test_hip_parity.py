@@ -1300,7 +1300,8 @@ def test_side_stream_pyramid_projections_change_nothing():
                 torch.cuda.synchronize()
                 for x, y in zip(ref, got[:4]):
                     assert torch.equal(x, y)
-            assert all(l.proj_attn._vp_event is None for l in dec.layers)          # every event consumed / dropped
+            assert not dec.products.pending()                                      # every event consumed / dropped
+            assert all(l.proj_attn.products is dec.products for l in dec.layers)
             assert all(l._run is None for l in dec.layers)                         # no run attached: every hook fired / dropped
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):

@@ -58,7 +58,7 @@ def test_producer_in_place_pyramid_and_weight_refresh():
 
 
 def test_graph_survives_an_eager_call_with_other_shapes_on_the_same_decoder():
-    """the captured graph addresses ProjAttn._vp / _G and the cached operands by raw pointer.  An eager forward of
+    """the captured graph addresses the layers' value planes / G (PyramidProducts) and the cached operands by raw pointer.  An eager forward of
     the same decoder with another compute dtype / resolution re-allocates them; the runner pins what it captured and re-captures
     when the decoder has moved to other buffers -- results stay those of the eager forward."""
     from mvgformer_amd.factory import build_decoder_for_case, case_to_device
@@ -69,7 +69,12 @@ def test_graph_survives_an_eager_call_with_other_shapes_on_the_same_decoder():
     run.load(src_views=c.src_views, tgt=c.tgt, query_pos=c.query_pos, reference_points=c.reference_points)
     first = [t.clone() for t in run.replay()[:4]]
     held = [t.data_ptr() for t in run._pinned]
-    assert held and all(l.proj_attn._vp.data_ptr() in held for l in dec.layers)
+    feat = run.ctx.feat         # every layer's (value planes, G): what a forward of this shape is handed
+    planes = [dec.products.buffers(l.proj_attn, torch.bfloat16, *feat.shape, feat.device) for l in dec.layers]
+    sig = dec.products.signature()
+    assert sig == run._captured and len(sig) == 2 * len(dec.layers)                  # ... which allocated nothing
+    assert held and all(vp.data_ptr() in held and G.data_ptr() in held for vp, G in planes)
+    assert len({vp.data_ptr() for vp, _ in planes}) == len(dec.layers) and all(vp.shape[1:] == (8, run.ctx.levels.S, 32) for vp, _ in planes)
     # another scene through the same decoder object: other map shapes -> the per-layer buffers are re-allocated
     small = [s[:, :, : s.shape[2] // 2, :].contiguous() for s in c.src_views]
     shapes = torch.tensor([[s.shape[2], s.shape[3]] for s in small], dtype=torch.long, device=DEV)
@@ -78,7 +83,7 @@ def test_graph_survives_an_eager_call_with_other_shapes_on_the_same_decoder():
         dec(c.tgt, c.reference_points, small, c.meta, shapes, starts, None, query_pos=c.query_pos, threshold=0.1)
         junk = [torch.full((1 << 22,), 7.0, device=DEV) for _ in range(8)]      # recycle whatever was freed
     torch.cuda.synchronize()
-    assert run._buffer_ptrs() != run._captured_ptrs
+    assert dec.products.signature() != run._captured
     again = [t.clone() for t in run.replay()[:4]]
     del junk
     assert all(torch.equal(x, y) for x, y in zip(first, again))
