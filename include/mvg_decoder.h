@@ -657,6 +657,8 @@ size_t mvg_pose_nms_workspace(int B, int N, int J);
  *   close[a, c] = #{ j : sqrt((dx^2 + dy^2) + dz^2) < limit_a } > num_nearby_joints_thr in fp64 from the fp32 inputs, every
  *   multiply and add rounded on its own, correctly rounded sqrt: numpy's arithmetic, so the matrix is the reference's bit for bit
  *   (not symmetric: the limit belongs to the row pose; a NaN coordinate gives a NaN limit as np.max / np.min do).
+ *   Caveat: as built, dy^2 and dz^2 enter their sums unrounded (fused multiply-add; csrc/exact_dev.h, CONTRACTION), which is the
+ *   same value while those squares are exact in fp64, i.e. while a coordinate difference has at most 26 significant bits.
  *   Greedy pass in visiting order = descending score, among equal scores the HIGHER row first
  *   (np.argsort(scores, kind="stable")[::-1]; the reference's default argsort is unstable, its order among tied scores is
  *   unspecified and coincides with this rule where numpy falls back to insertion sort, N <= 16): a candidate that is already
@@ -691,7 +693,8 @@ int mvg_pose_nms(const float* pred, int B, int N, int J, double dist_thr, int nu
  *   joints_3d (B, Gmax, J, 3) fp32, joints_3d_vis (B, Gmax, J) fp32 (visible iff > 0), num_person (B) int32 (clamped to [0, Gmax]).
  *   An element with num_person == 0 appends nothing and adds nothing to total_gt.  Every other element appends, per participating
  *   row in row order, mean_g = sum_j (dist(row_j, gt_g_j) * w_j) / sum_j w_j (w = 1 for a visible joint, else 0; fp64 from the fp32
- *   inputs, (dx^2 + dy^2) + dz^2, correctly rounded sqrt, joints in order; 0 / 0 = NaN for a person without visible joint) for
+ *   inputs, (dx^2 + dy^2) + dz^2, correctly rounded sqrt, joints in order; 0 / 0 = NaN for a person without visible joint; the
+ *   caveat of mvg_pose_nms on dy^2 and dz^2 holds for every distance of this call and of mvg_eval_pcp) for
  *   every g < num_person, takes the FIRST minimum over g with NaN ordered as +inf, and writes mpjpe = that mean as computed,
  *   score = the row's score, gt_id = total_gt before this element + g.  Entries go to mpjpe / score / gt_id (capacity each) at the
  *   cursor state[0], elements in batch order; an entry at or past `capacity` is not written.  After every element has read the
@@ -758,7 +761,8 @@ int mvg_linear_assignment(const double* cost, const int* n, const int* m, int B,
  *   Track state, owned by the caller: id (B, T) int32 (-1 = free slot), hits, misses (B, T) int32, born (B, T) int64 (the frame
  *   number), score (B, T) fp32, pose (B, T, J, 3) fp32, next_id (B) int32, state (MVG_TRACK_STATE_WORDS) int64.
  *   Per element: (1) the active tracks are the slots with id >= 0, in slot order.  (2) c[t, d] = (sum over joints in order of
- *   sqrt((dx*dx + dy*dy) + dz*dz)) / J in fp64 from the fp32 inputs, correctly rounded sqrt.  (3) c'[t, d] = c[t, d] if
+ *   sqrt((dx*dx + dy*dy) + dz*dz)) / J in fp64 from the fp32 inputs, correctly rounded sqrt (with the caveat of mvg_pose_nms:
+ *   dy*dy and dz*dz are fused into their sums; mvg_track_eval rounds every product on its own).  (3) c'[t, d] = c[t, d] if
  *   c[t, d] <= max_dist, else max_dist (also for NaN).  (4) the solver of mvg_linear_assignment on c', active tracks as rows,
  *   detections as columns: every non-match pays max_dist through the zero padding, the matching is the global optimum.  (5) an
  *   assigned pair is a match iff the ungated c[t, d] <= max_dist.  (6) a matched track takes the detection's pose (bit for bit)

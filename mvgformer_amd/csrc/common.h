@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <initializer_list>
+
 #include "../../include/mvg_decoder.h"
 
 #define MVG_WAVE 64
@@ -103,3 +105,16 @@ static inline int mvg_fill_levels(LevelTable* t, const int64_t* shapes_host, con
   } while (0)
 
 static inline int mvg_ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
+
+// Argument checks of the entry points: a required pointer that is null / a pointer that is not a multiple of `bytes` (a power of
+// two).  A null pointer is aligned, so an optional argument can stand in the second list as it is.
+static inline bool mvg_any_null(std::initializer_list<const void*> ptrs) {
+  for (const void* p : ptrs)
+    if (p == nullptr) return true;
+  return false;
+}
+static inline bool mvg_any_misaligned(unsigned bytes, std::initializer_list<const void*> ptrs) {
+  uintptr_t bits = 0;
+  for (const void* p : ptrs) bits |= (uintptr_t)p;
+  return (bits & (bytes - 1)) != 0;
+}

@@ -16,7 +16,7 @@
 // kernels are templates on MAPPED: the instantiation without a map (Jp == Jc, identity) is the code as it was before the map.
 #include <math.h>
 
-#include "common.h"
+#include "exact_dev.h"
 #include "match_dev.h"
 
 #define CRIT_THREADS MATCH_THREADS
@@ -184,19 +184,6 @@ __global__ __launch_bounds__(CRIT_THREADS) void crit_project_gt_kernel(const flo
   const float* A = cams + 21;                                    // record 0: view 0, batch element 0
   gt2d[idx * 2] = A[0] * u + A[1] * w + A[2];
   gt2d[idx * 2 + 1] = A[3] * u + A[4] * w + A[5];
-}
-
-// fixed-order sum over the workgroup; the result is valid in thread 0
-__device__ __forceinline__ double block_sum(double v, double* scratch) {
-#pragma unroll
-  for (int d = 1; d < MVG_WAVE; d <<= 1) v += __shfl_xor(v, d, MVG_WAVE);
-  __syncthreads();
-  if ((threadIdx.x & (MVG_WAVE - 1)) == 0) scratch[threadIdx.x / MVG_WAVE] = v;
-  __syncthreads();
-  double s = 0.0;
-  if (threadIdx.x == 0)
-    for (int w = 0; w < CRIT_WAVES; ++w) s += scratch[w];
-  return s;
 }
 
 struct CritArgs {
@@ -379,9 +366,9 @@ __global__ __launch_bounds__(CRIT_THREADS) void crit_layer_kernel(CritArgs a) {
       if (!s_named[(int)((e >> 1) % Jp)]) gp2[e] = 0.f;
 
   double* out = a.part + ((long)l * B + b) * CRIT_PART;
-  const double r0 = block_sum(s_ce, s_red), r1 = block_sum(s_3d, s_red), r2 = block_sum(s_2d, s_red);
-  const double r3 = block_sum((double)n_ok, s_red), r4 = block_sum((double)n_rec, s_red), r5 = block_sum((double)n_pos, s_red);
-  const double r6 = block_sum((double)n_tp, s_red), r7 = block_sum((double)n_card, s_red);
+  const auto sum = [&](double v) { return block_sum<CRIT_WAVES>(v, s_red); };      // exact_dev.h; valid in thread 0
+  const double r0 = sum(s_ce), r1 = sum(s_3d), r2 = sum(s_2d), r3 = sum((double)n_ok), r4 = sum((double)n_rec);
+  const double r5 = sum((double)n_pos), r6 = sum((double)n_tp), r7 = sum((double)n_card);
   if (tid == 0) {
     out[0] = r0; out[1] = r1; out[2] = r2; out[3] = r3; out[4] = r4; out[5] = r5; out[6] = r6; out[7] = r7;
   }
@@ -432,7 +419,7 @@ int mvg_knn_match_jm(const float* poses, const float* joints_3d, const void* num
                      const float* space_size, const float* space_center, int method, int K, float value, int B, int NQ, int Gmax,
                      int Jp, int Jc, const int* joint_map, int Pmax, void* workspace, size_t workspace_bytes, int* pair_query,
                      int* pair_gt, int* pair_count, uint8_t* matched, void* stream) {
-  if (!poses || !joints_3d || !num_person || !space_size || !space_center || !pair_query || !pair_gt || !pair_count || !matched)
+  if (mvg_any_null({poses, joints_3d, num_person, space_size, space_center, pair_query, pair_gt, pair_count, matched}))
     return MVG_E_BADARG;
   JointMap map;
   if (B < 1 || NQ < 1 || Gmax < 1 || Gmax > 64 || !pack_joint_map(Jp, Jc, joint_map, &map)) return MVG_E_BADARG;
@@ -483,14 +470,15 @@ int mvg_criterion_jm(const float* logits, const float* poses, const float* poses
                      void* workspace, size_t workspace_bytes, float* table, float* grad_logits, float* grad_poses,
                      float* grad_poses_2d, void* stream) {
   const int J = Jc;
-  if (!logits || !poses || !poses_2d || !pair_query || !pair_gt || !pair_count || !joints_3d || !joints_3d_vis || !joints_vis ||
-      !num_person || !cams || !space_size || !space_center || !workspace || !table || !grad_logits || !grad_poses || !grad_poses_2d)
+  if (mvg_any_null({logits, poses, poses_2d, pair_query, pair_gt, pair_count, joints_3d, joints_3d_vis, joints_vis, num_person,
+                    cams, space_size, space_center, workspace, table, grad_logits, grad_poses, grad_poses_2d}))
     return MVG_E_BADARG;
   CritArgs a;
   if (L < 1 || B < 1 || B > CRIT_MAX_B || NQ < 1 || NQ > CRIT_MAX_NQ || !pack_joint_map(Jp, Jc, joint_map, &a.map) || V < 1 ||
       Gmax < 1 || Gmax > 64 || Pmax < 1 || Pmax > CRIT_MAX_PAIRS)
     return MVG_E_BADARG;
-  if (workspace_bytes < mvg_criterion_workspace(L, B, Gmax, V, J) || ((uintptr_t)workspace & 7)) return MVG_E_BADARG;
+  if (workspace_bytes < mvg_criterion_workspace(L, B, Gmax, V, J)) return MVG_E_BADARG;
+  if (mvg_any_misaligned(8, {workspace})) return MVG_E_BADARG;
   a.logits = logits; a.poses = poses; a.poses_2d = poses_2d;
   a.pair_query = pair_query; a.pair_gt = pair_gt; a.pair_count = pair_count;
   a.gt = joints_3d; a.vis3d = joints_3d_vis; a.vis2d = joints_vis;

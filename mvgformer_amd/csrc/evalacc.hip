@@ -14,41 +14,29 @@
 //   mvg_eval_pcp     1 launch, one workgroup: elements and actors in order, threads over the rows; every counter has this one
 //                    writer (thread 0).
 //
-// Arithmetic: fp64 from the fp32 inputs, every multiply and add rounded on its own ((x^2 + y^2) + z^2, correctly rounded sqrt),
-// joints summed in joint order: this file switches contraction off like nms.hip.  The only atomics are integer adds in LDS; no
-// result depends on the order in which workgroups or wavefronts run, so two runs give the same bits.
+// Arithmetic: fp64 from the fp32 inputs, sqrt((x^2 + y^2) + z^2) with a correctly rounded sqrt, joints summed in joint order.
+// The distances are dist3 / norm3 of exact_dev.h, the FUSED form: see CONTRACTION there for when that is the rounding of every
+// operation on its own.  The only atomics are integer adds in LDS; no result depends on the order in which workgroups or
+// wavefronts run, so two runs give the same bits.
 #include <math.h>
 
-#include "common.h"
-
-#pragma clang fp contract(off)
+#include "exact_dev.h"
 
 #define EVAL_THREADS 256
+static_assert(EVAL_THREADS == SCAN_THREADS, "eval_match_kernel calls scan_rows; the other kernels only share the constant");
 #define EVAL_MAX_R MVG_EVAL_MAX_R
 #define EVAL_MAX_J MVG_EVAL_MAX_J
 
-typedef long long i64;
-
 enum { ST_ENTRIES = 0, ST_TOTAL_GT = 1, ST_FRAMES = 2, ST_OVERFLOW = 3, ST_KEPT_ROWS = 4, ST_MATCH_GT = 5, ST_EMPTY_FRAME = 6 };
 
-static __device__ __forceinline__ int eval_clamp(int v, int hi) { return min(max(v, 0), hi); }
-// rows of element b that can take part: all R, or the first count[b, 0] of them
-static __device__ __forceinline__ int eval_rows(const int* count, int b, int R) { return count == nullptr ? R : eval_clamp(count[2 * b], R); }
-static __device__ __forceinline__ bool eval_takes_part(const float* dets, int b, int i, int R, int J) {
-  return dets[((size_t)b * R + i) * J * 5 + 3] >= 0.f;
-}
-static __device__ __forceinline__ double eval_dist(const float* p, const float* g) {
-  const double dx = (double)p[0] - (double)g[0], dy = (double)p[1] - (double)g[1], dz = (double)p[2] - (double)g[2];
-  return __builtin_sqrt((dx * dx + dy * dy) + dz * dz);
-}
 // NaN is ordered last in the comparisons (evaluate._nan_last); the stored value stays what it is
 static __device__ __forceinline__ double eval_nan_last(double v) { return v != v ? (double)INFINITY : v; }
 
 // participating rows of element b, counted by the whole workgroup into *s_acc (LDS, zeroed by the caller, barrier after)
 static __device__ __forceinline__ void eval_count_rows(const float* dets, const int* count, int b, int R, int J, int* s_acc) {
-  const int rows = eval_rows(count, b, R);
+  const int rows = det_rows(count, b, R);
   int mine = 0;
-  for (int i = threadIdx.x; i < rows; i += EVAL_THREADS) mine += eval_takes_part(dets, b, i, R, J) ? 1 : 0;
+  for (int i = threadIdx.x; i < rows; i += EVAL_THREADS) mine += det_flag(dets, b, i, R, J) ? 1 : 0;
   if (mine) atomicAdd(s_acc, mine);
 }
 
@@ -60,37 +48,27 @@ __global__ __launch_bounds__(EVAL_THREADS) void eval_match_kernel(const float* _
                                                                   double* __restrict__ mpjpe, double* __restrict__ score,
                                                                   i64* __restrict__ gt_id, i64 capacity, const i64* __restrict__ state) {
   __shared__ int s_pos[EVAL_MAX_R];           // position of a participating row inside its element, -1 for the others
-  __shared__ int s_scan[2][EVAL_THREADS];
+  __shared__ int s_scan[2][1][SCAN_THREADS];
   __shared__ int s_before;                    // entries of the elements in front of this one
   const int b = blockIdx.x, t = threadIdx.x;
-  const int G = eval_clamp(num_person[b], Gmax);
+  const int G = clamp_count(num_person[b], Gmax);
   if (G == 0) return;                          // panoptic.py:508: no entry, nothing added to total_gt (uniform for the workgroup)
   if (t == 0) s_before = 0;
   __syncthreads();
   i64 gt_before = 0;
   for (int e = 0; e < b; ++e) {
-    const int Ge = eval_clamp(num_person[e], Gmax);
+    const int Ge = clamp_count(num_person[e], Gmax);
     if (Ge == 0) continue;
     gt_before += Ge;
     eval_count_rows(dets, count, e, R, J, &s_before);
   }
-  // exclusive scan of the flags: every thread owns a run of consecutive rows, the run totals go through an LDS scan
-  const int rows = eval_rows(count, b, R);
-  const int chunk = (R + EVAL_THREADS - 1) / EVAL_THREADS;
-  const int lo = min(t * chunk, R), hi = min(lo + chunk, R);
-  int mine = 0;
-  for (int i = lo; i < hi; ++i) mine += (i < rows && eval_takes_part(dets, b, i, R, J)) ? 1 : 0;
-  s_scan[0][t] = mine;
-  __syncthreads();
-  int src = 0;
-  for (int step = 1; step < EVAL_THREADS; step <<= 1) {
-    s_scan[src ^ 1][t] = s_scan[src][t] + (t >= step ? s_scan[src][t - step] : 0);
-    src ^= 1;
-    __syncthreads();
-  }
-  int pos = s_scan[src][t] - mine;
-  for (int i = lo; i < hi; ++i) {
-    const bool in = i < rows && eval_takes_part(dets, b, i, R, J);
+  // the position of every participating row among those of the element
+  const int rows = det_rows(count, b, R);
+  const auto takes_part = [=](int i) { return i < rows && det_flag(dets, b, i, R, J); };
+  const RowScan<1> run = scan_rows<1>(R, s_scan, [=](int i, int* n) { n[0] += takes_part(i) ? 1 : 0; });
+  int pos = run.before(0);
+  for (int i = run.lo; i < run.hi; ++i) {
+    const bool in = takes_part(i);
     s_pos[i] = in ? pos : -1;
     pos += in ? 1 : 0;
   }
@@ -111,7 +89,7 @@ __global__ __launch_bounds__(EVAL_THREADS) void eval_match_kernel(const float* _
       double sum = 0.0, w_sum = 0.0;
       for (int j = 0; j < J; ++j) {
         const double w = v0[g * J + j] > 0.f ? 1.0 : 0.0;
-        sum += eval_dist(p + j * 5, g0 + (g * J + j) * 3) * w;
+        sum += dist3(p + j * 5, g0 + (g * J + j) * 3) * w;
         w_sum += w;
       }
       const double m = sum / w_sum, cmp = eval_nan_last(m);
@@ -136,7 +114,7 @@ __global__ __launch_bounds__(EVAL_THREADS) void eval_advance_kernel(const float*
   __syncthreads();
   i64 gts = 0;
   for (int b = 0; b < B; ++b) {
-    const int G = eval_clamp(num_person[b], Gmax);
+    const int G = clamp_count(num_person[b], Gmax);
     gts += G;
     eval_count_rows(dets, count, b, R, J, &s_acc[1]);
     if (G > 0) eval_count_rows(dets, count, b, R, J, &s_acc[0]);
@@ -157,8 +135,6 @@ __global__ __launch_bounds__(EVAL_THREADS) void eval_advance_kernel(const float*
 __constant__ int c_limb_a[9] = {0, 1, 3, 4, 6, 7, 9, 10, 12};
 __constant__ int c_limb_b[9] = {1, 2, 4, 5, 7, 8, 10, 11, 13};
 
-static __device__ __forceinline__ double eval_norm3(double x, double y, double z) { return __builtin_sqrt((x * x + y * y) + z * z); }
-
 __global__ __launch_bounds__(EVAL_THREADS) void eval_pcp_kernel(const float* __restrict__ dets, const int* __restrict__ count,
                                                                 const float* __restrict__ gt, const float* __restrict__ vis,
                                                                 const int* __restrict__ num_person, int B, int R, int J, int Gmax, int A,
@@ -176,10 +152,10 @@ __global__ __launch_bounds__(EVAL_THREADS) void eval_pcp_kernel(const float* __r
   for (int b = 0; b < B; ++b) {
     if (t == 0) s_n = 0;
     __syncthreads();
-    const int rows = eval_rows(count, b, R);
+    const int rows = det_rows(count, b, R);
     int mine = 0;
     for (int i = t; i < R; i += EVAL_THREADS) {
-      const bool in = i < rows && eval_takes_part(dets, b, i, R, J);
+      const bool in = i < rows && det_flag(dets, b, i, R, J);
       s_part[i] = in ? 1 : 0;
       mine += in ? 1 : 0;
     }
@@ -187,7 +163,7 @@ __global__ __launch_bounds__(EVAL_THREADS) void eval_pcp_kernel(const float* __r
     __syncthreads();
     const int n = s_n;
     kept += n;
-    const int actors = min(eval_clamp(num_person[b], Gmax), A);
+    const int actors = min(clamp_count(num_person[b], Gmax), A);
     for (int a = 0; a < actors; ++a) {
       const float* g = gt + ((size_t)b * Gmax + a) * J * 3;
       const float* v = vis + ((size_t)b * Gmax + a) * J;
@@ -209,7 +185,7 @@ __global__ __launch_bounds__(EVAL_THREADS) void eval_pcp_kernel(const float* __r
         if (!s_part[i]) continue;
         const float* p = dets + ((size_t)b * R + i) * J * 5;
         double sum = 0.0;
-        for (int j = 0; j < J; ++j) sum += eval_dist(g + j * 3, p + j * 5);
+        for (int j = 0; j < J; ++j) sum += dist3(g + j * 3, p + j * 5);
         const double m = sum / (double)J, cmp = eval_nan_last(m);
         if (my_row == R || cmp < my_cmp) {                     // rows of a thread ascend: the first minimum stays
           my_cmp = cmp;
@@ -241,8 +217,8 @@ __global__ __launch_bounds__(EVAL_THREADS) void eval_pcp_kernel(const float* __r
         int ok_all = 0;
         for (int k = 0; k < 9; ++k) {
           const int ja = c_limb_a[k], jb = c_limb_b[k];
-          const double e_s = eval_dist(p + ja * 5, g + ja * 3), e_e = eval_dist(p + jb * 5, g + jb * 3);
-          const double len = eval_dist(g + ja * 3, g + jb * 3);
+          const double e_s = dist3(p + ja * 5, g + ja * 3), e_e = dist3(p + jb * 5, g + jb * 3);
+          const double len = dist3(g + ja * 3, g + jb * 3);
           const int ok = ((e_s + e_e) / 2.0 <= alpha * len) ? 1 : 0;
           bone_correct[a * 10 + k] += ok;
           ok_all += ok;
@@ -252,9 +228,9 @@ __global__ __launch_bounds__(EVAL_THREADS) void eval_pcp_kernel(const float* __r
           ph[c] = ((double)p[2 * 5 + c] + (double)p[3 * 5 + c]) / 2.0;
           gh[c] = ((double)g[2 * 3 + c] + (double)g[3 * 3 + c]) / 2.0;
         }
-        const double e_hip = eval_norm3(ph[0] - gh[0], ph[1] - gh[1], ph[2] - gh[2]);
-        const double e_head = eval_dist(p + 12 * 5, g + 12 * 3);
-        const double len = eval_norm3(gh[0] - (double)g[12 * 3], gh[1] - (double)g[12 * 3 + 1], gh[2] - (double)g[12 * 3 + 2]);
+        const double e_hip = norm3(ph[0] - gh[0], ph[1] - gh[1], ph[2] - gh[2]);
+        const double e_head = dist3(p + 12 * 5, g + 12 * 3);
+        const double len = norm3(gh[0] - (double)g[12 * 3], gh[1] - (double)g[12 * 3 + 1], gh[2] - (double)g[12 * 3 + 2]);
         const int ok = ((e_hip + e_head) / 2.0 <= alpha * len) ? 1 : 0;
         bone_correct[a * 10 + 9] += ok;
         correct[a] += ok_all + ok;
@@ -280,9 +256,8 @@ int mvg_eval_match(const float* dets, const int* count, const float* joints_3d, 
                    int R, int J, int Gmax, double* mpjpe, double* score, int64_t* gt_id, int64_t capacity, int64_t* state,
                    void* stream) {
   if (eval_bad_shape(B, R, J, Gmax) || capacity < 1) return MVG_E_BADARG;
-  if (dets == nullptr || joints_3d == nullptr || joints_3d_vis == nullptr || num_person == nullptr) return MVG_E_BADARG;
-  if (mpjpe == nullptr || score == nullptr || gt_id == nullptr || state == nullptr) return MVG_E_BADARG;
-  if (((uintptr_t)mpjpe & 7) || ((uintptr_t)score & 7) || ((uintptr_t)gt_id & 7) || ((uintptr_t)state & 7)) return MVG_E_BADARG;
+  if (mvg_any_null({dets, joints_3d, joints_3d_vis, num_person, mpjpe, score, gt_id, state})) return MVG_E_BADARG;
+  if (mvg_any_misaligned(8, {mpjpe, score, gt_id, state})) return MVG_E_BADARG;
   hipLaunchKernelGGL(eval_match_kernel, dim3(B), dim3(EVAL_THREADS), 0, (hipStream_t)stream, dets, count, joints_3d, joints_3d_vis,
                      num_person, R, J, Gmax, mpjpe, score, (i64*)gt_id, (i64)capacity, (const i64*)state);
   MVG_LAUNCH_CHECK();
@@ -297,9 +272,8 @@ int mvg_eval_pcp(const float* dets, const int* count, const float* joints_3d, co
                  int64_t* bone_correct, int64_t* state, void* stream) {
   if (eval_bad_shape(B, R, J, Gmax) || J != 14 || actors < 1 || actors > MVG_EVAL_MAX_G) return MVG_E_BADARG;
   if (!(alpha >= 0.0) || recall_threshold != recall_threshold) return MVG_E_BADARG;
-  if (dets == nullptr || joints_3d == nullptr || joints_3d_vis == nullptr || num_person == nullptr) return MVG_E_BADARG;
-  if (correct == nullptr || total == nullptr || bone_correct == nullptr || state == nullptr) return MVG_E_BADARG;
-  if (((uintptr_t)correct & 7) || ((uintptr_t)total & 7) || ((uintptr_t)bone_correct & 7) || ((uintptr_t)state & 7)) return MVG_E_BADARG;
+  if (mvg_any_null({dets, joints_3d, joints_3d_vis, num_person, correct, total, bone_correct, state})) return MVG_E_BADARG;
+  if (mvg_any_misaligned(8, {correct, total, bone_correct, state})) return MVG_E_BADARG;
   hipLaunchKernelGGL(eval_pcp_kernel, dim3(1), dim3(EVAL_THREADS), 0, (hipStream_t)stream, dets, count, joints_3d, joints_3d_vis,
                      num_person, B, R, J, Gmax, actors, recall_threshold, alpha, (i64*)correct, (i64*)total, (i64*)bone_correct,
                      (i64*)state);

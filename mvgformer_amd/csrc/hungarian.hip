@@ -18,15 +18,12 @@
 // u[r] has one writer per step: the lane of the used column whose row is r, thread 0 for the row being inserted.  The path is
 // flipped by thread 0 in LDS.  Every loop is counted (a search of row i takes at most i + 1 steps): no input can make it spin.
 //
-// Arithmetic: fp64, every operation rounded on its own.  The library is built with -ffp-contract=fast: a product that feeds an
-// add goes through hg_mul, whose empty asm statement the compiler cannot fuse across (as track.hip does).  No floating-point
-// atomics, no atomics at all: two runs give the same bits.
+// Arithmetic: fp64, every operation rounded on its own: a product that feeds an add goes through f64_mul (CONTRACTION in
+// exact_dev.h).  No floating-point atomics, no atomics at all: two runs give the same bits.
 #include <math.h>
 
-#include "common.h"
+#include "exact_dev.h"
 #include "match_dev.h"
-
-#pragma clang fp contract(off)
 
 #define HG_THREADS MATCH_THREADS
 #define HG_WAVES (HG_THREADS / MVG_WAVE)
@@ -53,12 +50,6 @@ struct HgArgs {
   JointMap map;
 };
 
-static __device__ __forceinline__ double hg_mul(double a, double b) {
-  double p = a * b;
-  asm volatile("" : "+v"(p));
-  return p;
-}
-
 // (k, q, d) <- the smaller of (k, q) and (ok, oq) in the order (value, then column), with its raw minv d
 static __device__ __forceinline__ void hg_take(double& k, int& q, double& d, double ok, int oq, double od) {
   if (ok < k || (ok == k && oq < q)) {
@@ -82,8 +73,7 @@ __global__ __launch_bounds__(HG_THREADS) void hungarian_match_kernel(HgArgs a) {
   const int p = blockIdx.x, b = p % a.B, tid = threadIdx.x, lane = tid & (MVG_WAVE - 1), wave = tid / MVG_WAVE;
   const int NQ = a.NQ, Gmax = a.Gmax, J = a.J;
   if (MAPPED && tid < J) s_map3[tid] = 3 * (int)a.map.m[tid];    // visible after the first barrier of the cost loop
-  const long Gl = load_count(a.num_person, a.np_is64, b);
-  const int G = (int)(Gl < 0 ? 0 : (Gl > Gmax ? Gmax : Gl));
+  const int G = clamp_count(load_count(a.num_person, a.np_is64, b), Gmax);
   float* cost = ((long)NQ * Gmax <= HG_LDS_COSTS) ? cost_lds : a.cost_ws + (long)p * NQ * Gmax;
   const float* pb = a.poses + (long)p * NQ * (MAPPED ? a.Jp : J) * 3;
   const float* gb = a.gt + (long)b * Gmax * J * 3;
@@ -107,9 +97,9 @@ __global__ __launch_bounds__(HG_THREADS) void hungarian_match_kernel(HgArgs a) {
         const double x = a.logits ? (double)a.logits[((long)p * NQ + q) * 2 + 1] : 1.0;
         const double pr = 1.0 / (1.0 + exp(-x));
         const double om = 1.0 - pr;
-        const double pos = hg_mul(hg_mul(0.25, hg_mul(om, om)), -log(pr + 1e-8));
-        const double neg = hg_mul(hg_mul(0.75, hg_mul(pr, pr)), -log(om + 1e-8));
-        cw[k] = hg_mul(a.cost_class, pos - neg);
+        const double pos = f64_mul(f64_mul(0.25, f64_mul(om, om)), -log(pr + 1e-8));
+        const double neg = f64_mul(f64_mul(0.75, f64_mul(pr, pr)), -log(om + 1e-8));
+        cw[k] = f64_mul(a.cost_class, pos - neg);
       }
     }
   }
@@ -136,7 +126,7 @@ __global__ __launch_bounds__(HG_THREADS) void hungarian_match_kernel(HgArgs a) {
         const int q = k * HG_THREADS + tid;
         if (q < NQ && !((used >> k) & 1u)) {
           const double pc = (double)cost[(long)i0 * NQ + q];
-          double c = dis ? pc : hg_mul(a.cost_pose, pc) + cw[k];
+          double c = dis ? pc : f64_mul(a.cost_pose, pc) + cw[k];
           if (!(c <= MVG_LAP_BIG)) c = MVG_LAP_BIG;              // NaN or above
           const double cur = (c - ui0) - v[k];
           if (cur < minv[k]) {
@@ -246,16 +236,16 @@ int mvg_hungarian_match(const float* logits, const float* poses, const float* jo
                         float cost_pose, int P, int B, int NQ, int Gmax, int Jp, int Jc, const int* joint_map, void* workspace,
                         size_t workspace_bytes, int* pair_query, int* pair_gt, int* pair_count, uint8_t* matched, double* duals,
                         void* stream) {
-  if (!poses || !joints_3d || !num_person || !space_size || !space_center || !pair_query || !pair_gt || !pair_count || !matched)
+  if (mvg_any_null({poses, joints_3d, num_person, space_size, space_center, pair_query, pair_gt, pair_count, matched}))
     return MVG_E_BADARG;
   if (method != MVG_MATCH_HUNGARIAN && method != MVG_MATCH_HUNGARIAN_DIS) return MVG_E_BADARG;
   HgArgs a;
   if (B < 1 || P < 1 || P % B != 0 || Gmax < 1 || Gmax > MVG_HUNGARIAN_MAX_G || NQ < Gmax || NQ > MVG_HUNGARIAN_MAX_NQ ||
       !pack_joint_map(Jp, Jc, joint_map, &a.map))
     return MVG_E_BADARG;
-  if (duals && ((uintptr_t)duals & 7)) return MVG_E_BADARG;
+  if (mvg_any_misaligned(8, {duals})) return MVG_E_BADARG;       // optional
   const size_t need = mvg_hungarian_match_workspace(P, NQ, Gmax);
-  if (need && (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 3))) return MVG_E_BADARG;
+  if (need && (!workspace || workspace_bytes < need || mvg_any_misaligned(4, {workspace}))) return MVG_E_BADARG;
   a.logits = logits; a.poses = poses; a.gt = joints_3d; a.num_person = num_person;
   a.cost_ws = (float*)workspace;
   a.pair_query = pair_query; a.pair_gt = pair_gt; a.pair_count = pair_count; a.matched = matched; a.duals = duals;

@@ -11,16 +11,13 @@
 //     (C) nms_greedy_kernel  one workgroup per batch element; wavefront 0 runs the greedy pass (lane w owns word w of the ignored
 //                            mask and of the current row), then all wavefronts apply max_dets and write keep / count / dets
 //
-// Arithmetic of the closeness test: fp64 from the fp32 inputs, every multiply and add rounded on its own in numpy's order
-// ((x^2 + y^2) + z^2, correctly rounded sqrt), so the boolean matrix is the reference's bit for bit.  The library is built with
-// -ffp-contract=fast; this file switches contraction off (the __dmul_rn / __dadd_rn forms are plain operators that
-// inherit the command line's mode, so they are not used).  No floating-point atomics, no data-dependent loop bound other than
-// the candidate count, which every kernel clamps to N.
+// Arithmetic of the closeness test: fp64 from the fp32 inputs in numpy's order, sqrt((x^2 + y^2) + z^2) with a correctly rounded
+// sqrt.  The diagonal and the distances are norm3 of exact_dev.h, the FUSED form: the boolean matrix is the reference's bit for
+// bit under the input condition that CONTRACTION there states.  No floating-point atomics, no data-dependent loop bound other
+// than the candidate count, which every kernel clamps to N.
 #include <math.h>
 
-#include "common.h"
-
-#pragma clang fp contract(off)
+#include "exact_dev.h"
 
 #define NMS_MAX_N MVG_NMS_MAX_N             // 2048: 32 words of 64 candidates: one lane per word in the greedy pass
 #define NMS_MAX_J MVG_NMS_MAX_J
@@ -30,8 +27,6 @@
 #define NMS_GREEDY_THREADS 256
 #define NMS_PREFETCH 8                      // rows of `close` the greedy pass loads ahead of their use
 #define NMS_HEADER 16                       // bytes in front of the per-element arrays: int32 candidate count
-
-typedef unsigned long long u64;
 
 // workspace of one batch element (8-byte aligned pieces, doubles and words first)
 struct NmsWorkspace {
@@ -62,7 +57,7 @@ static __device__ __forceinline__ NmsWorkspace nms_workspace(void* base, int b, 
   w.key = (unsigned*)(w.group_last + n_even);
   return w;
 }
-static __device__ __forceinline__ int nms_candidates(const NmsWorkspace& w, int N) { return min(max(w.header[0], 0), N); }
+static __device__ __forceinline__ int nms_candidates(const NmsWorkspace& w, int N) { return clamp_count(w.header[0], N); }
 
 // Total order on the scores that agrees with numpy's: -0 == +0, every NaN equal and above +inf (np.argsort puts NaN last, np.argmax
 // returns the first NaN).
@@ -118,7 +113,7 @@ __global__ __launch_bounds__(NMS_RANK_THREADS) void nms_rank_kernel(const float*
         hi[c] = fmaxf(hi[c], v);
       }
     const double sx = (double)hi[0] - (double)lo[0], sy = (double)hi[1] - (double)lo[1], sz = (double)hi[2] - (double)lo[2];
-    const double diag = __builtin_sqrt((sx * sx + sy * sy) + sz * sz);
+    const double diag = norm3(sx, sy, sz);
     ws.limit[before] = nan ? (double)NAN : diag * dist_thr;
     ws.rank2row[before] = n;
     ws.group_last[before] = before + equal_below;
@@ -160,8 +155,7 @@ __global__ __launch_bounds__(NMS_CLOSE_THREADS) void nms_close_kernel(const floa
       const double dx = (double)ra[3 * j] - (double)s_col[(3 * j) * NMS_TILE + lane];
       const double dy = (double)ra[3 * j + 1] - (double)s_col[(3 * j + 1) * NMS_TILE + lane];
       const double dz = (double)ra[3 * j + 2] - (double)s_col[(3 * j + 2) * NMS_TILE + lane];
-      const double d = __builtin_sqrt((dx * dx + dy * dy) + dz * dz);
-      near += (d < limit) ? 1 : 0;
+      near += (norm3(dx, dy, dz) < limit) ? 1 : 0;
     }
     const u64 word = __ballot(col_ok && near > num_nearby_joints_thr);
     if (lane == 0) ws.close[(size_t)a * W + blockIdx.x] = word;
@@ -286,8 +280,8 @@ int mvg_pose_nms(const float* pred, int B, int N, int J, double dist_thr, int nu
   if (B < 1 || N < 1 || N > NMS_MAX_N || J < 1 || J > NMS_MAX_J) return MVG_E_BADARG;
   if (!(dist_thr > 0.0) || num_nearby_joints_thr < 0 || num_nearby_joints_thr >= J) return MVG_E_BADARG;
   if (B > 65535 || (dets != nullptr && (dets_rows < 1 || dets_rows > NMS_MAX_N))) return MVG_E_BADARG;
-  if (pred == nullptr || keep == nullptr || count == nullptr || workspace == nullptr) return MVG_E_BADARG;
-  if (((uintptr_t)workspace & 7) || workspace_bytes < mvg_pose_nms_workspace(B, N, J)) return MVG_E_BADARG;
+  if (mvg_any_null({pred, keep, count, workspace}) || mvg_any_misaligned(8, {workspace})) return MVG_E_BADARG;
+  if (workspace_bytes < mvg_pose_nms_workspace(B, N, J)) return MVG_E_BADARG;
   const int tiles = mvg_ceil_div(N, NMS_TILE);
   const size_t lds = (size_t)2 * NMS_TILE * 3 * J * sizeof(float);
   hipLaunchKernelGGL(nms_rank_kernel, dim3(B), dim3(NMS_RANK_THREADS), 0, (hipStream_t)stream, pred, workspace, N, J, dist_thr);

@@ -21,7 +21,7 @@
 // contiguous lanes (one row, g = 0 .. 7), whose 16-byte pieces at columns 8g + {0, 4} would meet pairwise (g and g + 4 are 32
 // dwords apart): lanes g >= 4 write their second piece first, the eight pieces of one pass are then at columns
 // {0, 8, 16, 24, 36, 44, 52, 60} ^ s = banks {0, 8, 16, 24, 4, 12, 20, 28} ^ s, four dwords each: 32 banks.
-#include "common.h"
+#include "exact_dev.h"
 
 #define OPD_THREADS 256
 #define OPD_TILE MVG_OPERANDS_TILE
@@ -56,8 +56,6 @@ __device__ __forceinline__ unsigned opd_bf16_bits(float f) {
   return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
 }
 
-__device__ __forceinline__ bool opd_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 __global__ __launch_bounds__(OPD_THREADS) void refresh_operands_kernel(const OpdRecord* __restrict__ records, int n_records,
                                                                        const OpdTile* __restrict__ tiles) {
   __shared__ __attribute__((aligned(16))) unsigned s_tile[OPD_TILE * OPD_TILE];
@@ -72,8 +70,8 @@ __global__ __launch_bounds__(OPD_THREADS) void refresh_operands_kernel(const Opd
   const int t = threadIdx.x, g = t & 7, r = t >> 3;
 
   // ---- load + convert: bits[i][e] = element (n0 + r + 32 i, k0 + 8 g + e); zero outside the matrix (never stored)
-  const bool src_vec = full && opd_aligned16(rec.src) && (rec.src_ld & 3) == 0;
-  const bool dst_vec = rec.dst && full && opd_aligned16(rec.dst) && (rec.dst_ld & 7) == 0;
+  const bool src_vec = full && aligned16(rec.src) && (rec.src_ld & 3) == 0;
+  const bool dst_vec = rec.dst && full && aligned16(rec.dst) && (rec.dst_ld & 7) == 0;
   opd_gfloat* src = (opd_gfloat*)rec.src;
   opd_gbf16* dst = (opd_gbf16*)rec.dst;
   unsigned bits[2][8];
@@ -117,7 +115,7 @@ __global__ __launch_bounds__(OPD_THREADS) void refresh_operands_kernel(const Opd
   __syncthreads();
 
   // ---- column gather: thread (ng, kk) stores dstT[k0 + kk][n0 + 8 ng .. + 7]
-  const bool dstT_vec = full && opd_aligned16(rec.dstT) && (rec.dstT_ld & 7) == 0;
+  const bool dstT_vec = full && aligned16(rec.dstT) && (rec.dstT_ld & 7) == 0;
   opd_gbf16* dstT = (opd_gbf16*)rec.dstT;
   const int ng = g;
 #pragma unroll
@@ -142,8 +140,8 @@ extern "C" {
 
 int mvg_refresh_operands(const void* record_table, int n_records, const void* tile_table, int n_tiles, void* stream) {
   if (n_records < 0 || n_tiles < 0) return MVG_E_BADARG;
-  if (n_tiles > 0 && (!record_table || !tile_table || n_records < 1)) return MVG_E_BADARG;
-  if (((uintptr_t)record_table | (uintptr_t)tile_table) & 7) return MVG_E_BADARG;
+  if (n_tiles > 0 && (mvg_any_null({record_table, tile_table}) || n_records < 1)) return MVG_E_BADARG;
+  if (mvg_any_misaligned(8, {record_table, tile_table})) return MVG_E_BADARG;
   if (n_tiles == 0) return 0;
   hipLaunchKernelGGL(refresh_operands_kernel, dim3(n_tiles), dim3(OPD_THREADS), 0, (hipStream_t)stream,
                      (const OpdRecord*)record_table, n_records, (const OpdTile*)tile_table);

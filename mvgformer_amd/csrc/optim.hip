@@ -11,7 +11,7 @@
 // grid covers every tensor with MVG_OPTIM_CHUNK elements per workgroup, whatever the tensors' sizes are.
 #include <math.h>
 
-#include "common.h"
+#include "exact_dev.h"
 
 #define OPT_THREADS 256
 #define OPT_WAVES (OPT_THREADS / MVG_WAVE)
@@ -52,21 +52,6 @@ static_assert(sizeof(OptTensor) == MVG_OPTIM_TENSOR_WORDS * 8 && sizeof(OptChunk
 static_assert(sizeof(OptGroup) == MVG_OPTIM_GROUP_WORDS * 8 && sizeof(OptGroupState) == MVG_OPTIM_STATE_PER_GROUP, "table layout");
 static_assert(sizeof(OptState) == MVG_OPTIM_STATE_HEADER, "state header of mvg_decoder.h");
 
-// fixed-order sum over the workgroup (lanes: butterfly; wavefronts: in order); valid in thread 0
-__device__ __forceinline__ double opt_block_sum(double v, double* scratch) {
-#pragma unroll
-  for (int d = 1; d < MVG_WAVE; d <<= 1) v += __shfl_xor(v, d, MVG_WAVE);
-  __syncthreads();
-  if ((threadIdx.x & (MVG_WAVE - 1)) == 0) scratch[threadIdx.x / MVG_WAVE] = v;
-  __syncthreads();
-  double s = 0.0;
-  if (threadIdx.x == 0)
-    for (int w = 0; w < OPT_WAVES; ++w) s += scratch[w];
-  return s;
-}
-
-__device__ __forceinline__ bool opt_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 // The tensors' pointers come out of a table, so the compiler takes them for generic (flat) addresses; they are global memory.
 typedef __attribute__((address_space(1))) float gfloat;
 typedef __attribute__((address_space(1))) f32x4 gf32x4;
@@ -85,7 +70,7 @@ __global__ __launch_bounds__(OPT_THREADS) void optim_sumsq_kernel(const OptTenso
   if (c.tensor >= 0 && c.tensor < n_tensors && c.index >= 0) {
     const OptTensor t = tensors[c.tensor];
     const long base = (long)c.index * MVG_OPTIM_CHUNK;
-    const bool vec = opt_aligned16(t.grad);
+    const bool vec = aligned16(t.grad);
     gfloat* grad = opt_global(t.grad);
 #pragma unroll
     for (int k = 0; k < OPT_ITERS; ++k) {
@@ -103,7 +88,7 @@ __global__ __launch_bounds__(OPT_THREADS) void optim_sumsq_kernel(const OptTenso
       }
     }
   }
-  const double s = opt_block_sum(acc, s_red);
+  const double s = block_sum<OPT_WAVES>(acc, s_red);
   if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
@@ -116,7 +101,7 @@ __global__ __launch_bounds__(OPT_THREADS) void optim_state_kernel(const double* 
   __shared__ long s_step;
   double acc = 0.0;
   for (int i = threadIdx.x; i < n_chunks; i += OPT_THREADS) acc += partial[i];
-  const double sum = opt_block_sum(acc, s_red);
+  const double sum = block_sum<OPT_WAVES>(acc, s_red);
   if (threadIdx.x == 0) {
     const double norm = sqrt(sum);
     double coef = 1.0;
@@ -179,7 +164,7 @@ __global__ __launch_bounds__(OPT_THREADS) void optim_update_kernel(const OptTens
   const long base = (long)c.index * MVG_OPTIM_CHUNK;
   const bool skip = state->skip != 0;
   if (skip && !zero_grad) return;
-  const bool vec = opt_aligned16(t.p) && opt_aligned16(t.grad) && opt_aligned16(t.exp_avg) && opt_aligned16(t.exp_avg_sq);
+  const bool vec = aligned16(t.p) && aligned16(t.grad) && aligned16(t.exp_avg) && aligned16(t.exp_avg_sq);
   gfloat* tp = opt_global(t.p);
   gfloat* tg = opt_global(t.grad);
   gfloat* tm = opt_global(t.exp_avg);
@@ -250,12 +235,11 @@ size_t mvg_optim_workspace(int n_chunks) {
 int mvg_optim_step(const void* tensor_table, int n_tensors, const void* chunk_table, int n_chunks, const void* group_table,
                    int n_groups, void* state, size_t state_bytes, void* workspace, size_t workspace_bytes, const float* loss,
                    float max_norm, int zero_grad, float* norm_out, void* stream) {
-  if (!group_table || !state || !workspace) return MVG_E_BADARG;
+  if (mvg_any_null({group_table, state, workspace})) return MVG_E_BADARG;
   if (n_tensors < 0 || n_chunks < 0 || n_groups < 1 || n_groups > MVG_OPTIM_MAX_GROUPS) return MVG_E_BADARG;
-  if (n_chunks > 0 && (!tensor_table || !chunk_table || n_tensors < 1)) return MVG_E_BADARG;
-  if (((uintptr_t)tensor_table | (uintptr_t)chunk_table | (uintptr_t)group_table | (uintptr_t)state | (uintptr_t)workspace) & 7)
-    return MVG_E_BADARG;
-  if ((loss && ((uintptr_t)loss & 3)) || (norm_out && ((uintptr_t)norm_out & 3))) return MVG_E_BADARG;
+  if (n_chunks > 0 && (mvg_any_null({tensor_table, chunk_table}) || n_tensors < 1)) return MVG_E_BADARG;
+  if (mvg_any_misaligned(8, {tensor_table, chunk_table, group_table, state, workspace})) return MVG_E_BADARG;
+  if (mvg_any_misaligned(4, {loss, norm_out})) return MVG_E_BADARG;      // both optional
   if (state_bytes < (size_t)MVG_OPTIM_STATE_HEADER + (size_t)n_groups * MVG_OPTIM_STATE_PER_GROUP) return MVG_E_BADARG;
   if (workspace_bytes < mvg_optim_workspace(n_chunks)) return MVG_E_BADARG;
   if (!(max_norm == max_norm)) return MVG_E_BADARG;

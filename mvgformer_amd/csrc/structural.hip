@@ -17,16 +17,14 @@
 // the pivot s_j must be > 0 (a NaN is not), d = sqrt(s_j), L[j][j] = d, L[i][j] = s_i / d.  The inverse: lane c solves
 // L y = e_c downwards from row c (Y = L^-1, lower), then Inv[r][c] = sum_{k = r ascending}^{n-1} Y[k][r] Y[k][c] for c <= r, written
 // to both triangles.  Every sum is formed by one lane in ascending index order from +0.0, every product is rounded on its own
-// (st_mul: the library is built with -ffp-contract=fast, which the pragma below does not stop on its own; see track.hip), sqrt
+// (through f64_mul_nv: see CONTRACTION in exact_dev.h; this file has no product outside it that feeds an add), sqrt
 // and division are correctly rounded.  Every loop is counted; a failed pivot ends the person (status 1 or 2), wave-uniformly.
 //
 // LDS: two n x n fp64 matrices with a row stride of 49 (odd: a column walk touches all banks) = 2 x 18.4 KB, plus ~7 KB of small
 // tables (45.3 KB in all): three persons a CU by LDS.
 #include <math.h>
 
-#include "common.h"
-
-#pragma clang fp contract(off)
+#include "exact_dev.h"
 
 #define ST_THREADS MVG_WAVE
 #define ST_MAXJ MVG_ST_MAX_J
@@ -42,15 +40,6 @@ struct StTree {
   unsigned anc[ST_MAXJ];      // bit k of anc[i]: bone k (the one that ends at joint k >= 1) lies on the path root -> i
 };
 
-static __device__ __forceinline__ double st_mul(double a, double b) {
-  double p = a * b;
-  asm("" : "+v"(p));          // not volatile: the loads and products of a chain may still be scheduled ahead of its adds
-  return p;
-}
-static __device__ __forceinline__ double st_lane(double v, int from) {      // `from` is wave-uniform
-  const int l = __builtin_amdgcn_readfirstlane(from);
-  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
-}
 // entry e of a lower triangle stored row by row: e = r (r + 1) / 2 + c, c <= r
 static __device__ __forceinline__ void st_tri(int e, int& r, int& c) {
   int g = (int)((sqrtf(8.f * (float)e + 1.f) - 1.f) * 0.5f);
@@ -67,9 +56,9 @@ static __device__ bool st_chol(double* M, int n, int ld, int lane) {
     double s = 0.0;
     if (lane >= j && lane < n) {
       s = M[lane * ld + j];
-      for (int k = 0; k < j; ++k) s = s - st_mul(M[lane * ld + k], M[j * ld + k]);
+      for (int k = 0; k < j; ++k) s = s - f64_mul_nv(M[lane * ld + k], M[j * ld + k]);
     }
-    const double piv = st_lane(s, j);
+    const double piv = lane_of(s, j);
     if (!(piv > 0.0)) return false;
     const double d = __builtin_sqrt(piv);
     if (lane == j) M[j * ld + j] = d;
@@ -85,7 +74,7 @@ static __device__ void st_inverse(const double* Lm, double* Y, double* Inv, int 
     const int c = lane;
     for (int i = c; i < n; ++i) {
       double s = i == c ? 1.0 : 0.0;
-      for (int k = c; k < i; ++k) s = s - st_mul(Lm[i * ST_LD + k], Y[k * ST_LD + c]);
+      for (int k = c; k < i; ++k) s = s - f64_mul_nv(Lm[i * ST_LD + k], Y[k * ST_LD + c]);
       Y[i * ST_LD + c] = s / Lm[i * ST_LD + i];
     }
   }
@@ -94,7 +83,7 @@ static __device__ void st_inverse(const double* Lm, double* Y, double* Inv, int 
     int r, c;
     st_tri(e, r, c);
     double acc = 0.0;
-    for (int k = r; k < n; ++k) acc = acc + st_mul(Y[k * ST_LD + r], Y[k * ST_LD + c]);
+    for (int k = r; k < n; ++k) acc = acc + f64_mul_nv(Y[k * ST_LD + r], Y[k * ST_LD + c]);
     Inv[r * ST_LD + c] = acc;
     Inv[c * ST_LD + r] = acc;
   }
@@ -130,7 +119,7 @@ __global__ __launch_bounds__(ST_THREADS) void structural_kernel(const float* __r
   // which query, if any (wave-uniform)
   int q = -1;
   if (rows != nullptr) {
-    const int live = count == nullptr ? P : min(max(count[2 * b], 0), P);
+    const int live = det_rows(count, b, P);
     if (p < live) q = rows[(size_t)b * rows_ld + p];
   } else if (valid == nullptr || valid[(size_t)b * NQ + p] != 0) {
     q = p;
@@ -151,18 +140,20 @@ __global__ __launch_bounds__(ST_THREADS) void structural_kernel(const float* __r
       const double u = (double)ud[tok * 2], w = (double)ud[tok * 2 + 1];
       const double c2 = 2.0 * (conf == nullptr ? cdef : (double)conf[tok]);
       const double r20 = (double)Pv[8], r21 = (double)Pv[9], r22 = (double)Pv[10], t2 = (double)Pv[11];
-      const double g00 = (double)Pv[0] - st_mul(u, r20), g01 = (double)Pv[1] - st_mul(u, r21), g02 = (double)Pv[2] - st_mul(u, r22);
-      const double g10 = (double)Pv[4] - st_mul(w, r20), g11 = (double)Pv[5] - st_mul(w, r21), g12 = (double)Pv[6] - st_mul(w, r22);
-      const double h0 = (double)Pv[3] - st_mul(u, t2), h1 = (double)Pv[7] - st_mul(w, t2);
-      D00 = D00 + st_mul(c2, st_mul(g00, g00) + st_mul(g10, g10));
-      D01 = D01 + st_mul(c2, st_mul(g00, g01) + st_mul(g10, g11));
-      D02 = D02 + st_mul(c2, st_mul(g00, g02) + st_mul(g10, g12));
-      D11 = D11 + st_mul(c2, st_mul(g01, g01) + st_mul(g11, g11));
-      D12 = D12 + st_mul(c2, st_mul(g01, g02) + st_mul(g11, g12));
-      D22 = D22 + st_mul(c2, st_mul(g02, g02) + st_mul(g12, g12));
-      m0 = m0 - st_mul(c2, st_mul(g00, h0) + st_mul(g10, h1));
-      m1 = m1 - st_mul(c2, st_mul(g01, h0) + st_mul(g11, h1));
-      m2 = m2 - st_mul(c2, st_mul(g02, h0) + st_mul(g12, h1));
+      const double g00 = (double)Pv[0] - f64_mul_nv(u, r20), g01 = (double)Pv[1] - f64_mul_nv(u, r21);
+      const double g02 = (double)Pv[2] - f64_mul_nv(u, r22);
+      const double g10 = (double)Pv[4] - f64_mul_nv(w, r20), g11 = (double)Pv[5] - f64_mul_nv(w, r21);
+      const double g12 = (double)Pv[6] - f64_mul_nv(w, r22);
+      const double h0 = (double)Pv[3] - f64_mul_nv(u, t2), h1 = (double)Pv[7] - f64_mul_nv(w, t2);
+      D00 = D00 + f64_mul_nv(c2, f64_mul_nv(g00, g00) + f64_mul_nv(g10, g10));
+      D01 = D01 + f64_mul_nv(c2, f64_mul_nv(g00, g01) + f64_mul_nv(g10, g11));
+      D02 = D02 + f64_mul_nv(c2, f64_mul_nv(g00, g02) + f64_mul_nv(g10, g12));
+      D11 = D11 + f64_mul_nv(c2, f64_mul_nv(g01, g01) + f64_mul_nv(g11, g11));
+      D12 = D12 + f64_mul_nv(c2, f64_mul_nv(g01, g02) + f64_mul_nv(g11, g12));
+      D22 = D22 + f64_mul_nv(c2, f64_mul_nv(g02, g02) + f64_mul_nv(g12, g12));
+      m0 = m0 - f64_mul_nv(c2, f64_mul_nv(g00, h0) + f64_mul_nv(g10, h1));
+      m1 = m1 - f64_mul_nv(c2, f64_mul_nv(g01, h0) + f64_mul_nv(g11, h1));
+      m2 = m2 - f64_mul_nv(c2, f64_mul_nv(g02, h0) + f64_mul_nv(g12, h1));
     }
     double* d = s_D[lane];
     d[0] = D00; d[1] = D01; d[2] = D02;
@@ -196,12 +187,12 @@ __global__ __launch_bounds__(ST_THREADS) void structural_kernel(const float* __r
     for (int w = lane; w < K * 9; w += ST_THREADS) {
       const int k = w / 9, a = (w % 9) / 3, c = w % 3;
       double acc = 0.0;
-      for (int t = 0; t < 3; ++t) acc = acc + st_mul(s_Tinv[a * 3 + t], s_C[k][t * 3 + c]);
+      for (int t = 0; t < 3; ++t) acc = acc + f64_mul_nv(s_Tinv[a * 3 + t], s_C[k][t * 3 + c]);
       s_W[k][a * 3 + c] = acc;
     }
     if (lane < 3) {
       double acc = 0.0;
-      for (int t = 0; t < 3; ++t) acc = acc + st_mul(s_Tinv[lane * 3 + t], s_T[9 + t]);
+      for (int t = 0; t < 3; ++t) acc = acc + f64_mul_nv(s_Tinv[lane * 3 + t], s_T[9 + t]);
       s_tm[lane] = acc;
     }
     __syncthreads();
@@ -213,13 +204,13 @@ __global__ __launch_bounds__(ST_THREADS) void structural_kernel(const float* __r
       if ((tree.anc[l] >> k) & 1u) base = s_C[l - 1][a * 3 + bb];
       else if ((tree.anc[k] >> l) & 1u) base = s_C[k - 1][a * 3 + bb];
       double acc = 0.0;
-      for (int t = 0; t < 3; ++t) acc = acc + st_mul(s_C[k - 1][a * 3 + t], s_W[l - 1][t * 3 + bb]);
+      for (int t = 0; t < 3; ++t) acc = acc + f64_mul_nv(s_C[k - 1][a * 3 + t], s_W[l - 1][t * 3 + bb]);
       s_m0[r * ST_LD + c] = base - acc;
     }
     if (lane < n) {
       const int k = lane / 3, a = lane % 3;
       double acc = 0.0;
-      for (int t = 0; t < 3; ++t) acc = acc + st_mul(s_C[k][a * 3 + t], s_tm[t]);
+      for (int t = 0; t < 3; ++t) acc = acc + f64_mul_nv(s_C[k][a * 3 + t], s_tm[t]);
       s_beta[lane] = s_C[k][9 + a] - acc;
     }
     __syncthreads();
@@ -237,7 +228,7 @@ __global__ __launch_bounds__(ST_THREADS) void structural_kernel(const float* __r
   double* Alt = s_m1;
   if (lane < n) {
     double acc = 0.0;
-    for (int c = 0; c < n; ++c) acc = acc + st_mul(Inv[lane * ST_LD + c], s_beta[c]);
+    for (int c = 0; c < n; ++c) acc = acc + f64_mul_nv(Inv[lane * ST_LD + c], s_beta[c]);
     s_b[lane] = acc;
   }
   __syncthreads();
@@ -249,10 +240,10 @@ __global__ __launch_bounds__(ST_THREADS) void structural_kernel(const float* __r
       double rhs = 0.0;
       if (lane < K) {
         const double b0 = s_b[3 * lane], b1 = s_b[3 * lane + 1], b2 = s_b[3 * lane + 2];
-        const double start = __builtin_sqrt((st_mul(b0, b0) + st_mul(b1, b1)) + st_mul(b2, b2));
+        const double start = __builtin_sqrt((f64_mul_nv(b0, b0) + f64_mul_nv(b1, b1)) + f64_mul_nv(b2, b2));
         const double len = (double)bone_len[per_person ? (size_t)blockIdx.x * K + lane : (size_t)lane];
-        const double target = (st_mul(start, (double)(n_steps - s - 1)) + len) / (double)(n_steps - s);
-        rhs = (st_mul(start, start) - st_mul(target, target)) / 4.0;
+        const double target = (f64_mul_nv(start, (double)(n_steps - s - 1)) + len) / (double)(n_steps - s);
+        rhs = (f64_mul_nv(start, start) - f64_mul_nv(target, target)) / 4.0;
       }
       for (int e = lane; e < K * (K + 1) / 2; e += ST_THREADS) {
         int k, l;
@@ -260,8 +251,8 @@ __global__ __launch_bounds__(ST_THREADS) void structural_kernel(const float* __r
         double acc = 0.0;
         for (int a = 0; a < 3; ++a) {
           double t = 0.0;
-          for (int c = 0; c < 3; ++c) t = t + st_mul(Inv[(3 * k + a) * ST_LD + 3 * l + c], s_b[3 * l + c]);
-          acc = acc + st_mul(s_b[3 * k + a], t);
+          for (int c = 0; c < 3; ++c) t = t + f64_mul_nv(Inv[(3 * k + a) * ST_LD + 3 * l + c], s_b[3 * l + c]);
+          acc = acc + f64_mul_nv(s_b[3 * k + a], t);
         }
         s_S[k * ST_SLD + l] = acc;
       }
@@ -274,7 +265,7 @@ __global__ __launch_bounds__(ST_THREADS) void structural_kernel(const float* __r
       for (int i = 0; i < K; ++i) {
         if (lane == i) {
           double acc = rhs;
-          for (int k = 0; k < i; ++k) acc = acc - st_mul(s_S[i * ST_SLD + k], s_lam[k]);
+          for (int k = 0; k < i; ++k) acc = acc - f64_mul_nv(s_S[i * ST_SLD + k], s_lam[k]);
           s_lam[i] = acc / s_S[i * ST_SLD + i];
         }
         __syncthreads();
@@ -284,7 +275,7 @@ __global__ __launch_bounds__(ST_THREADS) void structural_kernel(const float* __r
       for (int i = K - 1; i >= 0; --i) {
         if (lane == i) {
           double acc = y;
-          for (int k = i + 1; k < K; ++k) acc = acc - st_mul(s_S[k * ST_SLD + i], s_lam[k]);
+          for (int k = i + 1; k < K; ++k) acc = acc - f64_mul_nv(s_S[k * ST_SLD + i], s_lam[k]);
           s_lam[i] = acc / s_S[i * ST_SLD + i];
         }
         __syncthreads();
@@ -294,7 +285,7 @@ __global__ __launch_bounds__(ST_THREADS) void structural_kernel(const float* __r
         st_tri(e, r, c);
         double acc = 0.0;
         for (int j = 0; j < n; ++j)
-          acc = acc + st_mul(st_mul(Inv[r * ST_LD + j], 2.0 * s_lam[j / 3]), Inv[j * ST_LD + c]);
+          acc = acc + f64_mul_nv(f64_mul_nv(Inv[r * ST_LD + j], 2.0 * s_lam[j / 3]), Inv[j * ST_LD + c]);
         const double val = Inv[r * ST_LD + c] - acc;
         Alt[r * ST_LD + c] = val;
         Alt[c * ST_LD + r] = val;
@@ -305,7 +296,7 @@ __global__ __launch_bounds__(ST_THREADS) void structural_kernel(const float* __r
       Alt = swap;
       if (lane < n) {
         double acc = 0.0;
-        for (int c = 0; c < n; ++c) acc = acc + st_mul(Inv[lane * ST_LD + c], s_beta[c]);
+        for (int c = 0; c < n; ++c) acc = acc + f64_mul_nv(Inv[lane * ST_LD + c], s_beta[c]);
         s_b[lane] = acc;
       }
       __syncthreads();
@@ -315,14 +306,14 @@ __global__ __launch_bounds__(ST_THREADS) void structural_kernel(const float* __r
   // 5. the root, then the joints along the tree
   if (lane < 3) {
     double qa = 0.0;
-    for (int j = 0; j < n; ++j) qa = qa + st_mul(s_C[j / 3][lane * 3 + j % 3], s_b[j]);
+    for (int j = 0; j < n; ++j) qa = qa + f64_mul_nv(s_C[j / 3][lane * 3 + j % 3], s_b[j]);
     s_x0[lane] = s_T[9 + lane] - qa;          // mu - q, T^-1 applied below
   }
   __syncthreads();
   if (lane < J) {
     for (int a = 0; a < 3; ++a) {
       double x = 0.0;
-      for (int t = 0; t < 3; ++t) x = x + st_mul(s_Tinv[a * 3 + t], s_x0[t]);
+      for (int t = 0; t < 3; ++t) x = x + f64_mul_nv(s_Tinv[a * 3 + t], s_x0[t]);
       for (int k = 1; k < J; ++k)
         if ((tree.anc[lane] >> k) & 1u) x = x + s_b[3 * (k - 1) + a];
       Xo[lane * 3 + a] = (float)x;
@@ -340,7 +331,7 @@ int mvg_structural_triangulate(const float* ud, const float* conf, const float* 
   if ((long long)B * P > 0x7fffffffLL || (long long)NQ * J > 0x7fffffffLL) return MVG_E_BADARG;
   if (method != MVG_ST_LS && method != MVG_ST_ST) return MVG_E_BADARG;
   if (n_steps < 1 || n_steps > MVG_ST_MAX_STEPS) return MVG_E_BADARG;
-  if (ud == nullptr || Pm == nullptr || X == nullptr || status == nullptr || parent_host == nullptr) return MVG_E_BADARG;
+  if (mvg_any_null({ud, Pm, X, status, parent_host})) return MVG_E_BADARG;
   if (method == MVG_ST_ST && bone_len == nullptr) return MVG_E_BADARG;
   if (rows != nullptr && (valid != nullptr || rows_ld < P)) return MVG_E_BADARG;
   if (rows == nullptr && (count != nullptr || P != NQ)) return MVG_E_BADARG;

@@ -25,24 +25,22 @@
 // unchanged by the column's lane; the minimum is taken under a total order (value, NaN as +inf, then column), so the shape of
 // the reduction does not matter.  Every loop is counted: no input, NaN included, can make a search spin.
 //
-// Arithmetic: fp64 from the fp32 inputs, every multiply and add rounded on its own ((x^2 + y^2) + z^2, correctly rounded sqrt),
-// joints summed in joint order: this file switches contraction off like nms.hip.  The only atomics are integer adds on the state
-// block, whose sums do not depend on the order of the workgroups: two runs give the same bits.
+// Arithmetic: fp64 from the fp32 inputs, sqrt((x^2 + y^2) + z^2) with a correctly rounded sqrt, joints summed in joint order.
+// CONTRACTION in exact_dev.h says which products are rounded on their own: the distances of track_update_kernel are dist3, the
+// FUSED form; those of track_eval_kernel are dist3_exact and the motion model goes through f64_mul, exact for every input.  The
+// only atomics are integer adds on the state block, whose sums do not depend on the order of the workgroups: two runs give
+// the same bits.
 #include <math.h>
 
-#include "common.h"
-
-#pragma clang fp contract(off)
+#include "exact_dev.h"
 
 #define LAP_N MVG_LAP_MAX_N
 #define LAP_VIRT LAP_N                // the virtual column a row's search starts from
 #define TRACK_THREADS 256
 
 static_assert(LAP_N == MVG_WAVE, "a lane per column");
+static_assert(TRACK_THREADS == SCAN_THREADS, "track_update_kernel and track_eval_kernel call scan_rows; the others only share it");
 static_assert(MVG_TRACK_MAX_D == LAP_N && MVG_TRACK_MAX_T == LAP_N, "tracks and detections are the solver's rows and columns");
-
-typedef long long i64;
-typedef unsigned long long u64;
 
 enum { TS_FRAMES = 0, TS_MATCHES = 1, TS_BIRTHS = 2, TS_DEATHS = 3, TS_OVERFLOW = 4, TS_DROPPED = 5, TS_ACTIVE = 6, TS_TICKET = 7 };
 
@@ -55,20 +53,13 @@ struct LapGate {
   __device__ __forceinline__ double operator()(double c) const { return c <= max_dist ? c : max_dist; }
 };
 
-// cross-lane moves of a double: two 32-bit halves through the DPP network (within a row of 16 lanes) / v_readlane (from a lane
-// whose index is wave-uniform)
+// cross-lane move of a double inside a row of 16 lanes: two 32-bit halves through the DPP network (lane_of of exact_dev.h reads
+// from a lane whose index is wave-uniform)
 template <int CTRL>
 static __device__ __forceinline__ double lap_dpp(double v) {
   const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, false);
   const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, false);
   return __hiloint2double(hi, lo);
-}
-static __device__ __forceinline__ int lap_lane(int v, int from) {
-  return __builtin_amdgcn_readlane(v, __builtin_amdgcn_readfirstlane(from));
-}
-static __device__ __forceinline__ double lap_lane(double v, int from) {
-  const int l = __builtin_amdgcn_readfirstlane(from);
-  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
 }
 static __device__ __forceinline__ double lap_min(double a, double b) { return b < a ? b : a; }
 
@@ -90,7 +81,7 @@ static __device__ void lap_solve(const double* s_raw, int n, int m, F f, int* s_
     for (int step = 0; step < s; ++step) {        // every step uses one more column and at most i are assigned: <= i + 1 steps
       if (lane == j0) used = true;
       if (lane == i0) rowused = true;
-      const double ui0 = lap_lane(u, i0);
+      const double ui0 = lane_of(u, i0);
       const bool cand = lane < s && !used;
       if (cand) {
         double sv = 0.0;
@@ -113,18 +104,18 @@ static __device__ void lap_solve(const double* s_raw, int n, int m, F f, int* s_
       kmin = lap_min(kmin, lap_dpp<0x4E>(kmin));
       kmin = lap_min(kmin, lap_dpp<0x141>(kmin));
       kmin = lap_min(kmin, lap_dpp<0x140>(kmin));
-      kmin = lap_min(lap_min(lap_lane(kmin, 0), lap_lane(kmin, 16)), lap_min(lap_lane(kmin, 32), lap_lane(kmin, 48)));
+      kmin = lap_min(lap_min(lane_of(kmin, 0), lane_of(kmin, 16)), lap_min(lane_of(kmin, 32), lane_of(kmin, 48)));
       const u64 holders = __ballot(cand && key == kmin);
       if (holders == 0) break;                     // not reachable: an unused column exists while the search runs
       const int j1 = __builtin_ctzll(holders);
-      const double delta = lap_lane(minv, j1);
+      const double delta = lane_of(minv, j1);
       if (rowused) u += delta;
       if (lane < s) {
         if (used) v -= delta;
         else minv -= delta;
       }
       j0 = j1;
-      const int pj0 = lap_lane(p, j0);
+      const int pj0 = lane_of(p, j0);
       if (pj0 < 0) {
         found = true;
         break;
@@ -133,8 +124,8 @@ static __device__ void lap_solve(const double* s_raw, int n, int m, F f, int* s_
     }
     if (!found) continue;                          // not reachable: the counted loop above always ends on a free column
     for (int k = 0; k <= s; ++k) {                 // flip the path back to the virtual column: <= i + 1 links
-      const int j1 = lap_lane(way, j0);
-      const int pj1 = j1 == LAP_VIRT ? i : lap_lane(p, j1 & (LAP_N - 1));
+      const int j1 = lane_of(way, j0);
+      const int pj1 = j1 == LAP_VIRT ? i : lane_of(p, j1 & (LAP_N - 1));
       if (lane == j0) p = pj1;
       j0 = j1;
       if (j0 == LAP_VIRT) break;
@@ -144,8 +135,6 @@ static __device__ void lap_solve(const double* s_raw, int n, int m, F f, int* s_
   if (p >= 0 && p < n && lane < m) s_col[p] = lane;
 }
 
-static __device__ __forceinline__ int track_clamp(int v, int hi) { return min(max(v, 0), hi); }
-
 // ------------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(LAP_N) void linear_assignment_kernel(const double* __restrict__ cost, const int* __restrict__ n_live,
                                                                   const int* __restrict__ m_live, int N, int M,
@@ -153,8 +142,8 @@ __global__ __launch_bounds__(LAP_N) void linear_assignment_kernel(const double* 
   __shared__ double s_raw[LAP_N * LAP_N];
   __shared__ int s_col[LAP_N];
   const int b = blockIdx.x, lane = threadIdx.x;
-  const int n = n_live == nullptr ? N : track_clamp(n_live[b], N);
-  const int m = m_live == nullptr ? M : track_clamp(m_live[b], M);
+  const int n = n_live == nullptr ? N : clamp_count(n_live[b], N);
+  const int m = m_live == nullptr ? M : clamp_count(m_live[b], M);
   const double* c = cost + (size_t)b * N * M;
   for (int e = lane; e < n * m; e += LAP_N) s_raw[(e / m) * LAP_N + (e % m)] = c[(size_t)(e / m) * M + (e % m)];
   __syncthreads();
@@ -170,14 +159,6 @@ __global__ __launch_bounds__(LAP_N) void linear_assignment_kernel(const double* 
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
-static __device__ __forceinline__ bool track_is_det(const float* dets, const int* count, int b, int i, int R, int J, int rows) {
-  return i < rows && dets[((size_t)b * R + i) * J * 5 + 3] >= 0.f;
-}
-static __device__ __forceinline__ double track_dist(const float* p, const float* g) {
-  const double dx = (double)p[0] - (double)g[0], dy = (double)p[1] - (double)g[1], dz = (double)p[2] - (double)g[2];
-  return __builtin_sqrt((dx * dx + dy * dy) + dz * dz);
-}
-
 __global__ __launch_bounds__(TRACK_THREADS) void track_update_kernel(const float* __restrict__ dets, const int* __restrict__ count,
                                                                      int B, int R, int J, int T, int* __restrict__ id,
                                                                      int* __restrict__ hits, int* __restrict__ misses,
@@ -186,7 +167,7 @@ __global__ __launch_bounds__(TRACK_THREADS) void track_update_kernel(const float
                                                                      double max_dist, int max_misses, int min_hits,
                                                                      int* __restrict__ ids, int* __restrict__ slots) {
   __shared__ double s_c[LAP_N * LAP_N];        // ungated mean joint distance of (active track a, detection d)
-  __shared__ int s_scan[2][TRACK_THREADS];
+  __shared__ int s_scan[2][1][SCAN_THREADS];
   __shared__ int s_det[LAP_N];                 // row of detection d
   __shared__ int s_trk[LAP_N];                 // slot of active track a
   __shared__ int s_col[LAP_N];                 // detection assigned to active track a, or -1
@@ -197,28 +178,18 @@ __global__ __launch_bounds__(TRACK_THREADS) void track_update_kernel(const float
   const int b = blockIdx.x, t = threadIdx.x;
   if (t == 0) s_frame = __hip_atomic_load(&state[TS_FRAMES], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 
-  // detections: the rows in front of count[b, 0] whose flag is >= 0, in row order.  Every thread owns a run of consecutive rows,
-  // the run totals go through an LDS scan.
-  const int rows = count == nullptr ? R : track_clamp(count[2 * b], R);
-  const int chunk = (R + TRACK_THREADS - 1) / TRACK_THREADS;
-  const int lo = min(t * chunk, R), hi = min(lo + chunk, R);
-  int mine = 0;
-  for (int i = lo; i < hi; ++i) mine += track_is_det(dets, count, b, i, R, J, rows) ? 1 : 0;
-  s_scan[0][t] = mine;
-  __syncthreads();
-  int src = 0;
-  for (int step = 1; step < TRACK_THREADS; step <<= 1) {
-    s_scan[src ^ 1][t] = s_scan[src][t] + (t >= step ? s_scan[src][t - step] : 0);
-    src ^= 1;
-    __syncthreads();
-  }
-  const int first = s_scan[src][t] - mine;     // detections in front of this thread's run
-  const int nd_all = s_scan[src][TRACK_THREADS - 1];
+  // detections: the rows in front of count[b, 0] whose flag is >= 0, in row order
+  const int rows = det_rows(count, b, R);
+  const auto is_det = [=](int i) { return i < rows && det_flag(dets, b, i, R, J); };
+  const RowScan<1> run = scan_rows<1>(R, s_scan, [=](int i, int* n) { n[0] += is_det(i) ? 1 : 0; });
+  const int lo = run.lo, hi = run.hi;
+  const int first = run.before(0);             // detections in front of this thread's run
+  const int nd_all = run.total(0);
   const int nd = min(nd_all, MVG_TRACK_MAX_D);
   {
     int pos = first;
     for (int i = lo; i < hi && pos < MVG_TRACK_MAX_D; ++i)
-      if (track_is_det(dets, count, b, i, R, J, rows)) s_det[pos++] = i;
+      if (is_det(i)) s_det[pos++] = i;
   }
   // active tracks: the slots with id >= 0, in slot order
   if (t < LAP_N) {
@@ -238,7 +209,7 @@ __global__ __launch_bounds__(TRACK_THREADS) void track_update_kernel(const float
     const float* p = pose + ((size_t)b * T + s_trk[a]) * J * 3;
     const float* g = dets + ((size_t)b * R + s_det[d]) * J * 5;
     double sum = 0.0;
-    for (int j = 0; j < J; ++j) sum += track_dist(p + j * 3, g + j * 5);
+    for (int j = 0; j < J; ++j) sum += dist3(p + j * 3, g + j * 5);
     s_c[a * LAP_N + d] = sum / (double)J;
   }
   __syncthreads();
@@ -315,7 +286,7 @@ __global__ __launch_bounds__(TRACK_THREADS) void track_update_kernel(const float
     int pos = first;
     for (int i = lo; i < hi; ++i) {
       int slot = -1, tid = -1;
-      if (track_is_det(dets, count, b, i, R, J, rows)) {
+      if (is_det(i)) {
         if (pos < MVG_TRACK_MAX_D) {
           slot = s_det_slot[pos];
           if (slot >= 0 && s_hits[slot] >= min_hits) tid = s_id[slot];
@@ -347,14 +318,7 @@ __global__ __launch_bounds__(TRACK_THREADS) void track_update_kernel(const float
 // ------------------------------------------------------------------------------------------------------------------------------
 // The constant-velocity motion model around the update.  One workgroup per stream, threads striding over the T * J * 3 coordinates
 // of its slots; a slot's three covariance entries belong to the thread of its first coordinate.  Each operation below is one
-// rounded fp64 operation, in the order of include/mvg_decoder.h.  The library is built with -ffp-contract=fast, which fuses a
-// multiply into the add behind it whatever the pragma above says; a product that feeds an add therefore goes through track_mul,
-// whose empty asm statement the compiler cannot fuse across.
-static __device__ __forceinline__ double track_mul(double a, double b) {
-  double p = a * b;
-  asm volatile("" : "+v"(p));
-  return p;
-}
+// rounded fp64 operation, in the order of include/mvg_decoder.h: a product that feeds an add goes through f64_mul (exact_dev.h).
 
 __global__ __launch_bounds__(TRACK_THREADS) void track_predict_kernel(int T, int J, const int* __restrict__ id, float* __restrict__ pose,
                                                                       double* __restrict__ mean, double* __restrict__ var, double dt,
@@ -368,14 +332,14 @@ __global__ __launch_bounds__(TRACK_THREADS) void track_predict_kernel(int T, int
     const size_t slot = (size_t)b * T + t;
     if (id[slot] < 0) continue;
     double* m = mean + (slot * J + k / 3) * 6 + k % 3;       // m[0] position, m[3] velocity of this joint and axis
-    const double x = m[0] + track_mul(m[3], dt);
+    const double x = m[0] + f64_mul(m[3], dt);
     m[0] = x;
     pose[slot * J3 + k] = (float)x;
     if (k == 0) {
       double* p = var + slot * 3;
       const double pxx = p[0], pxv = p[1], pvv = p[2];
-      p[0] = ((pxx + track_mul(2.0 * dt, pxv)) + track_mul(dt2, pvv)) + qxx;
-      p[1] = (pxv + track_mul(dt, pvv)) + qxv;
+      p[0] = ((pxx + f64_mul(2.0 * dt, pxv)) + f64_mul(dt2, pvv)) + qxx;
+      p[1] = (pxv + f64_mul(dt, pvv)) + qxv;
       p[2] = pvv + qvv;
     }
   }
@@ -406,8 +370,8 @@ __global__ __launch_bounds__(TRACK_THREADS) void track_correct_kernel(int R, int
       const double kx = pxx / s, kv = pxv / s;
       double x = m[0], v = m[3];
       const double d = (double)pose[slot * J3 + k] - x;
-      x = x + track_mul(kx, d);
-      v = v + track_mul(kv, d);
+      x = x + f64_mul(kx, d);
+      v = v + f64_mul(kv, d);
       m[0] = x;
       m[3] = v;
       pose[slot * J3 + k] = (float)x;
@@ -430,7 +394,7 @@ __global__ __launch_bounds__(TRACK_THREADS) void track_correct_kernel(int R, int
       const double pxx = p[0], pxv = p[1], pvv = p[2];
       const double s = pxx + r;
       const double kx = pxx / s, kv = pxv / s;
-      p[2] = pvv - track_mul(kv, pxv);
+      p[2] = pvv - f64_mul(kv, pxv);
       p[1] = (1.0 - kx) * pxv;
       p[0] = (1.0 - kx) * pxx;
     }
@@ -452,12 +416,6 @@ static_assert(MVG_TRACK_EVAL_WORDS == TE_RESERVED + 1, "the counters of include/
 static_assert(MVG_TRACK_EVAL_MAX_P == LAP_N, "persons are the solver's rows");
 static_assert(TE_GATHER * TRACK_THREADS == LAP_N * LAP_N, "the tile is compacted through TE_GATHER registers per thread");
 
-// track_dist with every product rounded on its own (track_mul): the distances are summed into dist_sum, which is compared bit for bit
-static __device__ __forceinline__ double track_eval_dist(const float* p, const float* g) {
-  const double dx = (double)p[0] - (double)g[0], dy = (double)p[1] - (double)g[1], dz = (double)p[2] - (double)g[2];
-  return __builtin_sqrt((track_mul(dx, dx) + track_mul(dy, dy)) + track_mul(dz, dz));
-}
-
 __global__ __launch_bounds__(TRACK_THREADS) void track_eval_kernel(const float* __restrict__ dets, const int* __restrict__ count,
                                                                    const int* __restrict__ ids, const float* __restrict__ row_pose,
                                                                    const float* __restrict__ joints_3d, const float* __restrict__ vis,
@@ -469,7 +427,7 @@ __global__ __launch_bounds__(TRACK_THREADS) void track_eval_kernel(const float* 
                                                                    int* __restrict__ overlap) {
   __shared__ double s_d[LAP_N * LAP_N];        // d[person a, hypothesis h]; from step 6 on: the remaining pairs, compacted
   __shared__ double s_pd[LAP_N];               // distance of person a's match
-  __shared__ int s_scan[2][2][TRACK_THREADS];  // [hypotheses, unreported rows]
+  __shared__ int s_scan[2][2][SCAN_THREADS];   // [hypotheses, unreported rows]; from step 6 on: the id_overflow counts
   __shared__ int s_row[LAP_N], s_hid[LAP_N];   // row and id of hypothesis h
   __shared__ int s_slot[LAP_N], s_pid[LAP_N];  // slot and identity of person a
   __shared__ int s_ph[LAP_N];                  // hypothesis matched to person a, or -1
@@ -481,32 +439,21 @@ __global__ __launch_bounds__(TRACK_THREADS) void track_eval_kernel(const float* 
   const int annotated = num_person[b];
   if (annotated < 0) return;                   // the whole workgroup: a frame without annotation
 
-  // hypotheses: the detection rows that carry an id, in row order (the scan of track_update_kernel, two counts at once)
-  const int rows = count == nullptr ? R : track_clamp(count[2 * b], R);
-  const int chunk = (R + TRACK_THREADS - 1) / TRACK_THREADS;
-  const int lo = min(t * chunk, R), hi = min(lo + chunk, R);
-  int mine = 0, mine_u = 0;
-  for (int i = lo; i < hi; ++i)
-    if (track_is_det(dets, count, b, i, R, J, rows)) {
-      if (ids[(size_t)b * R + i] >= 0) ++mine;
-      else ++mine_u;
+  // hypotheses: the detection rows that carry an id, in row order; the detection rows without one are only counted
+  const int rows = det_rows(count, b, R);
+  const auto is_det = [=](int i) { return i < rows && det_flag(dets, b, i, R, J); };
+  const RowScan<2> run = scan_rows<2>(R, s_scan, [=](int i, int* n) {
+    if (is_det(i)) {
+      if (ids[(size_t)b * R + i] >= 0) ++n[0];
+      else ++n[1];
     }
-  s_scan[0][0][t] = mine;
-  s_scan[0][1][t] = mine_u;
-  __syncthreads();
-  int src = 0;
-  for (int step = 1; step < TRACK_THREADS; step <<= 1) {
-    s_scan[src ^ 1][0][t] = s_scan[src][0][t] + (t >= step ? s_scan[src][0][t - step] : 0);
-    s_scan[src ^ 1][1][t] = s_scan[src][1][t] + (t >= step ? s_scan[src][1][t - step] : 0);
-    src ^= 1;
-    __syncthreads();
-  }
-  const int nh_all = s_scan[src][0][TRACK_THREADS - 1], unreported = s_scan[src][1][TRACK_THREADS - 1];
+  });
+  const int nh_all = run.total(0), unreported = run.total(1);
   const int nh = min(nh_all, MVG_TRACK_MAX_D);
   {
-    int pos = s_scan[src][0][t] - mine;
-    for (int i = lo; i < hi && pos < MVG_TRACK_MAX_D; ++i)
-      if (track_is_det(dets, count, b, i, R, J, rows) && ids[(size_t)b * R + i] >= 0) {
+    int pos = run.before(0);
+    for (int i = run.lo; i < run.hi && pos < MVG_TRACK_MAX_D; ++i)
+      if (is_det(i) && ids[(size_t)b * R + i] >= 0) {
         s_row[pos] = i;
         s_hid[pos++] = ids[(size_t)b * R + i];
       }
@@ -523,7 +470,7 @@ __global__ __launch_bounds__(TRACK_THREADS) void track_eval_kernel(const float* 
     const int pin = (live && p >= 0 && p < P) ? p : -1;
     bool twice = false;
     for (int k = 0; k < LAP_N; ++k) {
-      const int pk = lap_lane(pin, k);
+      const int pk = lane_of(pin, k);
       twice = twice || (k < t && pk >= 0 && pk == pin);
     }
     const bool ok = pin >= 0 && !twice;
@@ -554,7 +501,7 @@ __global__ __launch_bounds__(TRACK_THREADS) void track_eval_kernel(const float* 
     int n = 0;
     for (int j = 0; j < J; ++j)
       if (w[j] > 0.f) {
-        sum += track_eval_dist(x + j * hs, g + j * 3);
+        sum += dist3_exact(x + j * hs, g + j * 3);       // summed into dist_sum, compared bit for bit
         ++n;
       }
     s_d[a * LAP_N + h] = sum / (double)n;                                       // n >= 1: a person has a visible joint
@@ -579,7 +526,7 @@ __global__ __launch_bounds__(TRACK_THREADS) void track_eval_kernel(const float* 
     }
     bool keep = cand >= 0;
     for (int k = 0; k < LAP_N; ++k) {
-      const int ck = lap_lane(cand, k);
+      const int ck = lane_of(cand, k);
       if (k < t && ck >= 0 && ck == cand) keep = false;
     }
     if (keep) {
@@ -612,7 +559,7 @@ __global__ __launch_bounds__(TRACK_THREADS) void track_eval_kernel(const float* 
       s_nrh = __popcll(rh_mask);
     }
   }
-  s_scan[0][0][t] = over;                        // the scan is done with: the per-thread id_overflow counts
+  s_scan[0][0][t] = over;                        // `run` was last read barriers ago: the per-thread id_overflow counts
   __syncthreads();
   const int nrp = s_nrp, nrh = s_nrh;
   double moved[TE_GATHER];
@@ -684,8 +631,7 @@ extern "C" {
 
 int mvg_track_predict(int B, int T, int J, const int* id, float* pose, double* mean, double* var, double dt, double q, void* stream) {
   if (B < 1 || B > MVG_TRACK_MAX_B || T < 1 || T > MVG_TRACK_MAX_T || J < 1 || J > MVG_TRACK_MAX_J) return MVG_E_BADARG;
-  if (id == nullptr || pose == nullptr || mean == nullptr || var == nullptr) return MVG_E_BADARG;
-  if (((uintptr_t)mean & 7) || ((uintptr_t)var & 7)) return MVG_E_BADARG;
+  if (mvg_any_null({id, pose, mean, var}) || mvg_any_misaligned(8, {mean, var})) return MVG_E_BADARG;
   if (!(dt > 0.0) || !(dt <= 1.79769313486231570815e+308) || !track_noise_ok(q, true)) return MVG_E_BADARG;
   hipLaunchKernelGGL(track_predict_kernel, dim3(B), dim3(TRACK_THREADS), 0, (hipStream_t)stream, T, J, id, pose, mean, var, dt, q);
   MVG_LAUNCH_CHECK();
@@ -696,9 +642,7 @@ int mvg_track_correct(int B, int R, int T, int J, const int* id, const int* hits
                       double* mean, double* var, double r, double v0, float* row_pose, void* stream) {
   if (B < 1 || B > MVG_TRACK_MAX_B || R < 1 || R > MVG_TRACK_MAX_R || J < 1 || J > MVG_TRACK_MAX_J || T < 1 || T > MVG_TRACK_MAX_T)
     return MVG_E_BADARG;
-  if (id == nullptr || hits == nullptr || misses == nullptr || slots == nullptr || pose == nullptr) return MVG_E_BADARG;
-  if (mean == nullptr || var == nullptr || row_pose == nullptr) return MVG_E_BADARG;
-  if (((uintptr_t)mean & 7) || ((uintptr_t)var & 7)) return MVG_E_BADARG;
+  if (mvg_any_null({id, hits, misses, slots, pose, mean, var, row_pose}) || mvg_any_misaligned(8, {mean, var})) return MVG_E_BADARG;
   if (!track_noise_ok(r, false) || !track_noise_ok(v0, true)) return MVG_E_BADARG;
   hipLaunchKernelGGL(track_correct_kernel, dim3(B), dim3(TRACK_THREADS), 0, (hipStream_t)stream, R, T, J, id, hits, misses, slots, pose,
                      mean, var, r, v0, row_pose);
@@ -709,8 +653,7 @@ int mvg_track_correct(int B, int R, int T, int J, const int* id, const int* hits
 int mvg_linear_assignment(const double* cost, const int* n, const int* m, int B, int N, int M, int* col_of_row, double* total,
                           void* stream) {
   if (B < 1 || B > MVG_TRACK_MAX_B || N < 1 || N > MVG_LAP_MAX_N || M < 1 || M > MVG_LAP_MAX_N) return MVG_E_BADARG;
-  if (cost == nullptr || col_of_row == nullptr || total == nullptr) return MVG_E_BADARG;
-  if (((uintptr_t)cost & 7) || ((uintptr_t)total & 7)) return MVG_E_BADARG;
+  if (mvg_any_null({cost, col_of_row, total}) || mvg_any_misaligned(8, {cost, total})) return MVG_E_BADARG;
   hipLaunchKernelGGL(linear_assignment_kernel, dim3(B), dim3(LAP_N), 0, (hipStream_t)stream, cost, n, m, N, M, col_of_row, total);
   MVG_LAUNCH_CHECK();
   return 0;
@@ -722,9 +665,8 @@ int mvg_track_update(const float* dets, const int* count, int B, int R, int J, i
   if (B < 1 || B > MVG_TRACK_MAX_B || R < 1 || R > MVG_TRACK_MAX_R || J < 1 || J > MVG_TRACK_MAX_J || T < 1 || T > MVG_TRACK_MAX_T)
     return MVG_E_BADARG;
   if (!(max_dist >= 0.0) || max_dist > MVG_LAP_BIG || max_misses < 0 || min_hits < 0) return MVG_E_BADARG;
-  if (dets == nullptr || id == nullptr || hits == nullptr || misses == nullptr || born == nullptr || score == nullptr) return MVG_E_BADARG;
-  if (pose == nullptr || next_id == nullptr || state == nullptr || ids == nullptr || slots == nullptr) return MVG_E_BADARG;
-  if (((uintptr_t)born & 7) || ((uintptr_t)state & 7)) return MVG_E_BADARG;
+  if (mvg_any_null({dets, id, hits, misses, born, score, pose, next_id, state, ids, slots})) return MVG_E_BADARG;
+  if (mvg_any_misaligned(8, {born, state})) return MVG_E_BADARG;
   hipLaunchKernelGGL(track_update_kernel, dim3(B), dim3(TRACK_THREADS), 0, (hipStream_t)stream, dets, count, B, R, J, T, id, hits,
                      misses, (i64*)born, score, pose, next_id, (i64*)state, max_dist, max_misses, min_hits, ids, slots);
   MVG_LAUNCH_CHECK();
@@ -738,10 +680,9 @@ int mvg_track_eval(const float* dets, const int* count, const int* ids, const fl
   if (B < 1 || B > MVG_TRACK_MAX_B || R < 1 || R > MVG_TRACK_MAX_R || J < 1 || J > MVG_TRACK_MAX_J) return MVG_E_BADARG;
   if (G < 1 || P < G || P > MVG_TRACK_EVAL_MAX_P || K < 1 || K > MVG_TRACK_EVAL_MAX_K) return MVG_E_BADARG;
   if (!(dist_thr >= 0.0) || dist_thr > MVG_LAP_BIG) return MVG_E_BADARG;
-  if (dets == nullptr || ids == nullptr || joints_3d == nullptr || joints_3d_vis == nullptr || num_person == nullptr) return MVG_E_BADARG;
-  if (last_track == nullptr || counters == nullptr || dist_sum == nullptr || seen == nullptr || covered == nullptr) return MVG_E_BADARG;
-  if (overlap == nullptr) return MVG_E_BADARG;
-  if (((uintptr_t)counters & 7) || ((uintptr_t)dist_sum & 7) || ((uintptr_t)seen & 7) || ((uintptr_t)covered & 7)) return MVG_E_BADARG;
+  if (mvg_any_null({dets, ids, joints_3d, joints_3d_vis, num_person, last_track, counters, dist_sum, seen, covered, overlap}))
+    return MVG_E_BADARG;
+  if (mvg_any_misaligned(8, {counters, dist_sum, seen, covered})) return MVG_E_BADARG;
   hipLaunchKernelGGL(track_eval_kernel, dim3(B), dim3(TRACK_THREADS), 0, (hipStream_t)stream, dets, count, ids, row_pose, joints_3d,
                      joints_3d_vis, num_person, person_id, R, J, G, P, K, dist_thr, last_track, (i64*)counters, dist_sum, (i64*)seen,
                      (i64*)covered, overlap);
