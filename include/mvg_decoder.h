@@ -912,6 +912,44 @@ int mvg_structural_triangulate(const float* ud, const float* conf, const float* 
                                const int* count, const int* parent, const float* bone_len, int bone_len_per_person, int method,
                                int n_steps, float* X, int* status, int V, int B, int NQ, int P, int J, void* stream);
 
+/* ---- per-track bone lengths from the tracker's history (csrc/bones.hip) ------------------------------------------------------- */
+#define MVG_BONES_MAX_W 32            /* samples a slot's ring holds                                                           */
+
+/* The bone lengths of every tracked person, estimated over the frames the tracker has followed them, as the per-person bone_len
+ * of mvg_structural_triangulate: ONE launch per frame behind mvg_track_update (and mvg_track_correct), in front of
+ * mvg_structural_triangulate, one workgroup per stream, fixed shapes, nothing read back, NO atomics, every element with one
+ * writer, every loop counted: bit-reproducible, a stream's result does not depend on the others, capturable in a HIP graph.
+ *   dets (B, R, J, 5) fp32 and count (B, 2) int32 or NULL as mvg_pose_nms leaves them; slots (B, R) and id (B, T) int32 as
+ *   mvg_track_update leaves them: both are read only, nothing of the tracker's is written.  parent: J HOST ints, the tree of
+ *   mvg_structural_triangulate (parent[0] = -1, bone k = 1 .. J-1 ends at joint k), by value in the launch arguments.
+ *   State, owned by the caller: owner (B, T) int32, -1 at the start: the track id whose history the slot holds; seen (B, T) int32,
+ *   0 at the start; hist (B, T, W, J-1) fp32, the ring of the slot's last W samples; length (B, T, J-1) fp32, 0 at the start.
+ * Per stream b, in this order:
+ *   1. Ownership.  For every slot t with id[b, t] != owner[b, t]: owner = id, seen = 0, length[b, t, :] = 0 (a freed slot, id -1,
+ *      and a slot freed and reopened by the same update alike: a stream's ids never repeat).
+ *   2. Sample.  Row i is a detection iff i < count[b, 0] (clamped to [0, R]; every row without count) and dets[b, i, 0, 3] >= 0.
+ *      For every detection row with s = slots[b, i] in [0, T):  len[k-1] = (float) sqrt((dx*dx + dy*dy) + dz*dz) of joint k and
+ *      joint parent[k], k = 1 .. J-1, in fp64 from the RAW fp32 dets row (not the tracker's filtered pose), every product and sum
+ *      rounded on its own, correctly rounded sqrt, one rounding to fp32.  If all J-1 values are finite: hist[b, s, seen mod W, :]
+ *      = len, then seen = min(seen + 1, 2^30).  If several rows name the same slot (mvg_track_update never does that) the lowest
+ *      row is the sample and the others are none.
+ *   3. Estimate.  Only for the slots that took a sample in this call, with n = min(seen, W): length[b, s, k] = the median of
+ *      hist[b, s, 0 .. n-1, k]: the middle value for n odd, (float)(((double) lo + (double) hi) * 0.5) of the two middle values
+ *      for n even.  The values are selected by rank, rank = the number of smaller samples plus the number of equal samples at a
+ *      lower index: ties cannot change the value.
+ *   4. Rows, every element written by every call: row_length (B, R, J-1) fp32 and row_source (B, R) int32:
+ *      -1  the row is no detection: zeros;
+ *       0  a detection whose slot is in [0, T) with seen >= min_frames (as 2 left it): length of the slot;
+ *       1  otherwise, with fallback (J-1 fp32) given: fallback;
+ *       2  otherwise: the row's own len of 2 as computed, finite or not (the solver's status says what it made of them).
+ *      Detections behind the first MVG_TRACK_MAX_D have no slot and take 1 or 2.
+ * MVG_E_BADARG, and nothing launched, for B, R or T < 1 or above their MVG_TRACK_MAX_*, J < 2 or > MVG_ST_MAX_J, W < 1 or >
+ * MVG_BONES_MAX_W, min_frames < 1, a parent table that is no tree rooted at joint 0, a NULL pointer other than count and
+ * fallback. */
+int mvg_track_bones(const float* dets, const int* count, const int* slots, const int* id, const int* parent, int B, int R, int J,
+                    int T, int W, int min_frames, const float* fallback, int* owner, int* seen, float* hist, float* length,
+                    float* row_length, int* row_source, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

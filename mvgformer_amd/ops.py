@@ -1645,3 +1645,56 @@ def structural_triangulate(ud, conf, Pm, parent, bone_lengths, valid=None, rows=
     _launch(name, ud, conf, Pm, valid, rows, rows_ld, count, parent_c, bone_lengths, per_person, method_c, int(n_steps), X, status,
             V, B, NQ, P, J, label="structural_triangulate")
     return X, status
+
+
+BONES_MAX_W = _D["MVG_BONES_MAX_W"]
+_TRACK_BONES = _Layout("track_bones_buffers", ("owner", torch.int32, ("B", "T"), -1), ("seen", torch.int32, ("B", "T"), 0),
+                       ("hist", torch.float32, ("B", "T", "W", "K"), 0), ("length", torch.float32, ("B", "T", "K"), 0),
+                       ("row_length", torch.float32, ("B", "R", "K"), 0), ("row_source", torch.int32, ("B", "R"), -1))
+
+
+def _check_bones_limits(who, B, T, J, R, W):
+    _check_limits(who, ("B", B, TRACK_MAX_B), ("T", T, TRACK_MAX_T), ("J - 1", J - 1, ST_MAX_J - 1), ("R", R, TRACK_MAX_R),
+                  ("W", W, BONES_MAX_W))
+
+
+def track_bones_buffers(B, T, J, R, W, device="cuda"):
+    """the state of track_bones for B streams of T slots, J joints and a window of W frames -- owner (B, T) int32 filled with -1,
+    seen (B, T) int32, hist (B, T, W, J-1) fp32, length (B, T, J-1) fp32 -- plus the static outputs row_length (B, R, J-1) fp32 and
+    row_source (B, R) int32 (-1).  Allocated once and kept alive by the caller, like track_buffers."""
+    B, T, J, R, W = int(B), int(T), int(J), int(R), int(W)
+    _check_bones_limits("track_bones_buffers", B, T, J, R, W)
+    return _TRACK_BONES.alloc(dict(B=B, T=T, K=J - 1, R=R, W=W), device)
+
+
+def track_bones(dets, count, track_buffers, parent, bones_buffers, min_frames=4, fallback=None):
+    """One frame of the per-track bone-length estimate on the device (mvg_track_bones: one launch behind track_update /
+    track_correct, nothing read back, no atomics).  dets (B, R, J, 5) fp32 and count (B, 2) int32 or None as pose_nms leaves them;
+    ``track_buffers`` as track_update left them (its slots and id are read, nothing of it is written); parent: the tree as J host
+    ints (structural_check); ``bones_buffers`` from track_bones_buffers.  Every slot keeps the bone lengths of its track's last W
+    detections (W as the buffers have it) and their median; a slot that changed hands starts over.  -> (row_length (B, R, J-1)
+    fp32, row_source (B, R) int32), static tensors of ``bones_buffers``, per row of dets: the slot's median once the slot has
+    min_frames samples (source 0), else ``fallback`` (J-1 fp32; source 1) or, without one, the row's own lengths (source 2);
+    zeros and -1 for a row that is no detection.  row_length is the per-person bone_lengths of structural_triangulate."""
+    name = "mvg_track_bones"
+    slots, ident = track_buffers["slots"], track_buffers["id"]
+    tensors = [bones_buffers[k] for k in _TRACK_BONES.keys]
+    parent_c, _ = structural_check(parent)
+    B, R, J = _check_dets(name, dets, count)
+    if len(parent_c) != J:
+        raise RuntimeError("%s: a tree of %d joints for dets of %d joints" % (name, len(parent_c), J))
+    T = ident.shape[1] if ident.dim() == 2 else 0           # as many slots as the tracker's state has
+    hist = bones_buffers["hist"]
+    W = hist.shape[2] if hist.dim() == 4 else 0             # the window the caller's ring has
+    _TRACK.check(track_buffers, dict(B=B, T=T, J=J, R=R), ("slots", "id"), who=name)
+    _TRACK_BONES.check(bones_buffers, dict(B=B, T=T, K=J - 1, R=R, W=W), who=name)
+    if fallback is not None and (fallback.dtype != torch.float32 or tuple(fallback.shape) != (J - 1,)):
+        raise RuntimeError("%s: fallback (J-1) float32 or None expected" % name)
+    if not all(t is None or t.is_contiguous() for t in (dets, count, fallback)):
+        raise RuntimeError("%s: every tensor must be contiguous" % name)
+    L.require_cuda(dets, count, slots, ident, fallback, *tensors)        # behind the shape checks: those hold for any device
+    _check_bones_limits(name, B, T, J, R, W)
+    if int(min_frames) < 1:
+        raise L.MvgError("%s: min_frames >= 1 expected (got %r)" % (name, min_frames))
+    _launch(name, dets, count, slots, ident, parent_c, B, R, J, T, W, int(min_frames), fallback, *tensors, label="track_bones")
+    return bones_buffers["row_length"], bones_buffers["row_source"]

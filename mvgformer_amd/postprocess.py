@@ -45,6 +45,14 @@ the 15-joint tree.  ``refined`` = ``(poses (B, dets_rows, J, 3) fp32, status (B,
 (status 0: solved; rows behind the count: zeros, -1) and ``bone_lengths`` (J-1) fp32 are static tensors: new lengths written into
 ``bone_lengths`` take effect at the next run.  The projection matrices ``Pm`` come from the packed camera records and follow
 ``set_cameras``.
+
+``refine=dict(bone_lengths="track", window=8, min_frames=4, fallback=None | <J-1 values>, n_steps=1, method="ST")`` (requires
+``tracking`` as well) puts ``structural.BoneLengthEstimator.update`` behind the tracker (and ``track_evaluation``) and in front of
+the refiner, one more launch: every track's bone lengths are the median over its last ``window`` raw detections, and a row is
+solved under its own track's lengths once the track has ``min_frames`` samples, until then under ``fallback`` or, without one,
+the lengths the row has itself.  ``bone_lengths`` is then the (B, dets_rows, J-1) fp32 row tensor the solver reads,
+``bone_source`` (B, dets_rows) int32 where each row's lengths came from (0 track, 1 fallback, 2 the row itself, -1 no detection)
+and ``bone_estimator`` holds the histories (``.lengths()``, ``.reset()``).
 """
 from __future__ import annotations
 
@@ -59,8 +67,12 @@ OPTIONS = {
     "tracking": ({"max_tracks", "max_dist", "max_misses", "min_hits", "motion"}, "postprocess",
                  "tracking follows the rows the NMS keeps"),
     "track_evaluation": ({"dist_thr", "max_persons", "max_ids"}, "tracking", "track_evaluation scores the ids of the tracker"),
-    "refine": ({"bone_lengths", "n_steps", "method"}, "postprocess", "refine re-solves the rows the NMS keeps"),
+    "refine": ({"bone_lengths", "n_steps", "method", "window", "min_frames", "fallback"}, "postprocess",
+               "refine re-solves the rows the NMS keeps"),
 }
+# refine's bone_lengths="track" and the keys that belong to it alone
+TRACK_LENGTHS = "track"
+TRACK_LENGTH_KEYS = ("window", "min_frames", "fallback")
 
 
 def check_options(given):
@@ -75,6 +87,19 @@ def check_options(given):
             raise TypeError("PostProcess: unknown %s keys %s" % (name, sorted(unknown)))
     if given["postprocess"] is None:
         raise ValueError("PostProcess: nothing to run; it requires postprocess")
+    refine = given["refine"]
+    if refine is not None:
+        lengths = refine.get("bone_lengths")
+        if isinstance(lengths, str):
+            if lengths != TRACK_LENGTHS:
+                raise ValueError("PostProcess: refine bone_lengths = %r; the one name it knows is %r" % (lengths, TRACK_LENGTHS))
+            if given["tracking"] is None:
+                raise ValueError("PostProcess: refine with bone_lengths = %r estimates the lengths per track; it requires tracking"
+                                 % TRACK_LENGTHS)
+        else:
+            stray = sorted(k for k in TRACK_LENGTH_KEYS if k in refine)
+            if stray:
+                raise TypeError("PostProcess: refine keys %s belong to bone_lengths = %r" % (stray, TRACK_LENGTHS))
 
 
 class PostProcess:
@@ -126,13 +151,23 @@ class PostProcess:
                 self.tracker, dets, count, *self.ground_truth, person_id=self.person_id)))
         # structural triangulation of the kept queries (fixed bone lengths)
         self.refiner, self.refined, self.bone_lengths = None, None, None
+        self.bone_estimator, self.bone_source = None, None
         if refine is not None:
-            from .structural import PANOPTIC15_PARENT, StructuralRefiner
+            from .structural import PANOPTIC15_PARENT, BoneLengthEstimator, StructuralRefiner
             if convert_joint_format_indices is not None or num_joints != len(PANOPTIC15_PARENT):
                 raise ValueError("PostProcess: refine solves on the 15-joint tree of the decoder's own joints; it cannot be "
                                  "combined with convert_joint_format_indices")
             if rows > num_queries:              # postprocess["dets_rows"] is the caller's: keep has num_queries columns, no more
                 raise ValueError("PostProcess: refine with dets_rows = %d > num_queries = %d" % (rows, num_queries))
+            refine = dict(refine)
+            if isinstance(refine.get("bone_lengths"), str):         # check_options: it is TRACK_LENGTHS and there is a tracker
+                # the lengths of every row's track, estimated behind the tracker (and its scorer) and in front of the refiner
+                given = {k: refine.pop(k) for k in TRACK_LENGTH_KEYS if k in refine}
+                self.bone_estimator = BoneLengthEstimator(batch=batch, rows=rows, max_tracks=self.tracker.max_tracks,
+                                                          parent=PANOPTIC15_PARENT, device=dev, **given)
+                self.bone_source = self.bone_estimator.row_source
+                refine["bone_lengths"] = self.bone_estimator.row_length
+                self.stages.append((self.bone_estimator, lambda refs2d: self.bone_estimator.update(dets, count, self.tracker)))
             self.refiner = StructuralRefiner(batch=batch, rows=rows, parent=PANOPTIC15_PARENT, device=dev, **refine)
             self.refined = (self.refiner.poses, self.refiner.status)
             self.bone_lengths = self.refiner.bone_lengths

@@ -28,7 +28,7 @@ decoder, pins ``post.tensors()`` and puts ``post.snapshot()`` back after the war
 age and count nothing.  ``replay()`` still returns the five decoder outputs; ``runner.pred`` is the packed predictions
 (B, NQ, J, 5), and the pipeline's static tensors and stage objects are attributes of the runner under the same names
 (``detections``, ``evaluator``, ``ground_truth``, ``tracker``, ``track_ids``, ``track_poses``, ``track_evaluator``, ``person_id``,
-``refiner``, ``refined``, ``bone_lengths``; None for a stage that was not asked for):
+``refiner``, ``refined``, ``bone_lengths``, ``bone_estimator``, ``bone_source``; None for a stage that was not asked for):
 
         runner.replay()
         dets, count, keep = runner.detections
@@ -85,7 +85,7 @@ class GraphedDecoder:
             self.post = PostProcess(batch, num_queries, J, self.thr, dev, convert_joint_format_indices=convert_joint_format_indices,
                                     **stages).set_cameras(self.ctx.cams, self.V)
         for name in ("postprocess", "detections", "evaluator", "ground_truth", "tracker", "track_ids", "track_poses",
-                     "track_evaluator", "person_id", "refiner", "refined", "bone_lengths"):
+                     "track_evaluator", "person_id", "refiner", "refined", "bone_lengths", "bone_estimator", "bone_source"):
             setattr(self, name, getattr(self.post, name, None))         # static tensors and objects: bound once
 
     # ------------------------------------------------------------------ inputs (device-side copies on the current stream)

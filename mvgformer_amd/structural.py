@@ -19,7 +19,8 @@ import contextlib
 
 import torch
 
-__all__ = ["PANOPTIC15_PARENT", "H36M17_PARENT", "bone_lengths", "StructuralRefiner"]
+__all__ = ["PANOPTIC15_PARENT", "H36M17_PARENT", "bone_lengths", "StructuralRefiner"]      # what `import *` brings, pinned by a test;
+# BoneLengthEstimator (below) is imported by name
 
 # the 15-joint CMU Panoptic skeleton of the decoder (root: joint 0) and the 17-joint Human3.6M one
 PANOPTIC15_PARENT = (-1, 0, 0, 0, 3, 4, 2, 6, 7, 0, 9, 10, 2, 12, 13)
@@ -38,8 +39,10 @@ def bone_lengths(poses, parent):
 class StructuralRefiner:
     """batch, rows: B and R of the (B, R, J, 3) poses it writes; row r of element b is the query ``keep[b, r]`` the NMS kept.
     bone_lengths: J-1 values in the unit of the projection matrices' translations (mm), shared by every person; they live in the
-    static tensor ``self.bone_lengths`` and may be overwritten between updates.  n_steps (1 .. 8) and method ("ST", or "LS" for the
-    unconstrained least squares in the same bone coordinates) are fixed at construction."""
+    static tensor ``self.bone_lengths`` and may be overwritten between updates.  Or a static (B, rows, J-1) fp32 device tensor of
+    per-person lengths, row r for row r of the poses (``BoneLengthEstimator.row_length``): kept by reference and handed to the
+    solver in its per-person form.  n_steps (1 .. 8) and method ("ST", or "LS" for the unconstrained least squares in the same
+    bone coordinates) are fixed at construction."""
 
     def __init__(self, batch=1, rows=1024, parent=PANOPTIC15_PARENT, bone_lengths=None, n_steps=1, method="ST", device="cuda"):
         from . import ops
@@ -50,11 +53,21 @@ class StructuralRefiner:
         if bone_lengths is None:
             raise ValueError("StructuralRefiner: bone_lengths (%d values) are required" % (self.num_joints - 1))
         self.device = torch.device(device)
-        lengths = torch.as_tensor(bone_lengths, dtype=torch.float32).reshape(-1)
-        if lengths.numel() != self.num_joints - 1:
-            raise ValueError("StructuralRefiner: %d bone lengths for a tree of %d joints (%d expected)"
-                             % (lengths.numel(), self.num_joints, self.num_joints - 1))
-        self.bone_lengths = lengths.to(self.device).contiguous()
+        if torch.is_tensor(bone_lengths) and bone_lengths.dim() == 3:
+            # per-person lengths, a static tensor somebody else writes (BoneLengthEstimator.row_length): taken by reference
+            want = (self.batch, self.rows, self.num_joints - 1)
+            if tuple(bone_lengths.shape) != want or bone_lengths.dtype != torch.float32 or not bone_lengths.is_contiguous() \
+                    or bone_lengths.device.type != self.device.type:
+                raise ValueError("StructuralRefiner: per-person bone lengths must be a contiguous float32 tensor of shape %s on %s, "
+                                 "got %s %s on %s" % (want, self.device, bone_lengths.dtype, tuple(bone_lengths.shape),
+                                                      bone_lengths.device))
+            self.bone_lengths = bone_lengths
+        else:
+            lengths = torch.as_tensor(bone_lengths, dtype=torch.float32).reshape(-1)
+            if lengths.numel() != self.num_joints - 1:
+                raise ValueError("StructuralRefiner: %d bone lengths for a tree of %d joints (%d expected)"
+                                 % (lengths.numel(), self.num_joints, self.num_joints - 1))
+            self.bone_lengths = lengths.to(self.device).contiguous()
         self.buffers = ops.structural_buffers(self.batch, self.rows, self.num_joints, self.device)
 
     @property
@@ -80,3 +93,86 @@ class StructuralRefiner:
             ud, _ = ops.uncrop_undistort_jac(refs2d, cams, V, B)
             return ops.structural_triangulate(ud, None, Pm, self.parent, self.bone_lengths, rows=keep[:, :self.rows], count=count,
                                               n_steps=self.n_steps, method=self.method, out=self.buffers)
+
+
+class BoneLengthEstimator:
+    """The bone lengths of every tracked person, estimated on the device from the frames the tracker has followed them
+    (``ops.track_bones``, csrc/bones.hip: one launch per frame behind ``tracking.PoseTracker.update``, nothing read back, no
+    atomics): every track slot keeps the lengths of its track's last ``window`` detections and their median; a slot that changes
+    hands starts over.  ``row_length`` (B, rows, J-1) fp32 -- per row of the detections the median of its track once the track has
+    ``min_frames`` samples, else ``fallback`` (J-1 values) or, without one, the row's own lengths -- is what a ``StructuralRefiner``
+    takes as per-person ``bone_lengths``; ``row_source`` (B, rows) int32 says which of the three it was (0, 1, 2; -1: no detection).
+
+        estimator = BoneLengthEstimator(batch=1, rows=1024, max_tracks=32)
+        refiner = StructuralRefiner(batch=1, rows=1024, bone_lengths=estimator.row_length)
+        ids, slots = tracker.update(dets, count)
+        estimator.update(dets, count, tracker)                             # launch only
+        poses, status = refiner.update(refs2d, cams, Pm, keep, count)
+
+    The samples are taken from the raw detections, never from the tracker's filtered poses or the refiner's output: the estimate
+    does not feed on itself.  batch, rows and max_tracks are those of the tracker it follows."""
+
+    def __init__(self, batch=1, rows=1024, max_tracks=32, parent=PANOPTIC15_PARENT, window=8, min_frames=4, fallback=None,
+                 device="cuda"):
+        from . import ops
+        self.parent = tuple(int(p) for p in parent)
+        ops.structural_check(self.parent)
+        self.batch, self.rows, self.max_tracks, self.num_joints = int(batch), int(rows), int(max_tracks), len(self.parent)
+        self.window, self.min_frames = int(window), int(min_frames)
+        if not 1 <= self.window <= ops.BONES_MAX_W or self.min_frames < 1:
+            raise ValueError("BoneLengthEstimator: 1 <= window <= %d and min_frames >= 1 expected (got %r, %r)"
+                             % (ops.BONES_MAX_W, window, min_frames))
+        self.device = torch.device(device)
+        self.fallback = None
+        if fallback is not None:
+            values = torch.as_tensor(fallback, dtype=torch.float32).reshape(-1)
+            if values.numel() != self.num_joints - 1:
+                raise ValueError("BoneLengthEstimator: %d fallback lengths for a tree of %d joints (%d expected)"
+                                 % (values.numel(), self.num_joints, self.num_joints - 1))
+            self.fallback = values.to(self.device).contiguous()
+        self.buffers = ops.track_bones_buffers(self.batch, self.max_tracks, self.num_joints, self.rows, self.window, self.device)
+
+    @property
+    def row_length(self):
+        return self.buffers["row_length"]
+
+    @property
+    def row_source(self):
+        return self.buffers["row_source"]
+
+    def update(self, dets, count, tracker):
+        """dets (B, R, J, 5) fp32 and count (B, 2) int32 or None as ``tracker.update(dets, count)`` has just associated them ->
+        (row_length, row_source), static tensors that the next update overwrites.  One launch."""
+        from . import ops
+        with torch.cuda.device(dets.device) if dets.is_cuda else contextlib.nullcontext():
+            return ops.track_bones(dets, count, tracker.buffers, self.parent, self.buffers, self.min_frames, self.fallback)
+
+    def tensors(self):
+        """every device tensor ``update`` addresses besides its arguments (what a captured graph must keep alive)"""
+        return list(self.buffers.values()) + ([] if self.fallback is None else [self.fallback])
+
+    def reset(self):
+        """forget every history (device fills)"""
+        for k, t in self.buffers.items():
+            t.fill_(-1 if k in ("owner", "row_source") else 0)
+        return self
+
+    def snapshot(self):
+        """clones of the buffers (``restore`` puts them back: a graph capture's warm-up forwards must leave no history)"""
+        return {k: t.clone() for k, t in self.buffers.items()}
+
+    def restore(self, saved):
+        for k, t in self.buffers.items():
+            t.copy_(saved[k])
+        return self
+
+    def lengths(self):
+        """one read-back -> per stream {track id: (lengths (J-1) numpy fp32, seen)} of the slots that hold a live track's history"""
+        K = self.num_joints - 1
+        packed = torch.cat([self.buffers["owner"].reshape(-1).double(), self.buffers["seen"].reshape(-1).double(),
+                            self.buffers["length"].reshape(-1).double()]).cpu().numpy()
+        B, T = self.batch, self.max_tracks
+        owner, seen = packed[:B * T].reshape(B, T), packed[B * T:2 * B * T].reshape(B, T)
+        length = packed[2 * B * T:].reshape(B, T, K)
+        return [{int(owner[b, t]): (length[b, t].astype("float32"), int(seen[b, t])) for t in range(T) if owner[b, t] >= 0}
+                for b in range(B)]

@@ -21,7 +21,11 @@ frame loop then reads nothing back and the metrics are fetched once per threshol
 constant-velocity motion model.  ``--device-refine 1 --bone-lengths FILE.npy`` (on top of ``--device-nms 1``) re-solves the kept
 poses under the J-1 bone lengths of the file (mm) by structural triangulation (``structural.StructuralRefiner``, inside the HIP
 graph with ``--graph 1``) and reports the share of kept rows it solved and their mean absolute bone-length residual
-before and after.  ``--device-track-eval 1`` (on top of ``--device-track 1``) scores the track ids against the ground-truth
+before and after.  ``--bone-lengths track`` (with ``--device-track 1``; ``--bone-window``, ``--bone-min-frames``,
+``--bone-fallback FILE.npy``) solves every kept pose under the lengths estimated over its own track instead
+(``structural.BoneLengthEstimator``, one more launch between the tracker and the refiner); the report then also says which share of
+the kept rows took their track's lengths, the fallback or their own, and the residual is taken against the lengths each row was
+solved under.  ``--device-track-eval 1`` (on top of ``--device-track 1``) scores the track ids against the ground-truth
 identities of frames that carry ``joints_3d`` (``tracking.TrackEvaluator``: CLEAR-MOT counts, MOTA, MOTP, IDF1 per threshold).
 All of these stages are one ``postprocess.PostProcess`` per threshold, in both modes: the runner's (``runner.post``) with
 ``--graph 1``, one built from the same options and run behind the eager head with ``--graph 0``.
@@ -204,13 +208,24 @@ def main(argv=None):
                     help="1 (needs --device-nms 1 and --bone-lengths): the kept poses are re-solved under fixed bone lengths on the "
                          "device (structural.StructuralRefiner, two more launches per frame, inside the HIP graph with --graph 1)")
     ap.add_argument("--bone-lengths", default=None, help=".npy file with the J-1 bone lengths in mm (entry k-1: the bone that ends "
-                                                         "at joint k of structural.PANOPTIC15_PARENT) for --device-refine 1")
+                                                         "at joint k of structural.PANOPTIC15_PARENT) for --device-refine 1; or "
+                                                         "the word \"track\" (needs --device-track 1): every person is solved "
+                                                         "under the lengths estimated over its own track "
+                                                         "(structural.BoneLengthEstimator, one more launch per frame)")
     ap.add_argument("--refine-steps", type=int, default=1, help="n_steps of --device-refine 1 (1 .. 8)")
+    ap.add_argument("--bone-window", type=int, default=8, help="--bone-lengths track: frames of a track the median is taken over")
+    ap.add_argument("--bone-min-frames", type=int, default=4, help="--bone-lengths track: samples a track needs before its rows "
+                                                                   "are solved under its own lengths")
+    ap.add_argument("--bone-fallback", default=None, help="--bone-lengths track: .npy file with the J-1 lengths of a row whose "
+                                                          "track is younger (default: the lengths the row has itself)")
     args = ap.parse_args(argv)
+    track_lengths = args.bone_lengths == "track"
     if args.device_refine and not args.device_nms:
         ap.error("--device-refine 1 re-solves the rows of the device NMS: it requires --device-nms 1")
     if args.device_refine and not args.bone_lengths:
         ap.error("--device-refine 1 holds given bone lengths fixed: it requires --bone-lengths FILE.npy")
+    if args.device_refine and track_lengths and not args.device_track:
+        ap.error("--bone-lengths track estimates the lengths over the tracks of the device tracker: it requires --device-track 1")
     if args.device_track_motion and not args.device_track:
         ap.error("--device-track-motion 1 is an option of the device tracker: it requires --device-track 1")
     if args.device_track_eval and not args.device_track:
@@ -249,7 +264,13 @@ def main(argv=None):
         report["device_track_motion"] = True
     refine = None
     if args.device_refine:
-        refine = dict(bone_lengths=np.load(args.bone_lengths).astype(np.float32).reshape(-1), n_steps=args.refine_steps)
+        if track_lengths:
+            refine = dict(bone_lengths="track", window=args.bone_window, min_frames=args.bone_min_frames, n_steps=args.refine_steps,
+                          fallback=None if args.bone_fallback is None
+                          else np.load(args.bone_fallback).astype(np.float32).reshape(-1))
+            report["bone_lengths"] = "track"
+        else:
+            refine = dict(bone_lengths=np.load(args.bone_lengths).astype(np.float32).reshape(-1), n_steps=args.refine_steps)
         report["device_refine"] = True
     if args.device_eval:
         # which metric the ground truth gets (the rule of the host path below), and every frame's ground truth on the device
@@ -285,6 +306,7 @@ def main(argv=None):
         runner, post = None, None               # post: fresh stages (tracker, accumulators) per threshold pass
         if refine is not None:
             refine_sums = torch.zeros(4, dtype=torch.float64, device=dev)        # kept rows, solved rows, residual before, after
+            source_sums = torch.zeros(3, dtype=torch.int64, device=dev)
         if args.device_nms and not args.graph:
             post = PostProcess(1, head.num_instance, head.num_joints, thr, dev, **stages)
         for fi, (src, meta, gt) in enumerate(frames):
@@ -331,7 +353,11 @@ def main(argv=None):
                 want = post.bone_lengths.double()
                 before = (bone_lengths(dets[..., :3].double(), PANOPTIC15_PARENT) - want).abs().mean(-1)
                 after = (bone_lengths(poses.double(), PANOPTIC15_PARENT) - want).abs().mean(-1)
+                if track_lengths:                   # a row's own lengths may be non-finite; such a row is not solved
+                    before, after = (torch.where(solved, x, torch.zeros_like(x)) for x in (before, after))
                 refine_sums += torch.stack([live.sum(), solved.sum(), (before * solved).sum(), (after * solved).sum()])
+                if track_lengths:                                                # kept rows per source of their lengths
+                    source_sums += torch.stack([(live & (post.bone_source == s)).sum() for s in (0, 1, 2)])
             if args.device_nms and not args.device_eval:
                 dets, count, _ = post.detections                                 # static buffers, overwritten by the next frame
                 kept.extend(dets[b, :k].clone() for b, k in enumerate(count[:, 0].tolist()))   # the frame's one read-back
@@ -361,6 +387,9 @@ def main(argv=None):
             row["refine"] = {"kept_rows": int(n_live), "solved_share": round(n_solved / max(n_live, 1.0), 4),
                              "bone_residual_mm_before": round(before / max(n_solved, 1.0), 4),
                              "bone_residual_mm_after": round(after / max(n_solved, 1.0), 4)}
+            if track_lengths:
+                row["refine"]["length_source_share"] = {
+                    name: round(n / max(n_live, 1.0), 4) for name, n in zip(("track", "fallback", "own"), source_sums.tolist())}
         if gts and conv is not None:
             if np.asarray(gts[0]).shape[-2] == len(conv):
                 row["PCP"] = pcp_report(kept, gts, gts_vis, post.evaluator if args.device_eval else None)   # shelf.py:255-330
