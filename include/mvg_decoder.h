@@ -384,6 +384,49 @@ int mvg_triangulate_project(const float* r, const float* o, const float* cams, c
                             int V, int B, int NQ, int J, const int64_t* shapes_host, int L,
                             float* r_next, float* ref_lvl_next, uint8_t* inside_next, void* stream);
 
+/* ---- live-view table: the same launches on a per-stream subset of the V views ------------------------------------------------
+ * view_idx (B, V) i32: the live views of stream b in ascending order, padded with -1; n_live (B) i32: their count, >= 1.  Both on
+ * the device (a captured graph addresses them; mvgformer_amd.decoder.DecoderContext.set_live_views fills them).  Each entry point
+ * takes its namesake's arguments and the table in front of the stream, and gives -- bit for bit, in the slots of the live views --
+ * what the namesake gives when it is run on the live views alone; a dead view is not read (camera record, attn rows, pose outputs).
+ * V <= 64 for all six (checked by each; the projection, the bf16 chain and the triangulation keep a stream's live views in a 64-bit
+ * mask read from the V entries of its row).  The entries of view_idx must be -1 or in [0, V): the kernels shift and index by them
+ * unchecked, DecoderContext.set_live_views builds them on the host.
+ *   mvg_project_live                 pairs of a dead view: r = ref_lvl = 0, inside = 0
+ *   mvg_mean_views_live              (B: streams of the `rows` rows) live views added in ascending order, divided by n_live[b]
+ *   mvg_chain_update_ffn_class_live  the view mean of the row's stream (b = row / (NQ * J)): dead views add +0, divisor 1 / n_live[b];
+ *   ..._f32h_live
+ *   mvg_triangulate_live             lane `sub` of a problem takes the live views k = sub, sub + 8, ... < n_live[b]: softmax and Gram
+ *   mvg_triangulate_project_live     sums see the subset run's operands in its lanes; ref2d / proj2d / r_next / ref_lvl_next /
+ *                                    inside_next of dead views are zeros */
+int mvg_project_live(const float* X, const float* cams, const int64_t* shapes_host, int L, float* r, float* ref_lvl,
+                     uint8_t* inside, int V, int B, int Lq, const int32_t* view_idx, const int32_t* n_live, void* stream);
+int mvg_mean_views_live(const void* attn, int dtype, void* out, int V, int B, int rows, int C, const int32_t* view_idx,
+                        const int32_t* n_live, void* stream);
+int mvg_chain_update_ffn_class_live(const void* attn, int V, const float* tgt, const void* Wu, const float* bu,
+                                    const float* g2, const float* be2, const void* W1, const float* b1,
+                                    const void* W2, const float* b2, const float* g3, const float* be3,
+                                    const float* Wc, const float* bc, float threshold,
+                                    const uint8_t* forced_valid, float* tgt_out, float* prob, uint8_t* valid,
+                                    int* any_valid, const float* query_pos, const void* W_next, const float* b_next,
+                                    float* xw_next, int n_next, int B, int NQ, int J, int has_ffn, const uint8_t* attn_inside,
+                                    const int32_t* view_idx, const int32_t* n_live, void* stream);
+int mvg_chain_update_ffn_class_f32h_live(const float* attn, int V, const float* tgt, const void* Wu, int wu_scale, const float* bu,
+                                         const float* g2, const float* be2, const void* W1, int w1_scale, const float* b1,
+                                         const void* W2, int w2_scale, const float* b2, const float* g3, const float* be3,
+                                         const float* Wc, const float* bc, float threshold, const uint8_t* forced_valid,
+                                         float* tgt_out, float* prob, uint8_t* valid, int* any_valid, const float* query_pos,
+                                         const void* W_next, int wn_scale, const float* b_next, float* xw_next, int n_next, int B,
+                                         int NQ, int J, int has_ffn, const int32_t* view_idx, const int32_t* n_live, void* stream);
+int mvg_triangulate_live(const float* r, const float* o, const float* cams, const uint8_t* valid,
+                         const int* any_valid, float* new_ref, float* ref2d, float* proj2d,
+                         int V, int B, int NQ, int J, const int32_t* view_idx, const int32_t* n_live, void* stream);
+int mvg_triangulate_project_live(const float* r, const float* o, const float* cams, const uint8_t* valid,
+                                 const int* any_valid, float* new_ref, float* ref2d, float* proj2d,
+                                 int V, int B, int NQ, int J, const int64_t* shapes_host, int L,
+                                 float* r_next, float* ref_lvl_next, uint8_t* inside_next,
+                                 const int32_t* view_idx, const int32_t* n_live, void* stream);
+
 /* Training path: the refined 2D points ref2d (B, V, Lq, 2; network-image px) -> un-cropped, undistorted
  * original-image px ud (B, V, Lq, 2) (lib/models/dq_decoder.py:414-420, 119-204: inverse crop affine, K^-1, 5 fixed-point
  * iterations, K) and jac (B, V, Lq, 4) = the row-major 2 x 2 Jacobian d(ud) / d(ref2d) of every point (forward mode through the

@@ -131,7 +131,8 @@ class DecoderHead(nn.Module):
         With convert_joint_format_indices (Shelf / Campus: ground truth with len(indices) joints, dq_transformer.py:90-104,
         582-603) the matcher and the criterion get the indices as their joint map and the UNconverted decoder outputs -- there
         is no gather on the loss path -- and `out` is the converted dict, as in forward."""
-        from .decoder import DecoderContext
+        from .decoder import DecoderContext, refuse_live_views
+        refuse_live_views(context, "DecoderHead.forward_train")
         if self.criterion is None:
             raise RuntimeError("DecoderHead.forward_train: no criterion (set_criterion / factory.build_training_head)")
         dev = src_views[0].device
@@ -167,8 +168,9 @@ class DecoderHead(nn.Module):
         return out, loss_dict
 
     @torch.no_grad()
-    def forward(self, src_views, meta, spatial_shapes=None, level_start_index=None, threshold=0.1):
-        """src_views: list of L (V*B, C, H_l, W_l) backbone maps, view-major.  Returns (out dict, pred array)."""
+    def forward(self, src_views, meta, spatial_shapes=None, level_start_index=None, threshold=0.1, view_live=None):
+        """src_views: list of L (V*B, C, H_l, W_l) backbone maps, view-major.  Returns (out dict, pred array).
+        view_live: the mask of DecoderContext.set_live_views (DQDecoder.forward)."""
         dev = src_views[0].device
         V = len(meta)
         batch = src_views[0].shape[0] // V
@@ -179,7 +181,7 @@ class DecoderHead(nn.Module):
                                             t_pose=self.t_pose)
         hs, refs, refs2d, projs2d, classes = self.decoder(
             tgt.contiguous(), ref, src_views, meta, spatial_shapes, level_start_index, None,
-            query_pos=query_pos.contiguous(), threshold=threshold)
+            query_pos=query_pos.contiguous(), threshold=threshold, view_live=view_live)
         out = decoder_outputs_to_dict(hs, refs, refs2d, projs2d, classes, self.num_instance, self.num_joints,
                                       self.convert_joint_format_indices)
         return out, pack_predictions(out, threshold)

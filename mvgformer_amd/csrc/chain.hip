@@ -181,7 +181,11 @@ __device__ __forceinline__ void acc_to_x(char* __restrict__ xb, const f32x16 (&a
     }
 }
 
-template <int BRING, int NT, int JN, int RMT = 64>   // RMT rows per tile: 64 (4 persons of 15 joints) | 32 (2 persons: small launches)
+// LIVE: the view mean reads the live-view table (view_idx (B, V) ascending, -1 padded; n_live (B); lq = NQ * J rows per stream).  The
+// sum walks the views as without a table -- one accumulator, ascending -- and a dead view adds +0 unread, so the live views are added in
+// the order of a run on them alone (whose V <= 5 and groups-of-8 paths are both this one sequential sum); the divisor is the count
+// of the ROW's stream (a tile may span two).
+template <int BRING, int NT, int JN, int RMT = 64, bool LIVE = false>   // RMT rows per tile: 64 (4 persons of 15 joints) | 32 (2 persons: small launches)
 __global__ __launch_bounds__(NT) void chain_b_kernel(
     const bf16_t* __restrict__ attn, int V, const float* __restrict__ tgt, const bf16_t* __restrict__ Wu,
     const float* __restrict__ bu, const float* __restrict__ g2, const float* __restrict__ be2,
@@ -190,7 +194,8 @@ __global__ __launch_bounds__(NT) void chain_b_kernel(
     const float* __restrict__ Wc, const float* __restrict__ bc, float threshold, const uint8_t* __restrict__ forced,
     float* __restrict__ tgt_out, float* __restrict__ prob, uint8_t* __restrict__ valid, int* __restrict__ any_valid,
     const float* __restrict__ qpos, const bf16_t* __restrict__ Wn, const float* __restrict__ bn,
-    float* __restrict__ xw_next, int n_next, int rows, int J, int nq_total, int has_ffn, const uint8_t* __restrict__ inside) {
+    float* __restrict__ xw_next, int n_next, int rows, int J, int nq_total, int has_ffn, const uint8_t* __restrict__ inside,
+    const int* __restrict__ view_idx, const int* __restrict__ n_live, int lq) {
   constexpr int RM = RMT;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* act = smem;                       // RM x 256 bf16 : GEMM operand (mean, then t1)
@@ -272,6 +277,35 @@ __global__ __launch_bounds__(NT) void chain_b_kernel(
       const int c = u * NT + tid;
       off[u] = (long)(r0 + min(c >> 5, nrow - 1)) * 256 + (c & 31) * 8;
     }
+    // LIVE: the live views of every tile row's stream as a bit mask, built ONCE per workgroup -- thread i < RM for row i, from the V
+    // entries of the stream's row of the table whatever n_live says (padding skipped: independent loads, one round trip next to the
+    // flags') -- and kept in LDS, in the RM x 8 bytes of `pr`, which nothing else touches before the class head.  A dead view then
+    // simply clears the lane's (row slot, view) flag in front of the ballot, as a pair outside its image does: the loads and adds below
+    // are the code without a table.  (Masks per chunk in registers, tested per load, took the 64-row variant from 215 to 256 VGPRs
+    // with 75 spilled.)
+    unsigned long long* rowmask = reinterpret_cast<unsigned long long*>(pr);
+    if constexpr (LIVE) {
+      if (tid < RM) {
+        const int b = (r0 + min(tid, nrow - 1)) / lq;
+        unsigned long long m = 0ull;
+        for (int k = 0; k < V; ++k) {
+          const int v = view_idx[b * V + k];
+          m |= v >= 0 ? 1ull << v : 0ull;
+        }
+        rowmask[tid] = m;
+      }
+      __syncthreads();
+    }
+    // the lane's flag of load_flag's (row slot, view v0 + (lane & 7)) pair and that view's liveness -> the wavefront's 64 flags
+    auto flags_of = [&](const int v0) -> unsigned long long {
+      if constexpr (LIVE) {
+        const int slot = lane >> 3, trow = (slot >> 1) * (NT / 32) + wave * 2 + (slot & 1);
+        const bool alive = slot < 2 * NCHUNK && ((rowmask[min(trow, RM - 1)] >> (v0 + (lane & 7))) & 1ull);
+        return __ballot(flag != 0 && alive);
+      } else {
+        return inside ? __ballot(flag != 0) : ~0ull;
+      }
+    };
     const uint4* dummy = reinterpret_cast<const uint4*>(bu);
     // views in groups of KV, UC chunks of the thread in flight together (clamped / dummy address + select instead of a guard: a
     // guarded load makes hipcc wait vmcnt(0) per element).  Up to 5 views: one group, all chunks (20 loads); more: groups of 8, two chunks.
@@ -301,11 +335,11 @@ __global__ __launch_bounds__(NT) void chain_b_kernel(
         }
     };
     if (V <= 5) {
-      const unsigned long long m = inside ? __ballot(flag != 0) : ~0ull;
+      const unsigned long long m = flags_of(0);
       group(std::integral_constant<int, 5>{}, std::integral_constant<int, NCHUNK>{}, 0, 0, m);
     } else {
       for (int v0 = 0; v0 < V; v0 += 8) {
-        const unsigned long long m = inside ? __ballot(flag != 0) : ~0ull;
+        const unsigned long long m = flags_of(v0);
         if (inside && v0 + 8 < V) flag = load_flag(v0 + 8);        // the next group's flags, in flight under this group's rows
 #pragma unroll
         for (int u0 = 0; u0 < NCHUNK; u0 += 2) group(std::integral_constant<int, 8>{}, std::integral_constant<int, 2>{}, v0, u0, m);
@@ -318,7 +352,8 @@ __global__ __launch_bounds__(NT) void chain_b_kernel(
       unsigned* op = reinterpret_cast<unsigned*>(&o);
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
-        const float a = row < nrow ? sacc[u][2 * t] * inv : 0.f, b = row < nrow ? sacc[u][2 * t + 1] * inv : 0.f;
+        const float iv = LIVE ? 1.f / (float)__popcll(rowmask[LIVE ? row : 0]) : inv;
+        const float a = row < nrow ? sacc[u][2 * t] * iv : 0.f, b = row < nrow ? sacc[u][2 * t + 1] * iv : 0.f;
         op[t] = pack_bf16(a, b);
       }
       *reinterpret_cast<uint4*>(act + row * ACT_PITCH + v16 * 16) = o;
@@ -569,14 +604,17 @@ extern "C" int mvg_chain_attn_pose(const void* samp, const uint8_t* inside, cons
   return launch_chain_a<64, 256, 2>(samp, inside, Wp, bp, W0, b0, W1, b1, W2, b2, attn, o, order, o_masked, rows, st);
 }
 
-extern "C" int mvg_chain_update_ffn_class(const void* attn, int V, const float* tgt, const void* Wu, const float* bu,
+template <bool LIVE>
+static int launch_chain_b(const void* attn, int V, const float* tgt, const void* Wu, const float* bu,
                                           const float* g2, const float* be2, const void* W1, const float* b1,
                                           const void* W2, const float* b2, const float* g3, const float* be3,
                                           const float* Wc, const float* bc, float threshold, const uint8_t* forced_valid,
                                           float* tgt_out, float* prob, uint8_t* valid, int* any_valid,
                                           const float* query_pos, const void* W_next, const float* b_next,
                                           float* xw_next, int n_next, int B, int NQ, int J, int has_ffn,
-                                          const uint8_t* attn_inside, void* stream) {
+                                          const uint8_t* attn_inside, const int32_t* view_idx, const int32_t* n_live,
+                                          void* stream) {
+  if (LIVE && (!view_idx || !n_live || V > 64)) return MVG_E_BADARG;      // the kernel keeps a stream's live views in a 64-bit mask
   if (!attn || !tgt || !Wu || !bu || !g2 || !be2 || !Wc || !bc || !tgt_out || !prob || !valid || !any_valid) return MVG_E_BADARG;
   if (has_ffn && (!W1 || !b1 || !W2 || !b2 || !g3 || !be3)) return MVG_E_BADARG;
   if (V <= 0 || J <= 0 || J > 64 || B < 0 || NQ < 0) return MVG_E_BADARG;
@@ -593,22 +631,49 @@ extern "C" int mvg_chain_update_ffn_class(const void* attn, int V, const float* 
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MVG_MAX_DEVICES) return MVG_E_BADARG;
   const size_t lds64 = 2 * 64 * ACT_PITCH + 64 * XP + 64 * 2 * sizeof(float) + 9 * 256 * sizeof(float);
   if (!configured[dev]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&chain_b_kernel<4, 512, 1>),
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&chain_b_kernel<4, 512, 1, 64, LIVE>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds64);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&chain_b_kernel<4, 512, 1, 32>),
+    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&chain_b_kernel<4, 512, 1, 32, LIVE>),
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds64);
     if (e != hipSuccess) return (int)e;
     configured[dev] = true;
   }
   const dim3 grid((nq_total + qpt - 1) / qpt);
-#define MVG_CB(R, NTH, JNN, ...)                                                                                           \
-  hipLaunchKernelGGL((chain_b_kernel<R, NTH, JNN, ##__VA_ARGS__>), grid, dim3(NTH), lds, (hipStream_t)stream, (const bf16_t*)attn, V, tgt,  \
+#define MVG_CB(R, NTH, JNN, RMV)                                                                                           \
+  hipLaunchKernelGGL((chain_b_kernel<R, NTH, JNN, RMV, LIVE>), grid, dim3(NTH), lds, (hipStream_t)stream, (const bf16_t*)attn, V, tgt,  \
                      (const bf16_t*)Wu, bu, g2, be2, (const bf16_t*)W1, b1, (const bf16_t*)W2, b2, g3, be3, Wc, bc,     \
                      threshold, forced_valid, tgt_out, prob, valid, any_valid, query_pos, (const bf16_t*)W_next, b_next, xw_next,  \
-                     n_next, rows, J, nq_total, has_ffn, attn_inside)
+                     n_next, rows, J, nq_total, has_ffn, attn_inside, view_idx, n_live, NQ * J)
   if (small) MVG_CB(4, 512, 1, 32);
-  else MVG_CB(4, 512, 1);
+  else MVG_CB(4, 512, 1, 64);
 #undef MVG_CB
   MVG_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int mvg_chain_update_ffn_class(const void* attn, int V, const float* tgt, const void* Wu, const float* bu,
+                                          const float* g2, const float* be2, const void* W1, const float* b1,
+                                          const void* W2, const float* b2, const float* g3, const float* be3,
+                                          const float* Wc, const float* bc, float threshold, const uint8_t* forced_valid,
+                                          float* tgt_out, float* prob, uint8_t* valid, int* any_valid,
+                                          const float* query_pos, const void* W_next, const float* b_next,
+                                          float* xw_next, int n_next, int B, int NQ, int J, int has_ffn,
+                                          const uint8_t* attn_inside, void* stream) {
+  return launch_chain_b<false>(attn, V, tgt, Wu, bu, g2, be2, W1, b1, W2, b2, g3, be3, Wc, bc, threshold, forced_valid, tgt_out, prob,
+                               valid, any_valid, query_pos, W_next, b_next, xw_next, n_next, B, NQ, J, has_ffn, attn_inside, nullptr,
+                               nullptr, stream);
+}
+
+extern "C" int mvg_chain_update_ffn_class_live(const void* attn, int V, const float* tgt, const void* Wu, const float* bu,
+                                               const float* g2, const float* be2, const void* W1, const float* b1,
+                                               const void* W2, const float* b2, const float* g3, const float* be3,
+                                               const float* Wc, const float* bc, float threshold, const uint8_t* forced_valid,
+                                               float* tgt_out, float* prob, uint8_t* valid, int* any_valid,
+                                               const float* query_pos, const void* W_next, const float* b_next,
+                                               float* xw_next, int n_next, int B, int NQ, int J, int has_ffn,
+                                               const uint8_t* attn_inside, const int32_t* view_idx, const int32_t* n_live,
+                                               void* stream) {
+  return launch_chain_b<true>(attn, V, tgt, Wu, bu, g2, be2, W1, b1, W2, b2, g3, be3, Wc, bc, threshold, forced_valid, tgt_out, prob,
+                              valid, any_valid, query_pos, W_next, b_next, xw_next, n_next, B, NQ, J, has_ffn, attn_inside, view_idx,
+                              n_live, stream);
 }

@@ -530,7 +530,10 @@ __device__ __forceinline__ void write_row_h2(char* __restrict__ planes, int plan
 
 // MT = 1: 32-row tiles, two workgroups per CU (128 registers, fragment ring 2).  MT = 2: 64-row tiles, one workgroup per CU (135 KB, 256
 // registers, ring 4) -- half the fragment loads per row, six MFMAs per wavefront and k-step.  Same chunks, same order per row: bit-identical.
-template <int MT>
+// LIVE: the view mean reads the live-view table (view_idx (B, V) ascending, -1 padded; n_live (B); lq = NQ * J rows per stream): the
+// k-th step adds the k-th live view of the ROW's stream (a tile may span two), or +0 unread past their count -- the one sequential
+// sum of a run on the live views alone -- and the divisor is that count.
+template <int MT, bool LIVE = false>
 __global__ __launch_bounds__(NT, MT == 1 ? 4 : 2) void chain_b_f32h_kernel(
     const float* __restrict__ attn, int V, const float* __restrict__ tgt, const bf16_t* __restrict__ Wu, int su,
     const float* __restrict__ bu, const float* __restrict__ g2, const float* __restrict__ be2,
@@ -539,7 +542,8 @@ __global__ __launch_bounds__(NT, MT == 1 ? 4 : 2) void chain_b_f32h_kernel(
     const float* __restrict__ Wc, const float* __restrict__ bc, float threshold, const uint8_t* __restrict__ forced,
     float* __restrict__ tgt_out, float* __restrict__ prob, uint8_t* __restrict__ valid, int* __restrict__ any_valid,
     const float* __restrict__ qpos, const bf16_t* __restrict__ Wn, int sn, const float* __restrict__ bn,
-    float* __restrict__ xw_next, int n_next, int rows, int J, int nq_total, int has_ffn) {
+    float* __restrict__ xw_next, int n_next, int rows, int J, int nq_total, int has_ffn, const int* __restrict__ view_idx,
+    const int* __restrict__ n_live, int lq) {
   constexpr int RMT = 32 * MT, APL = RMT * PLP, RB = MT == 1 ? 2 : 4;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* act = smem;                                   // 2 planes x 32 rows x 256 columns: mean, then t1, then tgt' + query_pos
@@ -570,24 +574,46 @@ __global__ __launch_bounds__(NT, MT == 1 ? 4 : 2) void chain_b_f32h_kernel(
     f32x4 sacc[NCH];
 #pragma unroll
     for (int i = 0; i < NCH; ++i) sacc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    int lb[LIVE ? NCH : 1], ln[LIVE ? NCH : 1], lv0[LIVE ? NCH : 1];      // LIVE: stream of chunk i's row, its live views, the first of them
+    if constexpr (LIVE) {
+#pragma unroll
+      for (int i = 0; i < NCH; ++i) {
+        lb[i] = (r0 + min(8 * i + w, nrow - 1)) / lq;
+        ln[i] = n_live[lb[i]];
+        lv0[i] = view_idx[lb[i] * V];
+      }
+    }
     for (int v = 0; v < V; v += 2) {
       f32x4 xv[2][NCH];
 #pragma unroll
       for (int u = 0; u < 2; ++u)
 #pragma unroll
-        for (int i = 0; i < NCH; ++i)
-          xv[u][i] = *reinterpret_cast<const f32x4*>(attn + ((long)min(v + u, V - 1) * rows + r0 + min(8 * i + w, nrow - 1)) * 256 + lane * 4);
+        for (int i = 0; i < NCH; ++i) {
+          int vw = min(v + u, V - 1);
+          if constexpr (LIVE) {       // the row's entry itself (no wait for n_live); past the live views: the first one, an address only
+            const int raw = view_idx[lb[i] * V + vw];
+            vw = raw >= 0 ? raw : lv0[i];
+          }
+          xv[u][i] = *reinterpret_cast<const f32x4*>(attn + ((long)vw * rows + r0 + min(8 * i + w, nrow - 1)) * 256 + lane * 4);
+        }
 #pragma unroll
       for (int i = 0; i < NCH; ++i) {
-        sacc[i] += xv[0][i];
-        if (v + 1 < V) sacc[i] += xv[1][i];
+        if constexpr (LIVE) {
+          const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+          sacc[i] += v < ln[i] ? xv[0][i] : z;
+          if (v + 1 < V) sacc[i] += v + 1 < ln[i] ? xv[1][i] : z;
+        } else {
+          sacc[i] += xv[0][i];
+          if (v + 1 < V) sacc[i] += xv[1][i];
+        }
       }
     }
     const float Vf = (float)V;
 #pragma unroll
     for (int i = 0; i < NCH; ++i) {
       const int row = 8 * i + w;
-      f32x4 m4 = {sacc[i][0] / Vf, sacc[i][1] / Vf, sacc[i][2] / Vf, sacc[i][3] / Vf};
+      const float nf = LIVE ? (float)ln[LIVE ? i : 0] : Vf;
+      f32x4 m4 = {sacc[i][0] / nf, sacc[i][1] / nf, sacc[i][2] / nf, sacc[i][3] / nf};
       if (row >= nrow) m4 = f32x4{0.f, 0.f, 0.f, 0.f};
       float m = fmaxf(fmaxf(fabsf(m4[0]), fabsf(m4[1])), fmaxf(fabsf(m4[2]), fabsf(m4[3])));
 #pragma unroll
@@ -806,13 +832,15 @@ int cu_count() {
 }  // namespace
 
 
-extern "C" int mvg_chain_update_ffn_class_f32h(const float* attn, int V, const float* tgt, const void* Wu, int wu_scale, const float* bu,
+template <bool LIVE>
+static int launch_chain_b_f32h(const float* attn, int V, const float* tgt, const void* Wu, int wu_scale, const float* bu,
                                               const float* g2, const float* be2, const void* W1, int w1_scale, const float* b1,
                                               const void* W2, int w2_scale, const float* b2, const float* g3, const float* be3,
                                               const float* Wc, const float* bc, float threshold, const uint8_t* forced_valid,
                                               float* tgt_out, float* prob, uint8_t* valid, int* any_valid, const float* query_pos,
                                               const void* W_next, int wn_scale, const float* b_next, float* xw_next, int n_next, int B,
-                                              int NQ, int J, int has_ffn, void* stream) {
+                                              int NQ, int J, int has_ffn, const int32_t* view_idx, const int32_t* n_live, void* stream) {
+  if (LIVE && (!view_idx || !n_live || V > 64)) return MVG_E_BADARG;      // one bound on V for every entry point that takes a table
   if (!attn || !tgt || !Wu || !bu || !g2 || !be2 || !Wc || !bc || !tgt_out || !prob || !valid || !any_valid) return MVG_E_BADARG;
   if (has_ffn && (!W1 || !b1 || !W2 || !b2 || !g3 || !be3)) return MVG_E_BADARG;
   if (V <= 0 || J <= 0 || J > 32 || B < 0 || NQ < 0) return MVG_E_BADARG;
@@ -831,16 +859,41 @@ extern "C" int mvg_chain_update_ffn_class_f32h(const float* attn, int V, const f
     constexpr int R = 32 * MTV;                                                                                                        \
     const int qpt = R / J;                                                                                                             \
     const size_t lds = 4 * R * PLP + (3 * R * 8 + R * 2) * sizeof(float) + 2 * R * sizeof(int);                                        \
-    if (int rc = configure_lds(&chain_b_f32h_kernel<MTV>, lds, CFG)) return rc;                                                        \
-    hipLaunchKernelGGL(chain_b_f32h_kernel<MTV>, dim3((nq_total + qpt - 1) / qpt), dim3(NT), lds, (hipStream_t)stream, attn, V, tgt,   \
+    if (int rc = configure_lds(&chain_b_f32h_kernel<MTV, LIVE>, lds, CFG)) return rc;                                                  \
+    hipLaunchKernelGGL((chain_b_f32h_kernel<MTV, LIVE>), dim3((nq_total + qpt - 1) / qpt), dim3(NT), lds, (hipStream_t)stream, attn, V, tgt,   \
                        (const bf16_t*)Wu, wu_scale, bu, g2, be2, (const bf16_t*)W1, w1_scale, b1, (const bf16_t*)W2, w2_scale, b2, g3,  \
                        be3, Wc, bc, threshold, forced_valid, tgt_out, prob, valid, any_valid, query_pos, (const bf16_t*)W_next,        \
-                       wn_scale, b_next, xw_next, n_next, rows, J, nq_total, has_ffn);                                                 \
+                       wn_scale, b_next, xw_next, n_next, rows, J, nq_total, has_ffn, view_idx, n_live, NQ * J);                      \
   }
   if (big) MVG_CBH(2, configured2) else MVG_CBH(1, configured)
 #undef MVG_CBH
   MVG_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int mvg_chain_update_ffn_class_f32h(const float* attn, int V, const float* tgt, const void* Wu, int wu_scale, const float* bu,
+                                              const float* g2, const float* be2, const void* W1, int w1_scale, const float* b1,
+                                              const void* W2, int w2_scale, const float* b2, const float* g3, const float* be3,
+                                              const float* Wc, const float* bc, float threshold, const uint8_t* forced_valid,
+                                              float* tgt_out, float* prob, uint8_t* valid, int* any_valid, const float* query_pos,
+                                              const void* W_next, int wn_scale, const float* b_next, float* xw_next, int n_next, int B,
+                                              int NQ, int J, int has_ffn, void* stream) {
+  return launch_chain_b_f32h<false>(attn, V, tgt, Wu, wu_scale, bu, g2, be2, W1, w1_scale, b1, W2, w2_scale, b2, g3, be3, Wc, bc, threshold,
+                                    forced_valid, tgt_out, prob, valid, any_valid, query_pos, W_next, wn_scale, b_next, xw_next, n_next, B,
+                                    NQ, J, has_ffn, nullptr, nullptr, stream);
+}
+
+extern "C" int mvg_chain_update_ffn_class_f32h_live(const float* attn, int V, const float* tgt, const void* Wu, int wu_scale,
+                                                   const float* bu, const float* g2, const float* be2, const void* W1, int w1_scale,
+                                                   const float* b1, const void* W2, int w2_scale, const float* b2, const float* g3,
+                                                   const float* be3, const float* Wc, const float* bc, float threshold,
+                                                   const uint8_t* forced_valid, float* tgt_out, float* prob, uint8_t* valid,
+                                                   int* any_valid, const float* query_pos, const void* W_next, int wn_scale,
+                                                   const float* b_next, float* xw_next, int n_next, int B, int NQ, int J, int has_ffn,
+                                                   const int32_t* view_idx, const int32_t* n_live, void* stream) {
+  return launch_chain_b_f32h<true>(attn, V, tgt, Wu, wu_scale, bu, g2, be2, W1, w1_scale, b1, W2, w2_scale, b2, g3, be3, Wc, bc, threshold,
+                                   forced_valid, tgt_out, prob, valid, any_valid, query_pos, W_next, wn_scale, b_next, xw_next, n_next, B,
+                                   NQ, J, has_ffn, view_idx, n_live, stream);
 }
 
 extern "C" int mvg_chain_attn_pose_f32h(const float* samp, const uint8_t* inside, const void* Wp, int wp_scale, const float* bp,

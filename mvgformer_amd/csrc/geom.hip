@@ -104,15 +104,49 @@ __device__ __forceinline__ void project_point(const float x0, const float x1, co
   inside[idx] = in_img ? 1 : 0;
 }
 
+// Live-view table (DecoderContext.set_live_views): view_idx (B, V) holds the live views of stream b in ascending order, padded with
+// -1; n_live (B) their count.  A kernel built with LIVE = true reads it; LIVE = false is the code without a table.
+// The live views of stream b as a bit mask (V <= 64; their count is its popcount): the V entries of the row are read whatever n_live
+// says (the padding is skipped), so the loads are independent of each other and of n_live -- ONE memory round trip in front of
+// whatever the mask decides, and the same addresses in every lane of a stream (a broadcast).
+__device__ __forceinline__ unsigned long long live_view_mask(const int* __restrict__ view_idx, const int V, const int b) {
+  unsigned long long m = 0ull;
+  for (int k = 0; k < V; ++k) {
+    const int v = view_idx[b * V + k];
+    m |= v >= 0 ? 1ull << v : 0ull;
+  }
+  return m;
+}
+
+// what a pair of a view that is not live gets: outside its image, reference point 0 (the camera record is not read)
+__device__ __forceinline__ void project_dead(const LevelTable& lv, float* __restrict__ r, float* __restrict__ ref_lvl,
+                                             uint8_t* __restrict__ inside, const long idx) {
+  r[idx * 2] = 0.f;
+  r[idx * 2 + 1] = 0.f;
+  for (int l = 0; l < lv.L; ++l) {
+    ref_lvl[(idx * lv.L + l) * 2] = 0.f;
+    ref_lvl[(idx * lv.L + l) * 2 + 1] = 0.f;
+  }
+  inside[idx] = 0;
+}
+
+template <bool LIVE>
 __global__ __launch_bounds__(256) void project_kernel(const float* __restrict__ X, const float* __restrict__ cams,
                                                       LevelTable lv, float* __restrict__ r,
                                                       float* __restrict__ ref_lvl, uint8_t* __restrict__ inside,
-                                                      int B, int Lq, long total) {
+                                                      int B, int Lq, long total, const int* __restrict__ view_idx,
+                                                      const int* __restrict__ n_live, int V) {
   const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= total) return;
   const int q = (int)(idx % Lq);
   const int n = (int)(idx / Lq);
   const int b = n % B;
+  if constexpr (LIVE) {
+    if (!((live_view_mask(view_idx, V, b) >> (n / B)) & 1ull)) {
+      project_dead(lv, r, ref_lvl, inside, idx);
+      return;
+    }
+  }
   const float* xp = X + ((long)b * Lq + q) * 3;
   project_point(xp[0], xp[1], xp[2], cams + (long)n * MVG_CAM_STRIDE, lv, r, ref_lvl, inside, idx);
 }
@@ -164,14 +198,25 @@ __global__ __launch_bounds__(256) void gather_ref_kernel(const T* __restrict__ f
 }
 
 // ------------------------------------------------------------------------------------------
-template <typename T>
+// LIVE: the live views of the element's stream (stream4 elements of four per stream) in ascending order, as a run on those views
+// alone adds them; the divisor is their count
+template <typename T, bool LIVE>
 __global__ __launch_bounds__(256) void mean_views_kernel(const T* __restrict__ attn, T* __restrict__ out, int V,
-                                                         long n4) {
+                                                         long n4, const int* __restrict__ view_idx,
+                                                         const int* __restrict__ n_live, long stream4) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n4) return;
-  f32x4 acc = Vec4<T>::load(attn + i * 4);
-  for (int v = 1; v < V; ++v) acc += Vec4<T>::load(attn + ((long)v * n4 + i) * 4);
-  Vec4<T>::store(out + i * 4, acc / (float)V);
+  if constexpr (LIVE) {
+    const int b = (int)(i / stream4), n = n_live[b];
+    const int* vi = view_idx + (long)b * V;
+    f32x4 acc = Vec4<T>::load(attn + ((long)vi[0] * n4 + i) * 4);
+    for (int k = 1; k < n; ++k) acc += Vec4<T>::load(attn + ((long)vi[k] * n4 + i) * 4);
+    Vec4<T>::store(out + i * 4, acc / (float)n);
+  } else {
+    f32x4 acc = Vec4<T>::load(attn + i * 4);
+    for (int v = 1; v < V; ++v) acc += Vec4<T>::load(attn + ((long)v * n4 + i) * 4);
+    Vec4<T>::store(out + i * 4, acc / (float)V);
+  }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -606,7 +651,11 @@ MVG_STAMP_LOG(tri_stamps, 4096, 12, mvg_tri_read_stamps)
 #define TSTAMP_FLUSH()
 #endif
 
-template <bool LANES>
+// LIVE (view_idx, n_live: the live-view table, see live_view_mask): lane `sub` of a problem takes the live views k = sub, sub + 8, ...
+// of its stream, k < n_live[b], v = view_idx[b][k] -- max8 / add8 and the eight-way Gram sum see the operands of a run on the live
+// views alone, in the same lanes (a zero weight for the dead views would not: the DPP trees group by lane).  The 2D outputs and
+// the next layer's projections of the dead views are zeros.
+template <bool LANES, bool LIVE>
 __global__ __launch_bounds__(512) void triangulate_kernel(const float* __restrict__ r, const float* __restrict__ o,
                                                           const float* __restrict__ cams,
                                                           const uint8_t* __restrict__ valid,
@@ -615,7 +664,9 @@ __global__ __launch_bounds__(512) void triangulate_kernel(const float* __restric
                                                           float* __restrict__ proj2d, int V, int B, int NQ, int J,
                                                           LevelTable lv, float* __restrict__ r_next,
                                                           float* __restrict__ ref_lvl_next,
-                                                          uint8_t* __restrict__ inside_next) {
+                                                          uint8_t* __restrict__ inside_next,
+                                                          const int* __restrict__ view_idx,
+                                                          const int* __restrict__ n_live) {
   __shared__ double gram[10][TRI_PROBS][TRI_PAD];
   __shared__ float xnew[TRI_PROBS][3];
   TSTAMP_DECL;
@@ -624,6 +675,7 @@ __global__ __launch_bounds__(512) void triangulate_kernel(const float* __restric
   const int tid = threadIdx.x, pl = tid >> 3, sub = tid & 7;
   const int Lq = NQ * J;
   const long nprob = (long)B * Lq;
+  unsigned long long lmask = 0ull;                    // LIVE: the live views of the problem's stream (live_view_mask), for phase 3 too
   {
     long idx = (long)blockIdx.x * TRI_PROBS + pl;
     const bool live = idx < nprob;
@@ -636,8 +688,20 @@ __global__ __launch_bounds__(512) void triangulate_kernel(const float* __restric
     // Everything this lane needs is REQUESTED first -- validity, and per view of the lane (views sub, sub + 8, ...; the first
     // one held in registers) the three pose outputs, the reference point and the camera record -- so that the kernel pays one
     // memory round trip, not a chain of them (logits -> softmax -> per-view loads): it runs on 240 wavefronts' latency.
-    const long pair0 = ((long)min(sub, V - 1) * B + b) * Lq + q;
-    const float* cam0 = cams + ((long)min(sub, V - 1) * B + b) * MVG_CAM_STRIDE;
+    int nv = V;                                       // views of the problem; its k-th one
+    const int* vi = view_idx + (LIVE ? (long)b * V : 0);
+    auto view = [&](const int k) { if constexpr (LIVE) return vi[k]; else return k; };
+    int vfirst = min(sub, V - 1);
+    if constexpr (LIVE) {
+      // the lane's first view straight from the row (a lane past the live views takes the first live one: an address to read, its
+      // values are not used) next to the mask: one round trip in front of the loads below, none through n_live
+      const int vraw = sub < V ? vi[sub] : -1, v0 = vi[0];
+      lmask = live_view_mask(view_idx, V, b);
+      nv = __popcll(lmask);
+      vfirst = vraw >= 0 ? vraw : v0;
+    }
+    const long pair0 = ((long)vfirst * B + b) * Lq + q;
+    const float* cam0 = cams + ((long)vfirst * B + b) * MVG_CAM_STRIDE;
     const float o0x = o[pair0 * 3], o0y = o[pair0 * 3 + 1], o0l = o[pair0 * 3 + 2];
     const float2 r0 = *reinterpret_cast<const float2*>(r + pair0 * 2);
     float camr[40];
@@ -645,20 +709,21 @@ __global__ __launch_bounds__(512) void triangulate_kernel(const float* __restric
     for (int k = 0; k < 40; k += 4) *reinterpret_cast<f32x4*>(&camr[k]) = *reinterpret_cast<const f32x4*>(cam0 + k);
 
     // softmax over views of the confidence logit (dq_decoder.py:706-707)
-    float mx = sub < V ? o0l : -INFINITY;
-    for (int v = sub + 8; v < V; v += 8) mx = fmaxf(mx, o[(((long)v * B + b) * Lq + q) * 3 + 2]);
+    float mx = sub < nv ? o0l : -INFINITY;
+    for (int k = sub + 8; k < nv; k += 8) mx = fmaxf(mx, o[(((long)view(k) * B + b) * Lq + q) * 3 + 2]);
     mx = max8(mx);
-    float den = sub < V ? expf(o0l - mx) : 0.f;
-    for (int v = sub + 8; v < V; v += 8) den += expf(o[(((long)v * B + b) * Lq + q) * 3 + 2] - mx);
+    float den = sub < nv ? expf(o0l - mx) : 0.f;
+    for (int k = sub + 8; k < nv; k += 8) den += expf(o[(((long)view(k) * B + b) * Lq + q) * 3 + 2] - mx);
     den = add8(den);
 
     double G[10];
 #pragma unroll
     for (int e = 0; e < 10; ++e) G[e] = 0.0;
 
-    for (int v = sub; v < V; v += 8) {
+    for (int k = sub; k < nv; k += 8) {
+      const int v = view(k);
       const long pair = ((long)v * B + b) * Lq + q;
-      const bool first = v == sub;
+      const bool first = k == sub;
       float cam[40];
       if (first) {
 #pragma unroll
@@ -718,6 +783,15 @@ __global__ __launch_bounds__(512) void triangulate_kernel(const float* __restric
       for (int a = 0; a < 4; ++a)
 #pragma unroll
         for (int c = a; c < 4; ++c, ++e) G[e] += (double)a1[a] * (double)a1[c] + (double)a2[a] * (double)a2[c];
+    }
+    if constexpr (LIVE) {
+      if (live)
+        for (int v = sub; v < V; v += 8)
+          if (!((lmask >> v) & 1ull)) {
+            const long oidx = (((long)b * V + v) * Lq + q) * 2;
+            *reinterpret_cast<float2*>(ref2d + oidx) = make_float2(0.f, 0.f);
+            *reinterpret_cast<float2*>(proj2d + oidx) = make_float2(0.f, 0.f);
+          }
     }
 #pragma unroll
     for (int e = 0; e < 10; ++e) gram[e][pl][sub] = G[e];
@@ -874,6 +948,12 @@ __global__ __launch_bounds__(512) void triangulate_kernel(const float* __restric
       const float x0 = xnew[pl][0], x1 = xnew[pl][1], x2 = xnew[pl][2];
       for (int v = sub; v < V; v += 8) {
         const long n = (long)v * B + b;
+        if constexpr (LIVE) {
+          if (!((lmask >> v) & 1ull)) {
+            project_dead(lv, r_next, ref_lvl_next, inside_next, n * Lq + q);
+            continue;
+          }
+        }
         project_point(x0, x1, x2, cams + n * MVG_CAM_STRIDE, lv, r_next, ref_lvl_next, inside_next, n * Lq + q);
       }
     }
@@ -1445,19 +1525,33 @@ int mvg_pack_pyramid(const float* const* src_nchw_host, void* feat, int dtype, i
   return 0;
 }
 
-int mvg_project(const float* X, const float* cams, const int64_t* shapes_host, int L, float* r, float* ref_lvl,
-                uint8_t* inside, int V, int B, int Lq, void* stream) {
+extern "C++" {
+template <bool LIVE>
+static int launch_project(const float* X, const float* cams, const int64_t* shapes_host, int L, float* r, float* ref_lvl,
+                          uint8_t* inside, int V, int B, int Lq, const int32_t* view_idx, const int32_t* n_live, void* stream) {
   if (!X || !cams || !shapes_host || !r || !ref_lvl || !inside || V <= 0 || B <= 0 || Lq < 0) return MVG_E_BADARG;
+  if (LIVE && (!view_idx || !n_live || V > 64)) return MVG_E_BADARG;     // live_view_mask: 64 bits
   LevelTable lv;
   int64_t zeros[MVG_MAX_LEVELS] = {0};
   int e = mvg_fill_levels(&lv, shapes_host, zeros, L);
   if (e) return e;
   const long total = (long)V * B * Lq;
   if (total == 0) return 0;
-  hipLaunchKernelGGL(project_kernel, dim3(mvg_ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream, X, cams, lv, r,
-                     ref_lvl, inside, B, Lq, total);
+  hipLaunchKernelGGL(project_kernel<LIVE>, dim3(mvg_ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream, X, cams, lv, r,
+                     ref_lvl, inside, B, Lq, total, view_idx, n_live, V);
   MVG_LAUNCH_CHECK();
   return 0;
+}
+}  // extern "C++"
+
+int mvg_project(const float* X, const float* cams, const int64_t* shapes_host, int L, float* r, float* ref_lvl,
+                uint8_t* inside, int V, int B, int Lq, void* stream) {
+  return launch_project<false>(X, cams, shapes_host, L, r, ref_lvl, inside, V, B, Lq, nullptr, nullptr, stream);
+}
+
+int mvg_project_live(const float* X, const float* cams, const int64_t* shapes_host, int L, float* r, float* ref_lvl,
+                     uint8_t* inside, int V, int B, int Lq, const int32_t* view_idx, const int32_t* n_live, void* stream) {
+  return launch_project<true>(X, cams, shapes_host, L, r, ref_lvl, inside, V, B, Lq, view_idx, n_live, stream);
 }
 
 size_t mvg_bin_pairs_workspace(int N_img, int Lq) {
@@ -1531,19 +1625,36 @@ int mvg_gather_ref(const void* feat, int dtype, const float* ref_lvl, const floa
   return 0;
 }
 
-int mvg_mean_views(const void* attn, int dtype, void* out, int V, int rows, int C, void* stream) {
+extern "C++" {
+template <bool LIVE>
+static int launch_mean_views(const void* attn, int dtype, void* out, int V, int B, int rows, int C, const int32_t* view_idx,
+                             const int32_t* n_live, void* stream) {
   if (!attn || !out || V <= 0 || rows < 0 || C % 4 != 0) return MVG_E_BADARG;
+  if (LIVE && (!view_idx || !n_live || V > 64 || B <= 0 || rows % B != 0)) return MVG_E_BADARG;     // (V: the bound of all live entry points)
   const long n4 = (long)rows * C / 4;
   if (n4 == 0) return 0;
+  const long stream4 = LIVE ? n4 / B : n4;
   const int grid = mvg_ceil_div(n4, 256);
   if (dtype == MVG_F32)
-    hipLaunchKernelGGL((mean_views_kernel<float>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const float*)attn, (float*)out, V, n4);
+    hipLaunchKernelGGL((mean_views_kernel<float, LIVE>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const float*)attn,
+                       (float*)out, V, n4, view_idx, n_live, stream4);
   else if (dtype == MVG_BF16)
-    hipLaunchKernelGGL((mean_views_kernel<bf16_t>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)attn, (bf16_t*)out, V, n4);
+    hipLaunchKernelGGL((mean_views_kernel<bf16_t, LIVE>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)attn,
+                       (bf16_t*)out, V, n4, view_idx, n_live, stream4);
   else
     return MVG_E_BADARG;
   MVG_LAUNCH_CHECK();
   return 0;
+}
+}  // extern "C++"
+
+int mvg_mean_views(const void* attn, int dtype, void* out, int V, int rows, int C, void* stream) {
+  return launch_mean_views<false>(attn, dtype, out, V, 1, rows, C, nullptr, nullptr, stream);
+}
+
+int mvg_mean_views_live(const void* attn, int dtype, void* out, int V, int B, int rows, int C, const int32_t* view_idx,
+                        const int32_t* n_live, void* stream) {
+  return launch_mean_views<true>(attn, dtype, out, V, B, rows, C, view_idx, n_live, stream);
 }
 
 int mvg_add_layernorm(const float* res, const void* h, int h_dtype, const float* gamma, const float* beta, float* y,
@@ -1589,13 +1700,21 @@ int mvg_rowdot3(const void* h, int h_dtype, const float* W3, const float* b3, fl
 
 static int launch_triangulate(const float* r, const float* o, const float* cams, const uint8_t* valid, const int* any_valid,
                               float* new_ref, float* ref2d, float* proj2d, int V, int B, int NQ, int J, const LevelTable& lv,
-                              float* r_next, float* ref_lvl_next, uint8_t* inside_next, void* stream) {
+                              float* r_next, float* ref_lvl_next, uint8_t* inside_next, void* stream,
+                              const int32_t* view_idx = nullptr, const int32_t* n_live = nullptr) {
   if (!r || !o || !cams || !valid || !any_valid || !new_ref || !ref2d || !proj2d || V <= 0) return MVG_E_BADARG;
+  if ((view_idx == nullptr) != (n_live == nullptr) || (view_idx && V > 64)) return MVG_E_BADARG;     // live_view_mask: 64 bits
   const long nprob = (long)B * NQ * J;            // 64 problems per 512-thread workgroup (8 lanes each in phase 1)
   if (nprob == 0) return 0;
   // (a lane-parallel Jacobi -- triangulate_kernel<true>, bit-identical -- measured 2.3 % slower in the forward: not instantiated)
-  hipLaunchKernelGGL(triangulate_kernel<false>, dim3(mvg_ceil_div(nprob, TRI_PROBS)), dim3(512), 0, (hipStream_t)stream, r, o,
-                     cams, valid, any_valid, new_ref, ref2d, proj2d, V, B, NQ, J, lv, r_next, ref_lvl_next, inside_next);
+  if (view_idx)
+    hipLaunchKernelGGL((triangulate_kernel<false, true>), dim3(mvg_ceil_div(nprob, TRI_PROBS)), dim3(512), 0, (hipStream_t)stream,
+                       r, o, cams, valid, any_valid, new_ref, ref2d, proj2d, V, B, NQ, J, lv, r_next, ref_lvl_next, inside_next,
+                       view_idx, n_live);
+  else
+    hipLaunchKernelGGL((triangulate_kernel<false, false>), dim3(mvg_ceil_div(nprob, TRI_PROBS)), dim3(512), 0, (hipStream_t)stream,
+                       r, o, cams, valid, any_valid, new_ref, ref2d, proj2d, V, B, NQ, J, lv, r_next, ref_lvl_next, inside_next,
+                       view_idx, n_live);
   MVG_LAUNCH_CHECK();
   return 0;
 }
@@ -1618,6 +1737,28 @@ int mvg_triangulate_project(const float* r, const float* o, const float* cams, c
   if (e) return e;
   return launch_triangulate(r, o, cams, valid, any_valid, new_ref, ref2d, proj2d, V, B, NQ, J, lv, r_next, ref_lvl_next,
                             inside_next, stream);
+}
+
+int mvg_triangulate_live(const float* r, const float* o, const float* cams, const uint8_t* valid, const int* any_valid,
+                         float* new_ref, float* ref2d, float* proj2d, int V, int B, int NQ, int J, const int32_t* view_idx,
+                         const int32_t* n_live, void* stream) {
+  if (!view_idx || !n_live) return MVG_E_BADARG;
+  LevelTable lv = {};
+  return launch_triangulate(r, o, cams, valid, any_valid, new_ref, ref2d, proj2d, V, B, NQ, J, lv, nullptr, nullptr, nullptr,
+                            stream, view_idx, n_live);
+}
+
+int mvg_triangulate_project_live(const float* r, const float* o, const float* cams, const uint8_t* valid, const int* any_valid,
+                                 float* new_ref, float* ref2d, float* proj2d, int V, int B, int NQ, int J,
+                                 const int64_t* shapes_host, int L, float* r_next, float* ref_lvl_next, uint8_t* inside_next,
+                                 const int32_t* view_idx, const int32_t* n_live, void* stream) {
+  if (!shapes_host || !r_next || !ref_lvl_next || !inside_next || !view_idx || !n_live) return MVG_E_BADARG;
+  LevelTable lv;
+  int64_t zeros[MVG_MAX_LEVELS] = {0};
+  int e = mvg_fill_levels(&lv, shapes_host, zeros, L);
+  if (e) return e;
+  return launch_triangulate(r, o, cams, valid, any_valid, new_ref, ref2d, proj2d, V, B, NQ, J, lv, r_next, ref_lvl_next,
+                            inside_next, stream, view_idx, n_live);
 }
 
 int mvg_uncrop_undistort_jac(const float* ref2d, const float* cams, float* ud, float* jac, int V, int B, int Lq, void* stream) {

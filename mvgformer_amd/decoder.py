@@ -98,12 +98,47 @@ LayerPlan.__doc__ = """What one DQDecoderLayer.forward_features call runs (DQDec
 LayerOperands = collections.namedtuple("LayerOperands", "sampler self_attn chain_a o_masked pose masked_rows chain_b")
 
 
+def live_view_table(mask, B, V):
+    """The live-view table of DecoderContext.set_live_views as host arrays: mask (B, V) or (V,) -- bool; a sequence, a numpy array or
+    a CPU tensor -- -> (view_idx (B, V) int32: the live views of stream b in ascending order, padded with -1; n_live (B) int32).
+    A device tensor is refused (validating it would need a read-back), and so is a stream without a live view."""
+    import numpy as np
+    if torch.is_tensor(mask):
+        if mask.device.type != "cpu":
+            raise TypeError("set_live_views: the mask is validated on the host -- a CPU tensor, numpy array or sequence, not a "
+                            "tensor on %s" % (mask.device,))
+        mask = mask.detach().numpy()
+    m = np.asarray(mask)
+    if m.dtype != np.bool_:
+        if m.dtype.kind not in "iu" or ((m != 0) & (m != 1)).any():
+            raise ValueError("set_live_views: a bool mask expected (got dtype %s)" % (m.dtype,))
+        m = m.astype(np.bool_)
+    if m.shape == (V,):
+        m = np.broadcast_to(m, (B, V))
+    if m.shape != (B, V):
+        raise ValueError("set_live_views: mask of shape (%d, %d) or (%d,) expected, got %s" % (B, V, V, tuple(m.shape)))
+    n_live = m.sum(1).astype(np.int32)
+    if (n_live == 0).any():
+        raise ValueError("set_live_views: stream %d has no live view" % int(np.flatnonzero(n_live == 0)[0]))
+    view_idx = np.full((B, V), -1, dtype=np.int32)
+    for b in range(B):
+        view_idx[b, :n_live[b]] = np.flatnonzero(m[b])
+    return view_idx, n_live
+
+
 class DecoderContext:
     """Per-forward, layer-independent state: level table + packed cameras (host side, built from
     ``meta``) and the packed channels-last pyramid (device side, built from ``src_views``).
 
     ``prepare`` touches host memory (it reads the small camera tensors of ``meta``), ``pack`` only
     enqueues kernels -- so a HIP-graph capture can call ``pack`` with a prepared context."""
+
+    # live-view table (set_live_views).  Class defaults: a context that never had a table carries no field for it.
+    #   live          None (no table: the launches without one), or the static device pair (view_idx (B, V) i32, n_live (B) i32)
+    #   live_buffers  that pair, from the first table on and for good: switching the table off and on again refills the SAME
+    #                 tensors, so a graph captured with them keeps addressing live memory
+    #   live_staging  (pinned host pair, event recorded behind their last copy) on a CUDA context
+    live = live_buffers = live_staging = None
 
     def __init__(self, levels=None, cams=None, V=0, B=0, dtype=torch.float32):
         self.levels, self.cams, self.V, self.B, self.dtype = levels, cams, V, B, dtype
@@ -113,6 +148,40 @@ class DecoderContext:
         # training constants of a context that outlives its forward (training.GraphedTrainStep): the projection matrices of the camera
         # records, the (pointer, version) of the records they were built from, the head's initial reference points
         self.train_Pm = self.train_key = self.train_ref = None
+
+    def set_live_views(self, mask):
+        """Which of the V views take part, per stream: mask (B, V) or (V,) bool -- a sequence, a numpy array or a CPU tensor; None
+        switches the table off (every launch is then the one without a table; the buffers stay, and ``tensors()`` keeps pinning
+        them).  Fills the two static device buffers of ``live`` (live_view_table; allocated by the first call and refilled in
+        place ever after: a captured graph addresses them) with one small H2D copy each on the current stream.  On a CUDA context
+        the copies leave from two pinned host buffers the context keeps, so they are asynchronous; before refilling those the host
+        waits for the event behind the PREVIOUS call's copies (16 + 4 V bytes per stream: long done in a frame loop) -- no device
+        synchronisation, nothing waits for the forward.  The forward then gives, bit for bit, what it gives on the live views alone
+        (2D outputs of dead views: zeros).  One live view means what a V = 1 run means."""
+        if mask is None:
+            self.live = None
+            return self
+        host = tuple(torch.from_numpy(t) for t in live_view_table(mask, self.B, self.V))
+        cuda = self.cams.is_cuda
+        if self.live_buffers is None:
+            if cuda and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("set_live_views: first call inside a HIP-graph capture; set a table before capturing")
+            self.live_buffers = tuple(torch.empty(t.shape, dtype=torch.int32, device=self.cams.device) for t in host)
+            if cuda:
+                self.live_staging = (tuple(torch.empty(t.shape, dtype=torch.int32).pin_memory() for t in host), torch.cuda.Event())
+        if cuda:
+            with torch.cuda.device(self.cams.device):
+                pinned, sent = self.live_staging
+                sent.synchronize()          # the copies of the previous table have left the pinned buffers (no-op the first time)
+                for dst, stage, src in zip(self.live_buffers, pinned, host):
+                    stage.copy_(src)
+                    dst.copy_(stage, non_blocking=True)
+                sent.record()
+        else:
+            for dst, src in zip(self.live_buffers, host):
+                dst.copy_(src)
+        self.live = self.live_buffers
+        return self
 
     @classmethod
     def prepare(cls, spatial_shapes, level_start_index, meta, img_size, dtype, batch_size, device):
@@ -161,7 +230,8 @@ class DecoderContext:
 
     def tensors(self):
         """the device tensors the context holds (what a captured graph addresses and does not own)"""
-        return [t for t in (self.cams, self.feat, self._buffer, self.train_Pm, self.train_ref) if t is not None]
+        return [t for t in (self.cams, self.feat, self._buffer, self.train_Pm, self.train_ref) + (self.live_buffers or ())
+                if t is not None]
 
     @classmethod
     def build(cls, src_views, spatial_shapes, level_start_index, meta, img_size, dtype, batch_size):
@@ -202,6 +272,13 @@ class DecoderRun:
         """the current layer's slices of the stacked buffers: (hidden state, any-valid flag int32[1], (3D, 2D, projected 2D)) or None"""
         return (None if self.hs_buf is None else self.hs_buf[self.i], None if self.flags is None else self.flags[self.i:self.i + 1],
                 None if self.geo_buf is None else tuple(buf[self.i] for buf in self.geo_buf))
+
+
+def refuse_live_views(ctx, who):
+    """the paths that are not built for a live-view table (DecoderContext.set_live_views) say so by name, before any launch"""
+    if ctx is not None and getattr(ctx, "live", None) is not None:
+        raise NotImplementedError("%s: not built for a live-view table (DecoderContext.set_live_views); run it on all views, or on "
+                                  "a rig of the live views" % who)
 
 
 _NO_RUN = DecoderRun((), None, False)       # what a layer called on its own sees: no context, no next layer, no preallocated outputs
@@ -556,13 +633,19 @@ class DQDecoderLayer(MvPDecoderLayer):
             return self._forward(tgt, query_pos, reference_points, src_views, src_spatial_shapes, level_start_index, meta,
                                  indices, threshold)
 
+    def takes_autograd_path(self, tgt):
+        """True when forward() on tgt runs forward_autograd instead of the native kernels: under autograd, or in train() mode with
+        active dropout.  The ONE statement of that rule (_forward takes the path by it, DQDecoder.forward refuses by it)."""
+        dropping = self.training and max(self.dropout2.p, self.dropout3.p, self.dropout4.p) > 0
+        return bool(dropping or (torch.is_grad_enabled()
+                                 and (tgt.requires_grad or any(p.requires_grad for p in self.parameters()))))
+
     def _forward(self, tgt, query_pos, reference_points, src_views, src_spatial_shapes, level_start_index, meta, indices,
                  threshold):
         # The native path has no dropout: it is the eval()-mode layer.  Under autograd, and in train() mode with active
         # dropout (validation inside a training loop without .eval(), MC-dropout), the differentiable torch path runs,
         # which applies dropout2/3/4 like the reference (dq_decoder.py:776, mvp_decoder.py:94-98).
-        dropping = self.training and max(self.dropout2.p, self.dropout3.p, self.dropout4.p) > 0
-        if dropping or (torch.is_grad_enabled() and (tgt.requires_grad or any(p.requires_grad for p in self.parameters()))):
+        if self.takes_autograd_path(tgt):
             return self.forward_autograd(tgt, query_pos, reference_points, src_views, src_spatial_shapes,
                                          level_start_index, meta, indices, threshold)
         ctx = (self._run or _NO_RUN).ctx
@@ -616,6 +699,7 @@ class DQDecoderLayer(MvPDecoderLayer):
           softmax, dropout, sigmoid, the sampling op's locations / weights / gradients (fp32), UncropUndistort (fp32),
           DenseDLT (fp64) -- is the fp32 path's arithmetic."""
         from . import geometry_torch as G
+        refuse_live_views((self._run or _NO_RUN).ctx, "DQDecoderLayer.forward_autograd")
         B, Lq, C = tgt.shape
         J = self.num_joints
         NQ = Lq // J
@@ -751,7 +835,7 @@ class DQDecoderLayer(MvPDecoderLayer):
         if proj_in is not None and proj_in[0].data_ptr() == X.data_ptr() and tuple(proj_in[0].shape) == tuple(X.shape):
             r, ref_lvl, inside = proj_in[1]      # projected by the previous layer's triangulation launch (same arithmetic)
         else:
-            r, ref_lvl, inside = ops.project(X, ctx.cams, ctx.levels, V, B)
+            r, ref_lvl, inside = ops.project(X, ctx.cams, ctx.levels, V, B, live=ctx.live)
         qt = tgt if query_tgt is None else query_tgt
         x = lambda: self.with_pos_embed(qt.float(), None if query_pos is None else query_pos.float()).contiguous()
         if (query_pos is not None and qt.dtype == torch.float32 and query_pos.dtype == torch.float32 and qt.is_contiguous()
@@ -797,18 +881,19 @@ class DQDecoderLayer(MvPDecoderLayer):
             if plan.chain_b == "f32h":
                 res = ops.chain_update_ffn_class_f32h(
                     attn, V, tgt32, *w.chain_b, threshold, B, NQ, J, forced, self.open_forward_ffn,
-                    tgt_out=tgt_out, any_valid=flag, next_query_proj=next_proj)
+                    tgt_out=tgt_out, any_valid=flag, next_query_proj=next_proj, live=ctx.live)
             else:
                 res = ops.chain_update_ffn_class(
                     attn, V, tgt32, *w.chain_b, threshold, B, NQ, J, forced, self.open_forward_ffn,
                     tgt_out=tgt_out, any_valid=flag, next_query_proj=next_proj,
-                    attn_inside=inside.view(-1) if plan.chain_a == "bf16" else None)   # chain A wrote zeros for the pairs outside their image
+                    attn_inside=inside.view(-1) if plan.chain_a == "bf16" else None,   # chain A wrote zeros for the pairs outside their image
+                    live=ctx.live)
             tgt_update, prob, valid, any_valid = res[:4]
             if next_proj is not None:
                 run.xw_in[run.i + 1] = res[4]
         else:
             Wu, bu, g2, b2, W1, b1, W2, bb2, g3, b3, Wc, bc = w.chain_b
-            u = ops.linear(ops.mean_views(attn, V), Wu, bu, out_dtype=dt)
+            u = ops.linear(ops.mean_views(attn, V, live=ctx.live), Wu, bu, out_dtype=dt)
             tgt_update = ops.add_layernorm(tgt32, u, g2, b2)
             if self.open_forward_ffn:
                 h = ops.linear(tgt_update, W1, b1, out_dtype=dt, relu=True)
@@ -837,7 +922,8 @@ class DQDecoderLayer(MvPDecoderLayer):
         run = self._run or _NO_RUN
         boundary = self.fuse_boundary and run.next_layer() is not None     # the next layer's projection of the new points rides on this launch
         new_ref, ref2d, proj2d, *proj = ops.triangulate(st["r"], st["o"], ctx.cams, st["valid"], st["any_valid"], V, B, NQ, J,
-                                                        out=run.outputs()[2], next_levels=ctx.levels if boundary else None)
+                                                        out=run.outputs()[2], next_levels=ctx.levels if boundary else None,
+                                                        live=ctx.live)
         if boundary:
             run.proj_in[run.i + 1] = (new_ref, proj[0])
         return st["tgt_update"], new_ref, ref2d, proj2d, st["prob"]
@@ -1047,17 +1133,19 @@ class DQDecoder(MvPDecoder):
 
     def forward(self, tgt, reference_points, src_views, meta, src_spatial_shapes, src_level_start_index,
                 src_valid_ratios, query_pos=None, src_padding_mask=None, rgb_views=None, output_dir="./",
-                frame_id=None, indices=None, threshold=0.5, indices_all=None, context=None):
+                frame_id=None, indices=None, threshold=0.5, indices_all=None, context=None, view_live=None):
         """Returns (hs (layers,B,Lq,C), refs (layers,B,Lq,3), refs2d (layers,B,V,Lq,2),
         projs2d (layers,B,V,Lq,2), [class_prob (B,NQ,2)] * layers) when return_intermediate,
         else (output, reference_points, ref_points_2d).  ``context`` (optional, beyond the reference
         signature): a DecoderContext.prepare(...)d context, so the host-side camera packing is
-        hoisted out of a captured HIP graph."""
+        hoisted out of a captured HIP graph.  ``view_live`` (optional, beyond the reference signature): the mask of
+        DecoderContext.set_live_views, set on the context of this call -- the outputs are, bit for bit, those of a run on the live
+        views alone, with zeros in the 2D slots of the others; None leaves a given context's table as it is."""
         if tgt.is_cuda and tgt.device.index != torch.cuda.current_device():
             with torch.cuda.device(tgt.device):     # kernels go to the current stream of the TENSORS' device
                 return self.forward(tgt, reference_points, src_views, meta, src_spatial_shapes, src_level_start_index,
                                     src_valid_ratios, query_pos, src_padding_mask, rgb_views, output_dir, frame_id, indices,
-                                    threshold, indices_all, context)
+                                    threshold, indices_all, context, view_live)
         output = tgt
         layer0 = self.layers[0]
         ctx = context
@@ -1074,6 +1162,14 @@ class DQDecoder(MvPDecoder):
                 deferred_pack = src_views
             elif ctx.feat is None:
                 raise RuntimeError("DQDecoder.forward: context without a packed pyramid and no src_views")
+            if view_live is not None:
+                ctx.set_live_views(view_live)
+            if ctx.live is not None:
+                if not tgt.is_cuda:
+                    raise NotImplementedError("DQDecoder.forward: a live-view table needs the HIP path")
+                # (a later layer's input requires grad exactly when some layer before it took the autograd path or tgt does)
+                if any(layer.takes_autograd_path(tgt) for layer in self.layers):
+                    refuse_live_views(ctx, "DQDecoder.forward (the layers' forward_autograd)")      # before the pack: no launch
             inter, inter_ref, inter_2d, inter_proj, classes = [], [], [], [], []
             ref_points_2d = None
             with DecoderRun(self.layers, ctx, self.fuse_next_query_term) as run:

@@ -22,7 +22,7 @@ from __future__ import annotations
 import torch
 import torch.distributed as dist
 
-from .decoder import DecoderRun
+from .decoder import DecoderRun, refuse_live_views
 
 
 def refuse_coupled_queries(decoder):
@@ -113,6 +113,7 @@ def sharded_decoder_forward(decoder, tgt, reference_points, src_views, meta, spa
                             query_pos, threshold, group=None, gather_hidden=False, context=None):
     """Run DQDecoder.forward on this rank's block of queries and all-gather the pose set."""
     refuse_coupled_queries(decoder)
+    refuse_live_views(context, "dist.sharded_decoder_forward")
     world = dist.get_world_size(group)
     rank = dist.get_rank(group)
     J = decoder.layers[0].num_joints
@@ -160,6 +161,7 @@ class GraphedShardedDecoder:
     def __init__(self, decoder, tgt, reference_points, src_views, query_pos, ctx, threshold, NQ, group=None,
                  gather_hidden=False):
         refuse_coupled_queries(decoder)
+        refuse_live_views(ctx, "dist.GraphedShardedDecoder")
         self.dec, self.ctx, self.group, self.thr, self.NQ = decoder, ctx, group, threshold, NQ
         self.tgt, self.ref, self.src, self.qpos = tgt, reference_points, src_views, query_pos
         self.world, self.rank = dist.get_world_size(group), dist.get_rank(group)

@@ -287,12 +287,27 @@ def pack_pyramid(src_views, levels, dtype, out=None):
     return feat
 
 
-def project(X, cams, levels, V, B):
+def _live_table(who, live, V, B, device):
+    """live = (view_idx (B, V) i32, n_live (B) i32) on `device` (DecoderContext.set_live_views builds them) -> the pair, checked"""
+    view_idx, n_live = live
+    for t, shp in ((view_idx, (B, V)), (n_live, (B,))):
+        if (not torch.is_tensor(t) or t.dtype != torch.int32 or tuple(t.shape) != shp or not t.is_contiguous()
+                or t.device != torch.device(device)):
+            raise RuntimeError("%s: live = (view_idx (%d, %d), n_live (%d,)) contiguous int32 on %s expected" % (who, B, V, B, device))
+    return view_idx, n_live
+
+
+def project(X, cams, levels, V, B, live=None):
+    """live: the live-view table (_live_table); pairs of a dead view get inside = 0, r = ref_lvl = 0"""
     Lq = X.shape[1]
     r = torch.empty((V * B, Lq, 2), dtype=torch.float32, device=X.device)
     ref_lvl = torch.empty((V * B, Lq, levels.L, 2), dtype=torch.float32, device=X.device)
     inside = torch.empty((V * B, Lq), dtype=torch.uint8, device=X.device)
-    _launch("mvg_project", X, cams, levels.shapes_c, levels.L, r, ref_lvl, inside, V, B, Lq)
+    if live is not None:
+        _launch("mvg_project_live", X, cams, levels.shapes_c, levels.L, r, ref_lvl, inside, V, B, Lq,
+                *_live_table("mvg_project_live", live, V, B, X.device))
+    else:
+        _launch("mvg_project", X, cams, levels.shapes_c, levels.L, r, ref_lvl, inside, V, B, Lq)
     return r, ref_lvl, inside
 
 
@@ -614,7 +629,7 @@ def chain_masked_row_output_f32h(Wp, swp, bp, W0, sw0, b0, W1, sw1, b1, W2, b2):
 
 
 def chain_update_ffn_class_f32h(attn, V, tgt, Wu, su, bu, g2, be2, W1, s1, b1, W2, s2, b2, g3, be3, Wc, bc, threshold, B, NQ, J,
-                                forced_valid=None, has_ffn=True, tgt_out=None, any_valid=None, next_query_proj=None):
+                                forced_valid=None, has_ffn=True, tgt_out=None, any_valid=None, next_query_proj=None, live=None):
     """fp32 chain B on two-part fp16 operands (include/mvg_decoder.h: mvg_chain_update_ffn_class_f32h); arguments and results as
     chain_update_ffn_class, attn (V * rows, 256) f32, weights (planes, scale) from split_swizzle_weight_h2, next_query_proj = (qpos, Wn, sn, bn, n_next)."""
     dev = attn.device
@@ -642,9 +657,11 @@ def chain_update_ffn_class_f32h(attn, V, tgt, Wu, su, bu, g2, be2, W1, s1, b1, W
         xw_next = torch.empty((rows, n_next), dtype=torch.float32, device=dev)
     if any_valid is None:
         any_valid = torch.zeros((1,), dtype=torch.int32, device=dev)
-    _launch("mvg_chain_update_ffn_class_f32h", attn, V, tgt, Wu, int(su), bu, g2, be2, W1, int(s1 or 0), b1, W2, int(s2 or 0), b2, g3,
+    sym = "mvg_chain_update_ffn_class_f32h" if live is None else "mvg_chain_update_ffn_class_f32h_live"
+    _launch(sym, attn, V, tgt, Wu, int(su), bu, g2, be2, W1, int(s1 or 0), b1, W2, int(s2 or 0), b2, g3,
             be3, Wc, bc, float(threshold), forced_valid, tgt_out, prob, valid, any_valid, qpos, Wn, int(sn), bn, xw_next, n_next,
-            B, NQ, J, 1 if has_ffn else 0, label="chain_update_ffn_class_f32h")
+            B, NQ, J, 1 if has_ffn else 0, *(() if live is None else _live_table(sym, live, V, B, dev)),
+            label="chain_update_ffn_class_f32h")
     if next_query_proj is not None:
         return tgt_out, prob, valid, any_valid, xw_next
     return tgt_out, prob, valid, any_valid
@@ -680,9 +697,11 @@ def chain_masked_row_output(Wp, bp, W0, b0, W1, b1, W2, b2):
 
 
 def chain_update_ffn_class(attn, V, tgt, Wu, bu, g2, be2, W1, b1, W2, b2, g3, be3, Wc, bc, threshold, B, NQ, J,
-                           forced_valid=None, has_ffn=True, tgt_out=None, any_valid=None, next_query_proj=None, attn_inside=None):
+                           forced_valid=None, has_ffn=True, tgt_out=None, any_valid=None, next_query_proj=None, attn_inside=None,
+                           live=None):
     """fused view-mean + update MLP + LN2 + FFN + LN3 + class head (weights in swizzle_weight order).
     attn_inside (V * rows) u8: chain A's in-image flags -- attn rows with flag 0 are zero and are not read.
+    live: the live-view table (_live_table) -- the mean is the one over the live views of the row's stream.
     Returns (tgt_update f32 (B*NQ*J,256), prob (B,NQ,2), valid (B,NQ) u8, any_valid int32[1])."""
     dev = attn.device
     rows = B * NQ * J
@@ -707,18 +726,27 @@ def chain_update_ffn_class(attn, V, tgt, Wu, bu, g2, be2, W1, b1, W2, b2, g3, be
         any_valid = torch.zeros((1,), dtype=torch.int32, device=dev)
     if attn_inside is not None:
         assert attn_inside.dtype == torch.uint8 and attn_inside.numel() == V * rows and attn_inside.is_contiguous()
-    _launch("mvg_chain_update_ffn_class", attn, V, tgt, Wu, bu, g2, be2, W1, b1, W2, b2, g3, be3, Wc, bc, float(threshold),
+    sym = "mvg_chain_update_ffn_class" if live is None else "mvg_chain_update_ffn_class_live"
+    _launch(sym, attn, V, tgt, Wu, bu, g2, be2, W1, b1, W2, b2, g3, be3, Wc, bc, float(threshold),
             forced_valid, tgt_out, prob, valid, any_valid, qpos, Wn, bn, xw_next, n_next, B, NQ, J, 1 if has_ffn else 0, attn_inside,
-            label="chain_update_ffn_class")
+            *(() if live is None else _live_table(sym, live, V, B, dev)), label="chain_update_ffn_class")
     if next_query_proj is not None:
         return tgt_out, prob, valid, any_valid, xw_next
     return tgt_out, prob, valid, any_valid
 
 
-def mean_views(attn, V):
+def mean_views(attn, V, live=None):
+    """live: the live-view table (_live_table; its B streams split the rows evenly) -- the mean over the live views of the row's stream"""
     rows = attn.shape[0] // V
     out = torch.empty((rows, attn.shape[1]), dtype=attn.dtype, device=attn.device)
-    _launch("mvg_mean_views", attn, L.dtype_code(attn.dtype), out, V, rows, attn.shape[1])
+    if live is not None:
+        B = live[1].shape[0]
+        if rows % B:
+            raise RuntimeError("mvg_mean_views_live: %d rows do not split into %d streams" % (rows, B))
+        _launch("mvg_mean_views_live", attn, L.dtype_code(attn.dtype), out, V, B, rows, attn.shape[1],
+                *_live_table("mvg_mean_views_live", live, V, B, attn.device))
+    else:
+        _launch("mvg_mean_views", attn, L.dtype_code(attn.dtype), out, V, rows, attn.shape[1])
     return out
 
 
@@ -838,8 +866,10 @@ def rowdot3(h, W3, b3):
     return o
 
 
-def triangulate(r, o, cams, valid, any_valid, V, B, NQ, J, out=None, next_levels=None):
-    """out: optional caller-owned (new_ref (B,Lq,3), ref2d (B,V,Lq,2), proj2d (B,V,Lq,2)) contiguous f32 destinations
+def triangulate(r, o, cams, valid, any_valid, V, B, NQ, J, out=None, next_levels=None, live=None):
+    """live: the live-view table (_live_table) -- the problem of a token is the one of its stream's live views; 2D outputs and next
+    projections of dead views are zeros.
+    out: optional caller-owned (new_ref (B,Lq,3), ref2d (B,V,Lq,2), proj2d (B,V,Lq,2)) contiguous f32 destinations
     (e.g. slices of the stacked per-layer outputs).  next_levels (a Levels): also project the new points for the next
     layer in the same launch -> returns (new_ref, ref2d, proj2d, (r_next, ref_lvl_next, inside_next))."""
     Lq = NQ * J
@@ -852,15 +882,16 @@ def triangulate(r, o, cams, valid, any_valid, V, B, NQ, J, out=None, next_levels
         new_ref = torch.empty((B, Lq, 3), dtype=torch.float32, device=dev)
         ref2d = torch.empty((B, V, Lq, 2), dtype=torch.float32, device=dev)
         proj2d = torch.empty((B, V, Lq, 2), dtype=torch.float32, device=dev)
+    sfx, tab = ("", ()) if live is None else ("_live", _live_table("mvg_triangulate_live", live, V, B, dev))
     if next_levels is not None:
         lv = next_levels
         r_n = torch.empty((V * B, Lq, 2), dtype=torch.float32, device=dev)
         ref_n = torch.empty((V * B, Lq, lv.L, 2), dtype=torch.float32, device=dev)
         in_n = torch.empty((V * B, Lq), dtype=torch.uint8, device=dev)
-        _launch("mvg_triangulate_project", r, o, cams, valid, any_valid, new_ref, ref2d, proj2d, V, B, NQ, J, lv.shapes_c, lv.L,
-                r_n, ref_n, in_n, label="triangulate_project")
+        _launch("mvg_triangulate_project" + sfx, r, o, cams, valid, any_valid, new_ref, ref2d, proj2d, V, B, NQ, J, lv.shapes_c, lv.L,
+                r_n, ref_n, in_n, *tab, label="triangulate_project")
         return new_ref, ref2d, proj2d, (r_n, ref_n, in_n)
-    _launch("mvg_triangulate", r, o, cams, valid, any_valid, new_ref, ref2d, proj2d, V, B, NQ, J, label="triangulate")
+    _launch("mvg_triangulate" + sfx, r, o, cams, valid, any_valid, new_ref, ref2d, proj2d, V, B, NQ, J, *tab, label="triangulate")
     return new_ref, ref2d, proj2d
 
 

@@ -44,7 +44,9 @@ evaluator's person slots: ``max_persons`` defaults to the evaluator's and may no
 the 15-joint tree.  ``refined`` = ``(poses (B, dets_rows, J, 3) fp32, status (B, dets_rows) int32)`` per row of ``detections[0]``
 (status 0: solved; rows behind the count: zeros, -1) and ``bone_lengths`` (J-1) fp32 are static tensors: new lengths written into
 ``bone_lengths`` take effect at the next run.  The projection matrices ``Pm`` come from the packed camera records and follow
-``set_cameras``.
+``set_cameras``.  With a live-view table (``set_live_views``: the decoder context's, ``serving.GraphedDecoder(live_views=True)``) the
+solver gets view weights ``conf`` (B, V, NQ*J) fp32 -- ``1 / n_live[b]`` for the live views of stream b, 0 for the others, built from
+the table by launches -- so that a dead view's (zero) 2D points add exact zeros to its sums.
 
 ``refine=dict(bone_lengths="track", window=8, min_frames=4, fallback=None | <J-1 values>, n_steps=1, method="ST")`` (requires
 ``tracking`` as well) puts ``structural.BoneLengthEstimator.update`` behind the tracker (and ``track_evaluation``) and in front of
@@ -122,6 +124,7 @@ class PostProcess:
         rows = dets.shape[1]
         self.stages = []                            # (stage object, its launch: refs2d -> None) in launch order
         self.cams, self.Pm = None, None             # set_cameras
+        self.live = None                            # set_live_views
         # scoring of the kept poses against ground truth
         self.evaluator = None
         if evaluation is not None:
@@ -171,7 +174,8 @@ class PostProcess:
             self.refiner = StructuralRefiner(batch=batch, rows=rows, parent=PANOPTIC15_PARENT, device=dev, **refine)
             self.refined = (self.refiner.poses, self.refiner.status)
             self.bone_lengths = self.refiner.bone_lengths
-            self.stages.append((self.refiner, lambda refs2d: self.refiner.update(refs2d, self.cams, self.Pm, keep, count)))
+            self.stages.append((self.refiner, lambda refs2d: self.refiner.update(refs2d, self.cams, self.Pm, keep, count,
+                                                                                 conf=self.view_weights(refs2d))))
         # the static ground-truth inputs, shared by the two scorers: slot g is identity g until load_ground_truth says otherwise
         self.ground_truth, self.person_id = None, None
         scorer = self.evaluator or self.track_evaluator
@@ -218,6 +222,31 @@ class PostProcess:
                 self.Pm.copy_(fresh)
         return self
 
+    def set_live_views(self, live):
+        """live: the decoder context's live-view table (``DecoderContext.live``: view_idx (B, V) i32, n_live (B) i32 on the device),
+        kept by reference, or None; only ``refine`` reads it (``view_weights``)"""
+        if live is not None:
+            view_idx, n_live = live
+            if (view_idx.dtype != torch.int32 or n_live.dtype != torch.int32 or view_idx.dim() != 2
+                    or tuple(n_live.shape) != (view_idx.shape[0],)):
+                raise ValueError("PostProcess: live = (view_idx (B, V) int32, n_live (B) int32) expected")
+        self.live = live
+        return self
+
+    def view_weights(self, refs2d):
+        """the refiner's conf (B, V, NQ*J) fp32 from the live-view table -- 1 / n_live[b] (an fp32 division) for the live views of
+        stream b, 0 for the others -- or None without a table.  Torch launches on the table's device tensors: no read-back."""
+        if self.live is None:
+            return None
+        view_idx, n_live = self.live
+        B, V, Lq = refs2d.shape[:3]
+        if tuple(view_idx.shape) != (B, V):
+            raise ValueError("PostProcess: live-view table for %s, 2D points of (%d, %d)" % (tuple(view_idx.shape), B, V))
+        views = torch.arange(V, dtype=torch.int32, device=view_idx.device)
+        live = (view_idx.unsqueeze(2) == views.view(1, 1, V)).any(1)                  # (B, V): view v is in the row of stream b
+        w = live.to(torch.float32) / n_live.to(torch.float32).unsqueeze(1)
+        return w.unsqueeze(2).expand(B, V, Lq).contiguous()
+
     # ------------------------------------------------------------------ the chain: launches only
     def run(self, outputs):
         """the five outputs of ``DQDecoder.forward`` -> the packed predictions (B, NQ, J, 5), every stage launched behind them"""
@@ -247,5 +276,5 @@ class PostProcess:
 
     def tensors(self):
         """every device tensor a captured ``run`` addresses by raw pointer and does not allocate itself"""
-        own = list(self.nms.values()) + list(self.ground_truth or ()) + [self.person_id, self.Pm]
+        own = list(self.nms.values()) + list(self.ground_truth or ()) + [self.person_id, self.Pm] + list(self.live or ())
         return [t for t in own + [t for s, _ in self.stages for t in s.tensors()] if t is not None]

@@ -48,7 +48,7 @@ from .decoder import DecoderContext
 class GraphedDecoder:
     def __init__(self, decoder, meta, spatial_shapes, level_start_index, batch, num_queries, threshold=0.1, device=None,
                  producer_writes_in_place=False, channels=256, postprocess=None, convert_joint_format_indices=None, evaluation=None,
-                 tracking=None, refine=None, track_evaluation=None):
+                 tracking=None, refine=None, track_evaluation=None, live_views=False):
         layer0 = decoder.layers[0]
         dev = torch.device(device) if device is not None else next(decoder.parameters()).device
         if dev.type != "cuda":
@@ -62,6 +62,11 @@ class GraphedDecoder:
         self.level_start_index = level_start_index.to(dev)
         self.meta = meta
         self.ctx = DecoderContext.prepare(self.spatial_shapes, self.level_start_index, meta, layer0.img_size, self.dtype, batch, dev)
+        # live_views: the graph is captured with the kernels that read the context's live-view table (all views live until
+        # load(view_live=...) says otherwise); without it the graph holds the launches without a table
+        self.live_views = bool(live_views)
+        if self.live_views:
+            self.ctx.set_live_views([True] * self.V)
         # static inputs
         self.tgt = torch.zeros((batch, Lq, C), dtype=torch.float32, device=dev)
         self.query_pos = torch.zeros((batch, Lq, C), dtype=torch.float32, device=dev)
@@ -83,15 +88,22 @@ class GraphedDecoder:
         if any(v is not None for v in stages.values()):
             from .postprocess import PostProcess
             self.post = PostProcess(batch, num_queries, J, self.thr, dev, convert_joint_format_indices=convert_joint_format_indices,
-                                    **stages).set_cameras(self.ctx.cams, self.V)
+                                    **stages).set_cameras(self.ctx.cams, self.V).set_live_views(self.ctx.live)
         for name in ("postprocess", "detections", "evaluator", "ground_truth", "tracker", "track_ids", "track_poses",
                      "track_evaluator", "person_id", "refiner", "refined", "bone_lengths", "bone_estimator", "bone_source"):
             setattr(self, name, getattr(self.post, name, None))         # static tensors and objects: bound once
 
     # ------------------------------------------------------------------ inputs (device-side copies on the current stream)
-    def load(self, src_views=None, tgt=None, query_pos=None, reference_points=None, ground_truth=None):
+    def load(self, src_views=None, tgt=None, query_pos=None, reference_points=None, ground_truth=None, view_live=None):
         """ground_truth: see ``postprocess.PostProcess.load_ground_truth`` (a runner built with ``evaluation`` or
-        ``track_evaluation``)"""
+        ``track_evaluation``).  view_live: the mask of ``DecoderContext.set_live_views`` -- (B, V) or (V,) bool on the host -- for a
+        runner built with ``live_views=True``: validated on the host and copied into the table's static buffers (two small H2D
+        copies; no re-capture, nothing inside ``replay()``).  It stays in force until the next one."""
+        if view_live is not None:
+            if not self.live_views:
+                raise RuntimeError("GraphedDecoder.load: view_live needs a runner built with live_views=True (the graph is "
+                                   "captured with the kernels that read the table)")
+            self.ctx.set_live_views(view_live)
         with torch.no_grad():
             if ground_truth is not None:
                 if self.post is None:

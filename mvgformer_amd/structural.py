@@ -82,8 +82,10 @@ class StructuralRefiner:
         """every device tensor ``update`` addresses besides its arguments (what a captured graph must keep alive)"""
         return list(self.buffers.values()) + [self.bone_lengths]
 
-    def update(self, refs2d, cams, Pm, keep, count):
-        """refs2d (B, V, NQ*J, 2) fp32 network-image px (the last layer's), cams the packed camera records, Pm (B, V, 3, 4) fp32, keep
+    def update(self, refs2d, cams, Pm, keep, count, conf=None):
+        """conf (B, V, NQ*J) fp32 or None: the views' weights in the solver's sums (ops.structural_triangulate); a view with weight 0
+        adds exact zeros.
+        refs2d (B, V, NQ*J, 2) fp32 network-image px (the last layer's), cams the packed camera records, Pm (B, V, 3, 4) fp32, keep
         (B, NQ) int32 and count (B, 2) int32 as ``ops.pose_nms`` leaves them -> (poses, status), static tensors that the next update
         overwrites: row r < count[b, 0] holds query keep[b, r], the others zeros and status -1.  Two launches."""
         from . import _lib as L, ops
@@ -91,7 +93,7 @@ class StructuralRefiner:
         with torch.cuda.device(refs2d.device) if refs2d.is_cuda else contextlib.nullcontext():
             B, V = refs2d.shape[:2]
             ud, _ = ops.uncrop_undistort_jac(refs2d, cams, V, B)
-            return ops.structural_triangulate(ud, None, Pm, self.parent, self.bone_lengths, rows=keep[:, :self.rows], count=count,
+            return ops.structural_triangulate(ud, conf, Pm, self.parent, self.bone_lengths, rows=keep[:, :self.rows], count=count,
                                               n_steps=self.n_steps, method=self.method, out=self.buffers)
 
 

@@ -29,7 +29,7 @@ import torch
 
 from . import ops
 from .caller import level_tables, total_loss
-from .decoder import DecoderContext
+from .decoder import DecoderContext, refuse_live_views
 
 TILE = ops.OPERANDS_TILE
 RECORD_WORDS = ops.OPERANDS_RECORD_WORDS
@@ -232,6 +232,7 @@ class GraphedTrainStep:
 
     # ------------------------------------------------------------------ the step
     def _step(self):
+        refuse_live_views(self.ctx, "GraphedTrainStep")
         out, loss_dict = self.head.forward_train(self.src_views, self.meta, self.spatial_shapes, self.level_start_index,
                                                  threshold=self.thr, context=self.ctx)
         total = total_loss(loss_dict, self.weight_dict)
@@ -303,6 +304,7 @@ class GraphedTrainStep:
     def replay(self):
         """one training step on the loaded inputs: (total loss, loss dict, gradient norm before clipping, out dict) -- the graph's
         static tensors, overwritten by the next replay"""
+        refuse_live_views(self.ctx, "GraphedTrainStep")
         if self.graph is None:
             self.capture()
         if self._grads() != self._grad_ptrs:

@@ -171,6 +171,25 @@ def pcp_report(kept, gts, gts_vis, evaluator=None):
             "recall500": round(100 * float(recall), 2)}
 
 
+def parse_view_subsets(text, views):
+    """--view-subsets "0,1,2;0,2,4;0,1,2,3,4" -> [(0, 1, 2), (0, 2, 4), (0, 1, 2, 3, 4)]: camera subsets of a rig of `views`
+    cameras, each sorted; an empty subset, a repeated camera or one outside the rig is a ValueError"""
+    out = []
+    for part in text.split(";"):
+        try:
+            subset = [int(v) for v in part.split(",") if v.strip()]
+        except ValueError:
+            raise ValueError("--view-subsets: %r is not a comma-separated list of camera numbers" % part) from None
+        if not subset:
+            raise ValueError("--view-subsets: empty subset in %r" % text)
+        if len(set(subset)) != len(subset):
+            raise ValueError("--view-subsets: camera repeated in %r" % part)
+        if min(subset) < 0 or max(subset) >= views:
+            raise ValueError("--view-subsets: %r names a camera outside 0 .. %d" % (part, views - 1))
+        out.append(tuple(sorted(subset)))
+    return out
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description="decoder-side validate_3d")
     ap.add_argument("--cfg", required=True, help="YAML entry point of the reference, or extract:<path relative to the reference>")
@@ -218,7 +237,13 @@ def main(argv=None):
                                                                    "are solved under its own lengths")
     ap.add_argument("--bone-fallback", default=None, help="--bone-lengths track: .npy file with the J-1 lengths of a row whose "
                                                           "track is younger (default: the lengths the row has itself)")
+    ap.add_argument("--view-subsets", default=None,
+                    help="camera subsets, e.g. \"0,1,2;0,2,4;0,1,2,3,4\" (the generalization experiment, configs/panoptic/"
+                         "generalization): the frames run once per subset through ONE runner and one capture (the decoder's "
+                         "live-view table, serving.GraphedDecoder(live_views=True)); a result row per threshold and subset")
     args = ap.parse_args(argv)
+    if args.view_subsets and args.device_refine and not args.graph:
+        ap.error("--view-subsets with --device-refine 1 gives the refiner its view weights through the runner: it requires --graph 1")
     track_lengths = args.bone_lengths == "track"
     if args.device_refine and not args.device_nms:
         ap.error("--device-refine 1 re-solves the rows of the device NMS: it requires --device-nms 1")
@@ -251,6 +276,13 @@ def main(argv=None):
         report["checkpoint"] = {"path": args.model_path, "missing_keys": missing[:8], "n_missing": len(missing),
                                 "n_ignored_keys_of_other_modules": len(ignored)}
     frames = list(npz_frames(args.frames_npz) if args.frames_npz else synthetic_frames(cfg, args.frames, args.seed))
+    subsets = [None]
+    if args.view_subsets:
+        try:
+            subsets = parse_view_subsets(args.view_subsets, len(frames[0][1]))
+        except ValueError as e:
+            ap.error(str(e))
+        report["view_subsets"] = [list(s) for s in subsets]
     results = []
     from . import caller, ops
     from .postprocess import PostProcess
@@ -300,10 +332,15 @@ def main(argv=None):
     stages = dict(postprocess={} if args.device_nms else None, convert_joint_format_indices=head.convert_joint_format_indices,
                   evaluation=evaluation, tracking=tracking, refine=refine, track_evaluation=track_evaluation)
     truths = track_gt or gt_dev
-    for thr in cfg.DECODER.inference_conf_thr:                                   # validate_3d.py:185
+    runner, post, fresh, runner_thr = None, None, None, None
+    for thr, subset in [(t, s) for t in cfg.DECODER.inference_conf_thr for s in subsets]:       # validate_3d.py:185
         preds, gts, gts_vis, t_dec, n_timed = [], [], [], 0.0, 0
         kept = []
-        runner, post = None, None               # post: fresh stages (tracker, accumulators) per threshold pass
+        view_live = None if subset is None else [v in subset for v in range(len(frames[0][1]))]
+        if thr != runner_thr:
+            runner, post, runner_thr = None, None, thr      # post: fresh stages (tracker, accumulators) per threshold pass ...
+        elif runner is not None and fresh is not None:
+            post.restore(fresh)                             # ... and per subset: the same runner, its stages as the capture left them
         if refine is not None:
             refine_sums = torch.zeros(4, dtype=torch.float64, device=dev)        # kept rows, solved rows, residual before, after
             source_sums = torch.zeros(3, dtype=torch.int64, device=dev)
@@ -315,16 +352,18 @@ def main(argv=None):
             if args.graph and runner is None:
                 # queries and initial poses do not depend on the frame (dq_transformer.py:394-432, 298-323): loaded once
                 shapes, starts = caller.level_tables(src)
-                runner = GraphedDecoder(head.decoder, meta, shapes, starts, 1, head.num_instance, thr, **stages)
+                runner = GraphedDecoder(head.decoder, meta, shapes, starts, 1, head.num_instance, thr, live_views=subset is not None,
+                                        **stages)
                 post = runner.post
                 qpos, tgt = caller.person_joint_queries(head.joint_embedding.weight, head.instance_embedding.weight, 1)
                 ref0 = caller.sample_space_reference_points(head.num_instance, head.space_size, head.space_center, 1, dev,
                                                             t_pose=head.t_pose)
                 runner.load(tgt=tgt, query_pos=qpos, reference_points=ref0).capture()
+                fresh = None if post is None else post.snapshot()
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             if runner is not None:
-                runner.set_cameras(meta).load(src_views=src, ground_truth=truths[fi] if truths else None)
+                runner.set_cameras(meta).load(src_views=src, ground_truth=truths[fi] if truths else None, view_live=view_live)
                 hs, refs, r2d, p2d, cls = runner.replay()
                 if args.device_nms:
                     pred = runner.pred.clone()                                   # static buffer: the next replay overwrites it
@@ -333,7 +372,7 @@ def main(argv=None):
                                                          head.convert_joint_format_indices)
                     pred = caller.pack_predictions(out, thr)                     # function.py:386-396
             else:
-                out, pred = head(src, meta, threshold=thr)                       # function.py:372-396
+                out, pred = head(src, meta, threshold=thr, view_live=view_live)  # function.py:372-396
             torch.cuda.synchronize()
             if fi > 0 or len(frames) == 1:          # the first frame builds the weight caches / captures the graph (one-time)
                 t_dec += time.perf_counter() - t0
@@ -371,6 +410,8 @@ def main(argv=None):
                "poses_after_nms": post.evaluator.state()["kept_rows"] if args.device_eval else int(sum(len(k) for k in kept)),
                "decoder_ms_per_frame": round(1e3 * t_dec / max(n_timed, 1), 3),    # host-timed, incl. the camera H2D copy
                "hip_graph": runner is not None}
+        if subset is not None:
+            row["view_subset"] = list(subset)
         if args.device_track:
             st = post.tracker.state()
             row["tracks"] = {k: st[k] for k in ("births", "deaths", "overflow", "dropped", "active")}
